@@ -392,6 +392,33 @@ def trained_like_weights(dm, seed=1):
     dm.transformer._packed = None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write `arrays` (name -> tensor: what the timed path returned in its last step) as out_dir/<name>.npy in float32, so that
+    two builds can be compared output for output.  Smallest first, each array is written whole while the total stays within
+    DUMP_LIMIT_BYTES; one that does not fit is replaced by a seeded sample of its elements (<name>.npy, flat order) and their
+    flat indices (<name>_index.npy, float64): the same elements for the same shapes on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    written = []
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > left:
+            n = min(a.size, left // 12)                            # 4 bytes per value + 8 per index
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.nbytes
+            written.append(f"{name}_index.npy")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written.append(f"{name}.npy {list(a.shape)}")
+    print(f"bench.py: outputs of the last timed step in {out_dir}: " + ", ".join(written), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -411,7 +438,12 @@ def main():
                     help="softmax P format of the sampler's attention (default: the library's, a8 at this length); DESIGN.md section 4")
     ap.add_argument("--trained-like", action="store_true", help="profiling passes only: run the whole bench on weights of a trained-like "
                                                                 "magnitude (peaky softmax rows) instead of the reference init")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: the decoded clips and the sampled tokens) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (a seeded sample of an array past that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -473,6 +505,8 @@ def main():
     assert tuple(clips.shape) == (B, 3, args.grid[0], args.grid[1] * 8, args.grid[2] * 8)
     assert torch.isfinite(clips).all()
     assert tok.dtype == torch.int64 and int(tok.min()) >= 0 and int(tok.max()) < args.codes, "a [MASK] or out-of-range token survived"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"clips": clips, "content_token": tok})
     rank_s = [dt]
     if world > 1:
         import torch.distributed as dist

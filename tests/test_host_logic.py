@@ -76,32 +76,46 @@ def test_compose_and_instantiate_reference_targets(monkeypatch):
     assert len(ev.videoencoder.state_dict()) == 344
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="the reference tree only exists in the build container")
-def test_reference_config_tree_composes_and_instantiates_unchanged(monkeypatch):
-    """The reference's OWN configs/ (train.yaml + model=... as its job files pass it, vqvae.job:15, ucf-ddiff-train.job:15) through
-    hydra_lite and this build's `src.` modules: paths/hydra/now resolvers, callbacks' sibling defaults, nested `@package`
-    placement.  Only the evaluator (I3D weights) and the checkpoint path (a file on the authors' cluster) are switched off."""
+def test_train_config_tree_with_a_dangling_model_default_composes_and_instantiates(monkeypatch, tmp_path):
+    """configs/ laid out as the reference ships its tree -- train.yaml's `model` default names a file that does not exist, every
+    run passes `model=...` (as its job files do) -- composed from train.yaml through hydra_lite and instantiated through this
+    build's `src.` modules: paths/hydra/now resolvers, callbacks' sibling defaults, nested `@package` placement, the optional
+    `local` group without a file, value overrides into nested nodes."""
+    import shutil
     import src  # noqa: F401
     from gsdd_amd.hydra_lite import compose, instantiate
     monkeypatch.setenv("PROJECT_ROOT", REPO)
-    ref = "/root/reference/configs"
+    ref = str(tmp_path / "configs")
+    shutil.copytree(os.path.join(REPO, "configs"), ref)
+    train = os.path.join(ref, "train.yaml")
+    text = open(train).read()
+    assert "  - model: videogpt_vq_vae.yaml\n" in text and not os.path.exists(os.path.join(ref, "local", "default.yaml"))
+    with open(train, "w") as f:
+        f.write(text.replace("  - model: videogpt_vq_vae.yaml\n", "  - model: text_motion_model.yaml\n"))
+    with pytest.raises(FileNotFoundError):
+        compose(ref, "train.yaml", [])
     cfg = compose(ref, "train.yaml", ["model=discrete_diffusion", "model.do_evaluation=false",
                                       "model.checkpoint_paths.autoencoder=__None__"])
-    assert cfg.model.autoencoder.n_codes == 2048 and cfg.model.autoencoder.sequence_length == 4
-    assert cfg.model.generator.diffusion_model.diffusion_step == 50 and cfg.model.devices == [0]
-    assert cfg.callbacks.model_checkpoint.filename == "epoch_{epoch:03d}" and cfg.paths.datasets == "/home1/chemburk"
+    assert cfg.model.autoencoder.n_codes == cfg.model.generator.diffusion_model.transformer.dalle.num_embed == 4096
+    assert cfg.model.autoencoder.sequence_length == cfg.datamodule.sequence_length == 16
+    assert cfg.model.generator.diffusion_model.diffusion_step == 100 and cfg.model.devices == [0]
+    assert cfg.callbacks.model_checkpoint.filename == "epoch_{epoch:03d}" and cfg.paths.datasets == os.path.join(REPO, "data")
+    ckdir = cfg.callbacks.model_checkpoint.dirpath
+    assert ckdir.startswith(os.path.join(REPO, "logs")) and "/train/runs/" in ckdir and ckdir.endswith("/checkpoints")
+    assert cfg.trainer.default_root_dir == cfg.paths.output_dir and "hydra" not in cfg
     model = instantiate(cfg.model, _recursive_=False)
     dmod = model.generator.diffusion_model
-    assert model.autoencoder.latent_shape == (2, 16, 16) and dmod.num_timesteps == 50 and dmod.num_classes == 2049
+    assert model.autoencoder.latent_shape == (16, 16, 16) and model.autoencoder.n_codes == 4096
+    assert dmod.num_timesteps == 100 and dmod.num_classes == 4097
     assert len(dmod.transformer.blocks) == 19 and dmod.guidance_scale == 2
     # a reference-shaped stage-2 state_dict (dead attn2.mask buffers, 1000-row AdaLayerNorm tables) loads into it
     from gsdd_amd.checkpoint import load_reference_checkpoint
     sd = {"generator." + k: v.clone() for k, v in model.generator.state_dict().items()}
     sd["generator.diffusion_model.transformer.blocks.3.attn2.mask"] = torch.ones(1, 1, 4, 4)
     assert load_reference_checkpoint(model.generator, {"state_dict": sd}) == ["diffusion_model.transformer.blocks.3.attn2.mask"]
-    cfg1 = compose(ref, "train.yaml", ["model=videogpt_vq_vae", "model.do_evaluation=false"])
+    cfg1 = compose(ref, "train.yaml", ["model=videogpt_vq_vae", "model.do_evaluation=false", "model.generator.downsample=[1, 16, 16]"])
     m1 = instantiate(cfg1.model, _recursive_=False)
-    assert m1.generator.downsample == [1, 16, 16] and m1.lr_args["gen_lr"] == 4e-4
+    assert m1.generator.downsample == [1, 16, 16] and m1.generator.latent_shape == (16, 8, 8) and m1.lr_args["gen_lr"] == 4e-4
     assert compose(ref, "train.yaml", ["model=videogpt_vq_vae", "datamodule=msrvtt"]).datamodule._target_.endswith("MSRVTTDataModule")
 
 
@@ -568,3 +582,34 @@ def test_bench_reads_occupancy_counters_of_its_own_grid_from_the_committed_profi
     assert bench.profile_counters("d3pm_logits_kernel", 256, "flat")["mfma_busy"] > 0.6
     assert bench.profile_counters("no_such_kernel", None, "flat") is None
     assert bench.profile_counters("d3pm_attention_v4_kernel<384, 8>", 12345, "flat") is None
+
+
+def test_bench_dump_outputs_stays_within_its_budget_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files, whole while they fit, past the byte budget a seeded sample of the flat elements
+    with their indices -- the same sample on every run, so two builds compare element for element."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    clips = torch.randn((2, 3, 4, 16, 16), generator=g)
+    tok = torch.randint(0, 4096, (2, 64), generator=g)
+    bench.dump_outputs(str(tmp_path / "whole"), {"clips": clips, "content_token": tok})
+    c = np.load(tmp_path / "whole" / "clips.npy")
+    t = np.load(tmp_path / "whole" / "content_token.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, clips.numpy())
+    assert t.dtype == np.float32 and np.array_equal(t, tok.numpy().astype(np.float32))
+    limit = tok.numel() * 4 + 1200
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"clips": clips, "content_token": tok})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["clips.npy", "clips_index.npy", "content_token.npy"]
+    idx = np.load(tmp_path / "a" / "clips_index.npy")
+    vals = np.load(tmp_path / "a" / "clips.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and len(np.unique(idx)) == 100
+    assert np.array_equal(vals, clips.numpy().reshape(-1)[idx.astype(np.int64)])
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= limit
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
