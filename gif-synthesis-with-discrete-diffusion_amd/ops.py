@@ -559,10 +559,10 @@ def adam(p, g, m, v, lr, beta1, beta2, eps, step, stream=None):
 
 # ----------------------------------------------------------------------------- VQ-VAE training-step building blocks
 def conv_wgrad(x, dY, dW, *, in_dims, out_grid, stride=(1, 1, 1), taps=None, ntaps=1, cin, cout, in_pitch=None, pro=None,
-               out_dims=None, out_step=(1, 1, 1), out_off=(0, 0, 0), stream=None):
+               out_dims=None, out_step=(1, 1, 1), out_off=(0, 0, 0), exact_f32=None, stream=None):
     """dW[tap][cout][cin] += sum_m dY[orow(m)] (x) pro(x[src(m,tap)])  (same geometry arguments as the forward gemm)."""
     d = gemm(x, dW, dW, in_dims=in_dims, out_grid=out_grid, stride=stride, taps=taps, ntaps=ntaps, cin=cin, in_pitch=in_pitch,
-             pro=pro, out_dims=out_dims, out_step=out_step, out_off=out_off, cout=cout, _desc_only=True)
+             pro=pro, out_dims=out_dims, out_step=out_step, out_off=out_off, cout=cout, exact_f32=exact_f32, _desc_only=True)
     check(lib().gsdd_conv_wgrad(C.byref(d), ptr(dY), dY.shape[-1], ptr(dW), stream_ptr(stream)))
 
 
