@@ -223,7 +223,10 @@ __device__ __forceinline__ void kv_image_store_knorm(const float4 (&o)[8], int h
         const float n2 = (o[q].x * o[q].x + o[q].y * o[q].y) + (o[q].z * o[q].z + o[q].w * o[q].w);
         const float nb = half32_norm_bound(n2);
         const float4 sk = make_float4(half32_sum(o[q].x), half32_sum(o[q].y), half32_sum(o[q].z), half32_sum(o[q].w));
-        const int hd = 8 * (q >> 2) + 2 * (q & 3) + h;
+        // the head through an opaque copy in every step: hipcc otherwise computes the eight 64-bit store addresses up front and keeps
+        // them live (spilled to scratch in the fused layer kernels) through the reductions
+        int hd = 8 * (q >> 2) + 2 * (q & 3) + h;
+        asm volatile("" : "+v"(hd));
         if (li == 16) {                           // (the reductions are valid in the upper 16 lanes of each half)
             knorm[(int64_t)hd * (M >> 5) + grp] = nb;
             ksum[(int64_t)hd * (M >> 5) + grp] = sk;

@@ -747,72 +747,99 @@ __global__ __launch_bounds__(512, 1) void d3pm_layer_h2_kernel(const LayerArgs a
     uint4* iw2 = iw1 + H2_W2_OFF;                            // 32 fragments
     uint4* iwp = iw1 + H2_WP_OFF;                            // 8 fragments
     float* par = lds + H2_PAR_OFF;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, wave = tid >> 6;
     float* scr = lds + H2_SCR_OFF + wave * 192;
     const uint4* img_qkv = a.wqkv_h2;                        // 24 fragments
 
+    const int64_t ngroups = (a.M + 31) / 32;
+    const bool batch_uniform = a.L % 32 == 0;
+    float act[32], x1[32];
+    // a group's rows (clamped to the last row), and with batch_uniform the values its wave keeps in scr: cvec[b] in lanes 0-15, the
+    // AdaLN row (times 16) in lanes 16-47
+    auto request = [&](int64_t g, int lane, float4& sv) {
+        const int li = lane & 31, h = lane >> 5;
+        const int64_t mc = g * 32 + li < a.M ? g * 32 + li : a.M - 1;
+        if (QKV_ONLY) {
+            load_frag(a.x + mc * D, h, x1);
+        } else {
+            load_frag(a.y + mc * D, h, act);
+            load_frag(a.x + mc * D, h, x1);
+        }
+        sv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (batch_uniform) {
+            const int bu = (int)((uint32_t)(g * 32) / (uint32_t)a.L);
+            if (lane < 16) {
+                if (a.cvec != nullptr) sv = *reinterpret_cast<const float4*>(a.cvec + (int64_t)bu * D + 4 * lane);
+            } else if (HAS_QKV && lane < 48) {
+                const float4 tv = *reinterpret_cast<const float4*>(a.ada + a.t2[bu] * (2 * D) + 4 * (lane - 16));
+                sv = make_float4(tv.x * H2_ASCALE, tv.y * H2_ASCALE, tv.z * H2_ASCALE, tv.w * H2_ASCALE);
+            }
+        }
+    };
+    const int64_t grp0 = (int64_t)blockIdx.x * 8 + wave;
+    float4 scr_v = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the wave's first group is requested before the weight images: its latency overlaps the image copy instead of following the
+    // barrier (at the sampler's lane shape, M = 65536, the first group is the only one)
+    if (grp0 < ngroups) request(grp0, tid & 63, scr_v);
     // the weight images go global -> registers -> LDS with every load in flight before the first store (a copy loop pays one L2
-    // round trip per iteration: 18 of them were 5 us of an 84 us kernel)
+    // round trip per iteration: 18 of them were 5 us of an 84 us kernel); the parameter block rides along
     {
         constexpr int NCP = (QKV_ONLY ? 24 * H2_FRAG_U4 : H2_IMG_U4) / 512;
         static_assert(H2_IMG_U4 % 512 == 0 && (24 * H2_FRAG_U4) % 512 == 0, "image copy assumes whole rounds of the workgroup");
+        static_assert(PAR_N <= 2 * 512, "parameter block: at most two values per thread");
         const uint4* src = QKV_ONLY ? img_qkv : a.lay_h2;
         uint4 tmp[NCP];
 #pragma unroll
         for (int i = 0; i < NCP; ++i) tmp[i] = src[tid + 512 * i];
+        float pv[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int i = tid + 512 * j;
+            float v;
+            if (i >= PAR_N) v = 0.f;
+            else if (QKV_ONLY) v = i >= PAR_BQKV ? a.bqkv[i - PAR_BQKV] : 0.f;
+            else if (i < PAR_G2) v = a.bproj[i];
+            else if (i < PAR_B2LN) v = a.ln2_g[i - PAR_G2] * H2_ASCALE;          // LN2 output, GELU2 input: carried 16 x
+            else if (i < PAR_B1) v = a.ln2_b[i - PAR_B2LN] * H2_ASCALE;
+            else if (i < PAR_B2) v = a.b1[i - PAR_B1] * H2_ASCALE;
+            else if (i < PAR_BQKV) v = a.b2[i - PAR_B2];
+            else v = HAS_QKV ? a.bqkv[i - PAR_BQKV] : 0.f;
+            pv[j] = v;
+        }
 #pragma unroll
         for (int i = 0; i < NCP; ++i) iw1[tid + 512 * i] = tmp[i];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (tid + 512 * j < PAR_N) par[tid + 512 * j] = pv[j];
     }
-    for (int i = tid; i < PAR_N; i += 512) {
-        float v;
-        if (QKV_ONLY) v = i >= PAR_BQKV ? a.bqkv[i - PAR_BQKV] : 0.f;
-        else if (i < PAR_G2) v = a.bproj[i];
-        else if (i < PAR_B2LN) v = a.ln2_g[i - PAR_G2] * H2_ASCALE;          // LN2 output, GELU2 input: carried 16 x
-        else if (i < PAR_B1) v = a.ln2_b[i - PAR_B2LN] * H2_ASCALE;
-        else if (i < PAR_B2) v = a.b1[i - PAR_B1] * H2_ASCALE;
-        else if (i < PAR_BQKV) v = a.b2[i - PAR_B2];
-        else v = HAS_QKV ? a.bqkv[i - PAR_BQKV] : 0.f;
-        par[i] = v;
-    }
+    if (batch_uniform && (tid & 63) < 48) *reinterpret_cast<float4*>(scr + 4 * (tid & 63)) = scr_v;
     __syncthreads();
 
-    const int64_t ngroups = (a.M + 31) / 32;
-    const bool batch_uniform = a.L % 32 == 0;
-    for (int64_t grp = (int64_t)blockIdx.x * 8 + wave; grp < ngroups; grp += (int64_t)gridDim.x * 8) {
+    for (int64_t grp = grp0; grp < ngroups; grp += (int64_t)gridDim.x * 8) {
+        // The lane id goes through an opaque copy in every group: otherwise hipcc hoists each lane-dependent address of the body out
+        // of the loop and spills them (260 B of scratch per lane, 34 MB written per launch at the lane shape, where the loop runs once).
+        int lane = tid & 63;
+        asm volatile("" : "+v"(lane));
+        const int li = lane & 31, h = lane >> 5;
         const int64_t m = grp * 32 + li;
         const bool valid = m < a.M;
         const bool full = grp * 32 + 32 <= a.M;
         const int64_t mc = valid ? m : a.M - 1;
         const int b = (int)((uint32_t)mc / (uint32_t)a.L);
-        if (batch_uniform) {
-            const int bu = (int)((uint32_t)(grp * 32) / (uint32_t)a.L);
-            if (lane < 16) {
-                float4 cv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a.cvec != nullptr) cv = *reinterpret_cast<const float4*>(a.cvec + (int64_t)bu * D + 4 * lane);
-                *reinterpret_cast<float4*>(scr + 4 * lane) = cv;
-            } else if (HAS_QKV && lane < 48) {
-                const float* tab = a.ada + a.t2[bu] * (2 * D);
-                const float4 tv = *reinterpret_cast<const float4*>(tab + 4 * (lane - 16));
-                *reinterpret_cast<float4*>(scr + 4 * lane) =
-                    make_float4(tv.x * H2_ASCALE, tv.y * H2_ASCALE, tv.z * H2_ASCALE, tv.w * H2_ASCALE);
-            }
+        if (grp != grp0) {
+            request(grp, lane, scr_v);
+            if (batch_uniform && lane < 48) *reinterpret_cast<float4*>(scr + 4 * lane) = scr_v;
         }
 
-        float act[32], x1[32];
         f32x16 acc[2];
         P2 bp[4];
         float mean, rstd;
-        if (QKV_ONLY) {
-            load_frag(a.x + mc * D, h, x1);
-        } else {
+        if (!QKV_ONLY) {
         // ---- x1 = x + proj(y) + b_proj + cvec[b]
         // (Tried and measured slower, each through spills of the 256-register budget: requesting the next group's rows during this
         // group's q|k|v stage, 77 -> 108 us -- vmcnt also retires in order, so every wait for a Wqkv fragment behind those loads waits
         // for their HBM latency; holding q and k in registers so that all stores follow the last product, 194 us; requesting Wqkv a
         // whole 8-fragment block at a time ahead of the previous block's stores, 110 us.)
-        load_frag(a.y + mc * D, h, act);
-        load_frag(a.x + mc * D, h, x1);
 #pragma unroll
         for (int i = 0; i < 32; ++i) act[i] *= H2_ASCALE;
         split_act_h2(act, bp);
@@ -955,6 +982,10 @@ __global__ __launch_bounds__(512, 1) void d3pm_layer_h2_kernel(const LayerArgs a
             split_act_h2(act, bp);
 #pragma unroll 1
             for (int c = 0; c < 3; ++c) {
+                // the row index through an opaque copy in every block: hipcc otherwise computes the 64-bit store addresses of all three
+                // blocks (K image, q rows) above this loop and spills them for the whole stage
+                int64_t mr = m;
+                asm volatile("" : "+v"(mr));
                 zero2(acc);
                 // The V image wants eight *rows* of one column in a lane (below), so for it the product is taken the other way
                 // round (activations as the A operand): acc[nt][r] = v[row 8 (r >> 2) + 4 h + (r & 3)][feature 32 nt + li].
@@ -1020,7 +1051,7 @@ __global__ __launch_bounds__(512, 1) void d3pm_layer_h2_kernel(const LayerArgs a
                         for (int q = 0; q < 8; ++q) {
                             const int hd = 8 * (q >> 2) + 2 * (q & 3) + h;
                             const float vals[4] = {o[q].x, o[q].y, o[q].z, o[q].w};
-                            kv_image_store_k(vals, (int64_t)hd * a.M + m, a.kimg);
+                            kv_image_store_k(vals, (int64_t)hd * a.M + mr, a.kimg);
                         }
                     }
                     kv_image_store_knorm(o, h, li, grp, a.M, a.knorm, a.ksum);      // M % 32 == 0 here: the group is one whole pair-tile
@@ -1028,13 +1059,13 @@ __global__ __launch_bounds__(512, 1) void d3pm_layer_h2_kernel(const LayerArgs a
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int n = 64 * c + 32 * (q >> 2) + 8 * (q & 3) + 4 * h;
-                        *reinterpret_cast<float4*>(a.qkv + ((int64_t)(n >> 2) * a.M + m) * 4) = o[q];
+                        *reinterpret_cast<float4*>(a.qkv + ((int64_t)(n >> 2) * a.M + mr) * 4) = o[q];
                     }
                 } else if (valid) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int n = 64 * c + 32 * (q >> 2) + 8 * (q & 3) + 4 * h;
-                        *reinterpret_cast<float4*>(a.qkv + ((int64_t)(n >> 2) * a.M + m) * 4) = o[q];
+                        *reinterpret_cast<float4*>(a.qkv + ((int64_t)(n >> 2) * a.M + mr) * 4) = o[q];
                     }
                 }
             }

@@ -106,19 +106,22 @@ def main():
                 lay["w2_x3"], lay["wqkv_x3"] = ops.d3pm_layer_pack(lay["w2"], lay["wproj"], lay["wqkv"])
             else:
                 lay["lay_h2"], lay["wqkv_h2"] = ops.d3pm_layer_pack_h2(lay["w1"], lay["w2"], lay["wproj"], lay["wqkv"])
-        x = torch.randn((M, D), device=dev); y = torch.randn((M, D), device=dev)
-        qkv = torch.empty((3 * H, M, 4), device=dev)
-        cv = torch.randn((B2, D), device=dev)
-        t2 = torch.full((B2,), 50, dtype=torch.int64, device=dev)
-        ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv, nxt=p["layers"][1], t2=t2, qkv=qkv))
-        fl = 2.0 * M * (64 * 64 + 2 * 64 * 256 + 64 * 192)
-        print(f"fused layer (proj+mlp+next qkv): {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
-        aws = ops.d3pm_attention_workspace(B2, L, H, dev)
-        ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv, nxt=p["layers"][1], t2=t2, qkv=qkv, kv_img=aws))
-        print(f"fused layer (proj+mlp+next q, K/V images): {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
-        ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv))
-        fl = 2.0 * M * (64 * 64 + 2 * 64 * 256)
-        print(f"fused layer (proj+mlp, last):    {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
+        # the full batch (2B = 32 rows of L) and one sampler lane's half of it (M = 65536)
+        for B2l in [int(v) for v in os.environ.get("GSDD_LAYER_B2", f"{B2},{B2 // 2}").split(",")]:
+            Ml = B2l * L
+            x = torch.randn((Ml, D), device=dev); y = torch.randn((Ml, D), device=dev)
+            qkv = torch.empty((3 * H, Ml, 4), device=dev)
+            cv = torch.randn((B2l, D), device=dev)
+            t2 = torch.full((B2l,), 50, dtype=torch.int64, device=dev)
+            ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv, nxt=p["layers"][1], t2=t2, qkv=qkv))
+            fl = 2.0 * Ml * (64 * 64 + 2 * 64 * 256 + 64 * 192)
+            print(f"M={Ml} fused layer (proj+mlp+next qkv): {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
+            aws = ops.d3pm_attention_workspace(B2l, L, H, dev)
+            ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv, nxt=p["layers"][1], t2=t2, qkv=qkv, kv_img=aws))
+            print(f"M={Ml} fused layer (proj+mlp+next q, K/V images): {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
+            ms = timeit(lambda: ops.d3pm_layer(y, x, L, p["layers"][0], cvec=cv))
+            fl = 2.0 * Ml * (64 * 64 + 2 * 64 * 256)
+            print(f"M={Ml} fused layer (proj+mlp, last):    {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
     if "logits" in which:
         x = torch.randn((M, D), device=dev)
         w = torch.randn((K, D), device=dev) * 0.05
