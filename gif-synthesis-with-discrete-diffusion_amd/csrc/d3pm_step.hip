@@ -211,8 +211,9 @@ __global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, S
         if (lane == 0) d.x0_dbg[((int64_t)b * (K + 1) + K) * d.L + l] = -70.f;
     }
 
-    // ---- q_posterior (:251-283)
-    const int64_t t = d.t_dev[b];
+    // ---- q_posterior (:251-283), at t' = t - post_skip for t > post_skip (skip-step sampling, :700-704; wave-uniform)
+    const int64_t t_in = d.t_dev[b];
+    const int64_t t = t_in > d.post_skip ? t_in - d.post_skip : t_in;
     const StepSched s = load_sched(sp.p, t, d.T);
     const int xt = (int)d.tok_in[pos];
     const bool masked = (xt == K);
@@ -315,6 +316,12 @@ __global__ __launch_bounds__(256) void d3pm_q_sample_kernel(const int64_t* x0, i
 __global__ void advance_kernel(int64_t* t_dev, int B, int64_t dt, int64_t* stream_dev, int64_t ds) {
     const int i = threadIdx.x + blockIdx.x * blockDim.x;
     if (t_dev != nullptr && i < B) t_dev[i] += dt;
+    if (stream_dev != nullptr && i == 0) stream_dev[0] += ds;
+}
+
+__global__ void advance_floor_kernel(int64_t* t_dev, int B, int64_t dt, int64_t t_min, int64_t* stream_dev, int64_t ds) {
+    const int i = threadIdx.x + blockIdx.x * blockDim.x;
+    if (t_dev != nullptr && i < B) t_dev[i] = t_dev[i] + dt > t_min ? t_dev[i] + dt : t_min;
     if (stream_dev != nullptr && i == 0) stream_dev[0] += ds;
 }
 
@@ -763,6 +770,7 @@ extern "C" int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream) {
     const int J = (d->K + 255) / 256;
     const bool dbg = d->post_dbg != nullptr || d->x0_dbg != nullptr;
     GSDD_CHECK_ARG(d->occupancy == 0 || d->occupancy == 2 || d->occupancy == 3, "occupancy: 0 (auto), 2 or 3 waves per SIMD");
+    GSDD_CHECK_ARG(d->post_skip >= 0, "post_skip must be >= 0");
     if (J > 8 && J <= 16 && d->K == 4096 && !dbg && d->occupancy != 3) {       // the production shape: no scratch (see the kernel's note)
         hipLaunchKernelGGL((d3pm_step_kernel<16, true, false, 2>), grid, block, 0, st, *d, sp);
         GSDD_CHECK_LAUNCH();
@@ -808,6 +816,16 @@ extern "C" int gsdd_advance(int64_t* t_dev, int B, int64_t dt, int64_t* stream_d
     GSDD_CHECK_ARG(B >= 0 && B <= 65536, "bad B");
     const int n = B > 0 ? B : 1;
     hipLaunchKernelGGL(advance_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t_dev, B, dt,
+                       stream_dev, ds);
+    GSDD_CHECK_LAUNCH();
+    return GSDD_OK;
+}
+
+extern "C" int gsdd_advance_floor(int64_t* t_dev, int B, int64_t dt, int64_t t_min, int64_t* stream_dev, int64_t ds,
+                                  void* stream) {
+    GSDD_CHECK_ARG(B >= 0 && B <= 65536, "bad B");
+    const int n = B > 0 ? B : 1;
+    hipLaunchKernelGGL(advance_floor_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t_dev, B, dt, t_min,
                        stream_dev, ds);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;

@@ -6,8 +6,10 @@ src/models/networks/discrete_diffusion.py.  The nn.Module tree only owns paramet
 reference's names; the sampling loop runs as one captured hipGraph per reverse
 step, replayed diffusion_step times with the timestep and the Philox stream id living in device memory.
 """
+import collections
 import collections.abc
 import contextlib
+import numbers
 import os
 
 import torch
@@ -402,6 +404,31 @@ def alpha_schedule(time_step, N=100, att_1=0.99999, att_T=0.000009, ctt_1=0.0000
     return at, bt, ct, att, btt, ctt
 
 
+SamplePlan = collections.namedtuple("SamplePlan", "t0 n_steps dt post_skip q_sample")
+SamplePlan.__doc__ = """A reverse chain: the denoiser's first timestep t0, the number of steps, how far t moves per step (t <- max(t - dt, 0)),
+the posterior's skip s (it runs at t - s for t > s, else at t) and whether the start is a q_sample draw of given tokens."""
+
+
+def sample_plan(T, skip_step=0, start_step=0):
+    """The chain sample() / sample_fast() run, host-side and pure.
+    start_step > 0: sample(filter_ratio > 0) -- q_sample at start_step - 1, then t = start_step - 1 ... 0.
+    Otherwise from all-[MASK]: t = T-1, T-1-(1+s), ... down to the last value >= 0, then 0 if the list does not end there
+    (diffusion_transformer.py:692-694); skip_step = 0 is sample(filter_ratio=0)."""
+    if start_step:
+        return SamplePlan(start_step - 1, start_step, 1, 0, True)
+    n = (T - 1) // (1 + skip_step) + 1 + (1 if (T - 1) % (1 + skip_step) else 0)
+    return SamplePlan(T - 1, n, 1 + skip_step, skip_step, False)
+
+
+def plan_timesteps(plan):
+    """-> [(t, t')]: the denoiser's and the posterior's timestep of every step of `plan`."""
+    out, t = [], plan.t0
+    for _ in range(plan.n_steps):
+        out.append((t, t - plan.post_skip if t > plan.post_skip else t))
+        t = max(t - plan.dt, 0)
+    return out
+
+
 SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct",
                "log_1_min_cumprod_ct")
 
@@ -459,35 +486,61 @@ class DiffusionTransformer(nn.Module):
     def _sched(self):
         return [getattr(self, n) for n in SCHED_ORDER]
 
-    # ------------------------------------------------------------------ sampling (diffusion_transformer.py:568-644)
+    # ------------------------------------------------------------------ sampling (diffusion_transformer.py:568-713)
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                print_log=True, use_graph=True, trace=None, **kwargs):
-        """diffusion_transformer.py:568-644.  The loop itself is `_sample_once`; this wrapper reads the layer kernel's range flags
-        once, after the loop (outside graph capture), and repeats the call on the bf16x3 layer kernel if an activation left the f16
-        operand range (Text2ImageTransformer.demote_to_x3p) -- same noise stream, so the tokens are those of an x3p run."""
-        args = (condition_token, condition_mask, condition_embed, cf_condition_embed)
-        kw = dict(content_token=content_token, filter_ratio=filter_ratio, return_logits=return_logits, use_graph=use_graph, **kwargs)
+        """diffusion_transformer.py:568-644.  The loop itself is `_sample_once`, driven by `sample_plan`; `_sample_checked` repeats it
+        on the bf16x3 layer kernel if an activation left the f16 operand range.
+        filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
+        (diffusion_transformer.py:590-592, :626-634; the reference's own loop there passes p_sample four of its six positional
+        parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step)."""
+        start_step = int(self.num_timesteps * filter_ratio)
+        if start_step != 0 and content_token is None:
+            raise GsddError("filter_ratio > 0 needs content_token (the tokens to start from)")
+        return self._sample_checked(sample_plan(self.num_timesteps, start_step=start_step), condition_token, condition_embed,
+                                    cf_condition_embed, content_token=content_token, return_logits=return_logits,
+                                    use_graph=use_graph, trace=trace, **kwargs)
+
+    @torch.no_grad()
+    def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
+                    temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None, print_log=True,
+                    skip_step=1, *, cf_condition_embed=None, use_graph=True, trace=None, **kwargs):
+        """VQ-Diffusion's skip-step sampler (diffusion_transformer.py:648-713): the denoiser runs at t = T-1, T-1-(1+s), ..., then 0
+        (`sample_plan`), and each step's posterior jumps to t - s (for t > s) across the skipped levels.  From all-[MASK] only, as the
+        reference asserts.  The reference passes cf_predict_start three of its four arguments; the
+        unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit."""
+        T = self.num_timesteps
+        if int(T * filter_ratio) != 0:
+            raise GsddError(f"sample_fast starts from all-[MASK] only: int(num_timesteps * filter_ratio) = {int(T * filter_ratio)}, "
+                            "must be 0 (diffusion_transformer.py:686)")
+        if isinstance(skip_step, bool) or not isinstance(skip_step, numbers.Integral) or skip_step < 0:
+            raise GsddError(f"skip_step must be a non-negative int, got {skip_step!r}")
+        if abs(self.guidance_scale - 1) >= 1e-3 and cf_condition_embed is None:
+            raise GsddError("guided sampling (guidance_scale != 1) needs cf_condition_embed")
+        if return_logits:
+            raise NotImplementedError("return_logits is unused by the reference call sites")
+        return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
+                                    use_graph=use_graph, trace=trace, **kwargs)
+
+    def _sample_checked(self, plan, *args, trace=None, **kw):
+        """`_sample_once`, then one read of the layer kernel's range flags after the loop (outside graph capture): if an activation left
+        the f16 operand range the call is repeated on the bf16x3 layer kernel (Text2ImageTransformer.demote_to_x3p) -- same noise
+        stream, so the tokens are those of an x3p run."""
         mark = len(trace) if trace is not None else 0
-        out = self._sample_once(*args, trace=trace, **kw)
+        out = self._sample_once(plan, *args, trace=trace, **kw)
         if any(int(f.item()) != 0 for f in self._range_flags):
             if not self.transformer.demote_to_x3p():
                 raise GsddError("non-finite activations in the denoiser (inf / NaN in the inputs or weights?)")
             if trace is not None:
                 del trace[mark:]
             self.noise_stream -= self._last_draws
-            out = self._sample_once(*args, trace=trace, **kw)
+            out = self._sample_once(plan, *args, trace=trace, **kw)
         return out
 
-    def _sample_once(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
-                     filter_ratio=0.5, return_logits=False, use_graph=True, trace=None, **kwargs):
-        # filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
-        # (diffusion_transformer.py:590-592, :626-634; the reference's own loop there passes p_sample four of its six positional
-        # parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step)
-        start_step = int(self.num_timesteps * filter_ratio)
-        if start_step != 0 and content_token is None:
-            raise GsddError("filter_ratio > 0 needs content_token (the tokens to start from)")
+    def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
+                     use_graph=True, trace=None, **kwargs):
         dev = self.device
         if dev.type != "cuda":
             raise GsddError("sampling runs on the HIP path only: move the module to a ROCm device")
@@ -502,16 +555,16 @@ class DiffusionTransformer(nn.Module):
         # through the same arithmetic as the stacked pass, at half the denoiser work.  (One host comparison per sample() call;
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
         same_cond = (guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape and bool(torch.equal(cond, cf)))
-        n_steps = start_step if start_step != 0 else T
-        stream0 = self.noise_stream + (1 if start_step != 0 else 0)      # the partially noised start spends one draw on q_sample
-        if start_step != 0:
+        n_steps = plan.n_steps
+        stream0 = self.noise_stream + (1 if plan.q_sample else 0)      # the partially noised start spends one draw on q_sample
+        if plan.q_sample:
             x0_start = content_token.to(dev).long().reshape(B, L).contiguous()
             if int(x0_start.min()) < 0 or int(x0_start.max()) > K:
                 raise GsddError("content_token outside [0, num_embed]")
         rep = 2 if (guided and not same_cond) else 1
         self._last_cfg_dedupe = same_cond
         tr = self.transformer
-        # Independent sub-batches ("lanes") run their 100-step chains concurrently on separate HIP streams: every clip's chain
+        # Independent sub-batches ("lanes") run their reverse chains concurrently on separate HIP streams: every clip's chain
         # depends only on its own tokens, condition and noise rows (the noise key is the global row index), so the tokens are
         # those of the single-lane run, and workgroups of one lane fill the tail of the other lane's kernels.
         # Two lanes by default (measured +8.5 % at bs 16: BENCH_r02 extra.two_lanes); a lane keeps at least 4 clips.
@@ -538,12 +591,12 @@ class DiffusionTransformer(nn.Module):
                 ws = tr.workspace(rep * Bs, L, dev, rep=rep)
                 redo_counters.append(ws["redo"])
                 range_flags.append(ws["range"])
-                t2 = torch.full((rep * Bs,), n_steps - 1, dtype=torch.int64, device=dev)
+                t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
                 sid = torch.tensor([stream0], dtype=torch.int64, device=dev)
                 sched = self._sched()
                 M = Bs * L
                 row0 = (self.row_offset + ln * Bs) * L
-                if start_step == 0:
+                if not plan.q_sample:
                     tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)           # all [MASK] (:613-618)
                 else:                                                                    # q_sample at t = start_step - 1 (:628-630)
                     tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
@@ -554,8 +607,11 @@ class DiffusionTransformer(nn.Module):
                 def one_step(tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st):
                     logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
                     ops.d3pm_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, tok, tok, sched, t2, sid, K=K, T=T,
-                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, stream=st)
-                    ops.advance(t2, -1, sid, 1, stream=st)
+                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=plan.post_skip, stream=st)
+                    if plan.dt == 1:
+                        ops.advance(t2, -1, sid, 1, stream=st)
+                    else:                       # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
+                        ops.advance_floor(t2, -plan.dt, 0, sid, 1, stream=st)
 
                 if use_graph and trace is None:
                     one_step()                  # eager first step (validates arguments outside capture)
@@ -583,7 +639,8 @@ class DiffusionTransformer(nn.Module):
         self._redo_counters = redo_counters     # attention chunk-redo events of this call, one device counter per lane
         self._range_flags = range_flags
         self._last_lanes = lanes
-        self._last_draws = n_steps + (1 if start_step != 0 else 0)
+        self._last_plan = plan
+        self._last_draws = n_steps + (1 if plan.q_sample else 0)
         self.noise_stream += self._last_draws
         out = {"content_token": tok}
         if return_logits:
@@ -596,8 +653,9 @@ class DiffusionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ single-step pieces (parity tests, training glue)
     @torch.no_grad()
-    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None):
-        """One reverse step on tokens (p_sample, diffusion_transformer.py:304-352, prior_rule 0)."""
+    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0):
+        """One reverse step on tokens (p_sample, diffusion_transformer.py:304-352, prior_rule 0); post_skip > 0: the posterior at
+        t - post_skip for t > post_skip (a sample_fast step, :700-704)."""
         dev = tok.device
         B, L = tok.shape
         K, T = self.num_classes - 1, self.num_timesteps
@@ -614,7 +672,7 @@ class DiffusionTransformer(nn.Module):
         M = B * L
         ops.d3pm_step(logits[:M], logits[M:] if guided else None, tok, out, self._sched(), t2, sid, K=K, T=T,
                       guidance=float(self.guidance_scale), seed=self.noise_seed, row0=self.row_offset * L,
-                      post_dbg=post_dbg, x0_dbg=x0_dbg)
+                      post_dbg=post_dbg, x0_dbg=x0_dbg, post_skip=post_skip)
         return out
 
     # ------------------------------------------------------------------ training objective (forward value)
@@ -750,9 +808,10 @@ class DiscreteDiffusion(nn.Module):
     `diffusion_model` may be already-built modules or (with hydra present) configs to instantiate.
 
     zero_text_emb=True is the reference as written: both text embeddings are replaced by zeros (discrete_diffusion.py:25, :49).
-    False lets the captions condition the denoiser."""
+    False lets the captions condition the denoiser.
+    sample_skip_step=None samples with DiffusionTransformer.sample (every timestep); an int s samples with sample_fast(skip_step=s)."""
 
-    def __init__(self, textencoder, diffusion_model, zero_text_emb=True, **kwargs):
+    def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, **kwargs):
         super().__init__()
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -761,6 +820,10 @@ class DiscreteDiffusion(nn.Module):
         self.textencoder = textencoder
         self.diffusion_model = diffusion_model
         self.zero_text_emb = bool(zero_text_emb)
+        if sample_skip_step is not None and (isinstance(sample_skip_step, bool) or not isinstance(sample_skip_step, numbers.Integral)
+                                             or sample_skip_step < 0):
+            raise GsddError(f"sample_skip_step must be null or a non-negative int, got {sample_skip_step!r}")
+        self.sample_skip_step = None if sample_skip_step is None else int(sample_skip_step)
 
     def _text(self, texts, dev):
         emb = self.textencoder(texts)
@@ -828,7 +891,11 @@ class DiscreteDiffusion(nn.Module):
         if text_emb is None:
             text_emb = self._text(texts, dev)
         cf_emb = self._text([""] * B, dev)                                              # :46-49
-        out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=None, filter_ratio=0)
+        if self.sample_skip_step is None:
+            out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=None, filter_ratio=0)
+        else:
+            out = self.diffusion_model.sample_fast(texts, None, text_emb, content_token=None, filter_ratio=0,
+                                                   skip_step=self.sample_skip_step, cf_condition_embed=cf_emb)
         self.last_content_token = out["content_token"]
         shape = latent_shape if latent_shape is not None else autoencoder.latent_shape
         return autoencoder.decode(out["content_token"].view(B, *shape))

@@ -331,9 +331,10 @@ def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None):
 
 
 def d3pm_step(logits_c, logits_u, tok_in, tok_out, sched, t_dev, stream_dev, *, K, T, guidance, seed, row0=0,
-              post_dbg=None, x0_dbg=None, stream=None):
+              post_dbg=None, x0_dbg=None, post_skip=0, stream=None):
     B, L = tok_in.shape
     d = StepDesc()
+    d.post_skip = int(post_skip)
     d.occupancy = int(os.environ.get("GSDD_STEP_OCC", "0"))
     d.logits_c, d.logits_u = ptr(logits_c), ptr(logits_u)
     d.tok_in, d.tok_out = ptr(tok_in), ptr(tok_out)
@@ -410,6 +411,12 @@ def d3pm_train_loss_grad(logits, x0, xt, t_dev, pt, sched, Lt_history, Lt_count,
 def advance(t_dev, dt, stream_dev, ds, stream=None):
     B = 0 if t_dev is None else t_dev.numel()
     check(lib().gsdd_advance(ptr(t_dev), B, dt, ptr(stream_dev), ds, stream_ptr(stream)))
+
+
+def advance_floor(t_dev, dt, t_min, stream_dev, ds, stream=None):
+    """t = max(t + dt, t_min), stream += ds on the device (the skip-step sampler's loop counter)."""
+    B = 0 if t_dev is None else t_dev.numel()
+    check(lib().gsdd_advance_floor(ptr(t_dev), B, dt, t_min, ptr(stream_dev), ds, stream_ptr(stream)))
 
 
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):

@@ -320,6 +320,9 @@ typedef struct {
     float* x0_dbg;
     int occupancy;              /* 0 = default; 2 / 3: waves per SIMD the K = 4096 kernel's register budget is sized for       */
                                 /* (development switch: the default is 2, no scratch)                                          */
+    int post_skip;              /* >= 0; the posterior runs at t' = t - post_skip when t > post_skip, else at t' = t (skip-step */
+                                /* sampling, diffusion_transformer.py:700-704); the denoiser's logits are those of step t.     */
+                                /* 0 = the plain reverse step                                                                  */
 } gsdd_step_desc;
 int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream);
 
@@ -422,6 +425,8 @@ int gsdd_adam_multi_dev(const int64_t* table, int n_blocks, float lr, float beta
 
 /* t[b] += dt ; stream[0] += ds   (device-side loop counters for the captured step graph) */
 int gsdd_advance(int64_t* t_dev, int B, int64_t dt, int64_t* stream_dev, int64_t ds, void* stream);
+/* t[b] = max(t[b] + dt, t_min) ; stream[0] += ds   (the skip-step sampler's counter: t moves by -(1 + s) and stops at 0) */
+int gsdd_advance_floor(int64_t* t_dev, int B, int64_t dt, int64_t t_min, int64_t* stream_dev, int64_t ds, void* stream);
 
 /* uniform Philox floats, layout of oracle/philox.py uniform_rows (test hook) */
 int gsdd_philox_uniform(uint64_t seed, int64_t stream_id, int64_t row0, int64_t n_rows, int n_cols,

@@ -143,6 +143,13 @@ int main() {
         d.occupancy = 7;
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
         d.occupancy = 0;
+        d.post_skip = 3;
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true);
+        d.post_skip = -1;
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
+        d.post_skip = 0;
+        EXPECT(gsdd_advance_floor(devp<int64_t>(), B, -4, 0, devp<int64_t>(), 1, st), GSDD_OK, true);
+        EXPECT(gsdd_advance_floor(devp<int64_t>(), -1, -4, 0, devp<int64_t>(), 1, st), GSDD_E_ARG, false);
         for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { d.K = k; EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true); }
         d.K = 8196;
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
