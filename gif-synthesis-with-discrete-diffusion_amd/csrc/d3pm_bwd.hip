@@ -109,8 +109,26 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* dh, const floa
             for (int e = 0; e < 4; ++e) { ag[e] += dv[e] * xh[e]; ab[e] += dv[e]; }
         }
     }
-    if (dgamma != nullptr) {
-        // the rows of a block belong to one batch element when rows_per_batch % (16 * rit) == 0 (checked on the host)
+    if (dgamma == nullptr) return;
+    const int64_t row0 = (int64_t)blockIdx.x * rit * 16;
+    const int64_t rlast = (row0 + 16 * rit < M ? row0 + 16 * rit : M) - 1;
+    const uint32_t b0 = (uint32_t)row0 / (uint32_t)rows_per_batch;
+    if (acc_by_batch && b0 != (uint32_t)rlast / (uint32_t)rows_per_batch) {
+        // the block's rows span two or more batch elements (rows_per_batch % 16 != 0; the host then runs rit = 1): each row goes to its
+        // own slot, one atomic per element (block-uniform branch)
+        const int64_t row = row0 + rloc;
+        if (row < M) {
+            const int64_t slot = (uint32_t)row / (uint32_t)rows_per_batch;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                atomicAdd(dgamma + slot * gacc_stride + c + e, ag[e]);
+                atomicAdd(dbeta + slot * gacc_stride + c + e, ab[e]);
+            }
+        }
+        return;
+    }
+    {
+        // the rows of the block belong to one batch element
 #pragma unroll
         for (int e = 0; e < 4; ++e) { sg[rloc][c + e] = ag[e]; sb[rloc][c + e] = ab[e]; }
         __syncthreads();
@@ -118,8 +136,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* dh, const floa
             float a = 0.f, bb = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { a += sg[r][tid]; bb += sb[r][tid]; }
-            const int64_t row0 = (int64_t)blockIdx.x * rit * 16;
-            const int b0 = (int)((uint32_t)(row0 < M ? row0 : 0) / (uint32_t)rows_per_batch);
             const int64_t slot = acc_by_batch ? b0 : 0;
             atomicAdd(dgamma + slot * gacc_stride + tid, a);
             atomicAdd(dbeta + slot * gacc_stride + tid, bb);
@@ -594,8 +610,9 @@ extern "C" int gsdd_ln_bwd(const float* dh, const float* x, const float* stats, 
     GSDD_CHECK_ARG(dh && x && stats && gamma && dx_out, "null pointer");
     GSDD_CHECK_ARG(C == 64 && M > 0 && rows_per_batch > 0, "kernel is specialised for 64 features");
     GSDD_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "dgamma/dbeta come together");
-    GSDD_CHECK_ARG(!acc_by_batch || rows_per_batch % 16 == 0, "per-batch accumulation needs rows_per_batch % 16 == 0");
-    int rit = 4;                                               // 16-row groups per block: fewer, fatter atomics
+    // 16-row groups per block: fewer, fatter atomics.  With acc_by_batch a block's rows must not span two batch elements at rit > 1;
+    // when rows_per_batch % 16 != 0 (rit = 1) the blocks that do span two take a per-row atomic path
+    int rit = 4;
     while (rit > 1 && ((acc_by_batch && rows_per_batch % (16 * rit) != 0) || M < (int64_t)16 * rit * 512)) rit >>= 1;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)((M + 16 * rit - 1) / (16 * rit))), dim3(256), 0, (hipStream_t)stream, dh, x, stats,
                        gamma, sel, gstride, rows_per_batch, M, dx_in, dx_out, dgamma, dbeta, gacc_stride, acc_by_batch, rit);

@@ -3,7 +3,10 @@ C2 = VQ-VAE step on 64 clips of 16x128x128 (256 channels, 3 residual blocks, 409
 16x16x16 per GPU (19 layers, K = 4096, T = 100).  Three optimiser steps on one fixed batch: the loss is finite and falls, the first
 step (same weights, same batch, same noise) reproduces bit for bit in a fresh model, peak memory stays under a stated bound.
 The gradients themselves are checked against autograd of the oracle at small sizes in test_gpu_training.py /
-test_gpu_vqvae_training.py; the kernels take the same code paths here (same tile shapes, only more tiles)."""
+test_gpu_vqvae_training.py.  Those shapes do not reach every code path of C4's: LayerNorm backward blocks of 4 x 16 rows, the
+attention pair at 2^32 (batch, head, query, key) products, the embedding backward at 65,536 rows.  test_gpu_train_kernels.py holds
+each D3PM training kernel to fp64 element by element at C4's shape, and test_gpu_training.py's
+test_batch_of_16_equals_mean_of_single_clips_at_c4_shape pins the whole step's per-batch indexing at B = 16, L = 4096."""
 import pytest
 import torch
 

@@ -145,6 +145,105 @@ def test_loss_gradients_full_size_two_layers(G):
     assert worst[1] < 2e-3, worst
 
 
+def random_model(G, K, spatial, n_layer, seed, cond_dim=512):
+    """A denoiser with weights of a trained-like magnitude (softmax rows that are not flat) -> (dm on the GPU, CPU state dict)"""
+    L = spatial[0] * spatial[1]
+    d = G.DalleMaskImageEmbedding(num_embed=K, spatial_size=spatial, embed_dim=64)
+    tr = G.Text2ImageTransformer(dalle=d, n_layer=n_layer, n_embd=64, n_head=16, content_seq_len=L, block_activate="GELU2",
+                                 content_spatial_size=spatial, condition_dim=cond_dim, diffusion_step=100)
+    g = torch.Generator().manual_seed(seed)
+    for mod in tr.modules():
+        if isinstance(mod, torch.nn.Linear):
+            mod.weight.data = torch.randn(mod.weight.shape, generator=g) * (1.0 / mod.in_features ** 0.5)
+            mod.bias.data = 0.1 * torch.randn(mod.bias.shape, generator=g)
+        elif isinstance(mod, torch.nn.Embedding):
+            mod.weight.data = torch.randn(mod.weight.shape, generator=g) * 0.5
+    dm = G.DiffusionTransformer(transformer=tr, diffusion_step=100, alpha_init_type="alpha1", auxiliary_loss_weight=5e-4,
+                                adaptive_auxiliary_loss=True, guidance_scale=2, content_seq_len=L)
+    sd = {k: v.detach().clone() for k, v in dm.state_dict().items()}
+    return dm.cuda(), sd
+
+
+def test_batch_of_16_equals_mean_of_single_clips_at_c4_shape(G):
+    """The step at config C4's shape (B = 16, L = 4096, K = 4096, condition 512) against the mean of 16 one-clip steps, each drawing its
+    q_sample noise at its own row offset (what the batch does for clip b) with the clip's own t and p(t).  The one-clip path is pinned to
+    the oracle (test_loss_gradients_full_size_two_layers: within 4.3e-5 of it, measured), so this pins every per-batch index of the
+    step at the real batch: AdaLN table rows and dtab slots, cvec / dcvec, attention batch offsets, dpos, the loss kernel.
+    x_t must be the concatenation of the single draws bit for bit, the loss agree to rounding, and every gradient tensor to 2e-4 of
+    its largest entry (floor 1e-3 of the model's largest gradient: mathematically zero gradients are rounding noise)."""
+    from gsdd_amd.d3pm_train import D3PMTrainer
+    from tests.conftest import parity_report
+    B, K, L = 16, 4096, 4096
+    dm, _ = random_model(G, K, [64, 64], 2, 61)
+    g = torch.Generator().manual_seed(62)
+    x0 = torch.randint(0, K, (B, L), generator=g).cuda()
+    cond = torch.randn(B, 1, 512, generator=g).cuda()
+    t = torch.tensor([0, 99, 41, 41, 41, 7, 99, 63, 0, 12, 88, 50, 50, 3, 71, 29]).cuda()
+    pt = (torch.rand(B, generator=g) * 0.02 + 0.001).cuda()
+    tr = D3PMTrainer(dm)
+    dm.set_noise(91, stream=5)
+    loss, grads = tr.loss_and_grads(x0, cond, t=t, pt=pt)
+    loss = loss.item()
+    grads = {k: v.detach().clone() for k, v in grads.items()}
+    xt = tr.last_fwd["xt"].clone()
+    mean = {k: torch.zeros_like(v) for k, v in grads.items()}
+    losses, xts = [], []
+    for b in range(B):
+        dm.set_noise(91, stream=5, row_offset=b)
+        lb, gb = tr.loss_and_grads(x0[b:b + 1], cond[b:b + 1], t=t[b:b + 1], pt=pt[b:b + 1])
+        losses.append(lb.item())
+        xts.append(tr.last_fwd["xt"].clone())
+        for k, v in gb.items():
+            mean[k] += v / B
+    assert torch.equal(xt, torch.cat(xts)), "the batch's q_sample draw is not the concatenation of the single-clip draws"
+    want_loss = float(np.mean(losses))
+    gmax = max(v.abs().max().item() for v in mean.values())
+    worst = ("", 0.0)
+    for k, w in mean.items():
+        err = (grads[k] - w).abs().max().item() / max(w.abs().max().item(), 1e-3 * gmax)
+        if err > worst[1]:
+            worst = (k, err)
+    parity_report("d3pm_batch16_vs_single_clips_C4", {"loss": loss, "mean_single_loss": want_loss, "worst_relative_error": worst[1],
+                                                      "worst_parameter": worst[0], "worst_ratio": worst[1] / 2e-4})
+    assert abs(loss - want_loss) <= 1e-5 * abs(want_loss), (loss, want_loss)
+    assert worst[1] < 2e-4, worst
+
+
+@pytest.mark.parametrize("spatial", [[8, 6], [10, 10]])
+def test_loss_gradients_at_ragged_lengths_match_autograd_of_oracle(G, spatial):
+    """The trainer at L % 32 != 0 -- the VALU attention forward and backward, no captured graph -- and at L % 16 != 0 (L = 100: LayerNorm
+    backward blocks that span two clips add their AdaLN table gradients per row): loss and every parameter gradient against
+    torch.autograd of the CPU oracle, the bar of test_loss_gradients_match_autograd_of_oracle."""
+    from gsdd_amd.d3pm_train import D3PMTrainer
+    from oracle import d3pm as od
+    from tests.conftest import parity_report
+    K, B = 64, 3
+    L = spatial[0] * spatial[1]
+    dm, sd = random_model(G, K, spatial, 2, 70 + L)
+    g = torch.Generator().manual_seed(71)
+    x0 = torch.randint(0, K, (B, L), generator=g)
+    cond = torch.randn(B, 1, 512, generator=g)
+    t = torch.tensor([0, 57, 99])
+    pt = torch.ones(B) / 100
+    leaf = {k: (v.clone().requires_grad_(True) if k.startswith("transformer.") and v.dtype.is_floating_point else v) for k, v in sd.items()}
+    want_loss, _, _, _ = od.train_loss(x0, cond, t, pt, leaf, 23, 4)
+    want_loss.backward()
+    want = {k[len("transformer."):]: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaf.items()
+            if k.startswith("transformer.") and v.dtype.is_floating_point}
+    dm.set_noise(23, stream=4)
+    loss, got = D3PMTrainer(dm).loss_and_grads(x0.cuda(), cond.cuda(), t=t.cuda(), pt=pt.cuda())
+    np.testing.assert_allclose(loss.item(), want_loss.item(), rtol=2e-5)
+    assert set(got) == set(want), set(got) ^ set(want)
+    gmax = max(w.abs().max().item() for w in want.values())
+    worst = ("", 0.0)
+    for k, w in want.items():
+        err = (got[k].cpu() - w).abs().max().item() / max(w.abs().max().item(), 1e-3 * gmax)
+        if err > worst[1]:
+            worst = (k, err)
+    parity_report(f"d3pm_ragged_L{L}_gradients", {"worst_relative_error": worst[1], "worst_parameter": worst[0], "worst_ratio": worst[1] / 2e-3})
+    assert worst[1] < 2e-3, worst
+
+
 def test_training_forward_attention_modes_agree_at_long_sequences(G, monkeypatch):
     """The training forward's default attention arithmetic at L >= 2048 is the adaptive one (lo half only where a tile can hold a
     probability above 2^-8 of its row sum); GSDD_ATTN_TRAIN_P=22 forces hi + lo everywhere.  Loss and every parameter gradient of the
