@@ -7,7 +7,13 @@ K = 4096) followed by the VQ-VAE decode of those clips to (3,16,128,128).  Synth
 weights of the reference architecture.  One process per GPU; ranks sample independent clips (weak scaling,
 no data-path collective).
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the JSON line.  `--full` adds, after
+the timed steps and outside them, everything else the benchmark measures: the in-situ per-kernel rooflines (`roofline`), the CPU
+oracle baseline (`cpu_baseline`; `--no-cpu-baseline` drops it), and the side regimes and BASELINE.json's other configurations
+(`extra`; `--no-extra` drops them).
+
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -77,7 +83,7 @@ def profile_traffic(kernel, grid):
 def profile_counters(kernel, grid=None, regime="flat"):
     """Issue-port / matrix-pipe occupancy of `kernel` from the newest profiles/r*_pmc_sq_counters.csv that lists it in the per-kernel
     layout of tools/make_sq_csv.py (round 4 on): one row per (regime, kernel, grid), the means per dispatch of a rocprofv3 --pmc pass
-    over THIS program (`python3 bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra`, started directly after `--`;
+    over THIS program (`python3 bench.py --steps 1 --warmup 0 --no-graph --full --no-cpu-baseline --no-extra`, started directly after `--`;
     tools/profile_round.sh).  mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs over the dispatch's SQ_BUSY_CYCLES / 32 shader engines;
     valu_issue_busy = 4 * SQ_ACTIVE_INST_VALU (quad-cycles) / 1024 over the same.  Read, never typed in.  -> dict or None."""
     import csv
@@ -429,11 +435,14 @@ def main():
     ap.add_argument("--codes", type=int, default=4096)
     ap.add_argument("--layers", type=int, default=19)
     ap.add_argument("--diffusion-steps", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the rooflines, the CPU baseline, the side "
+                                                        "regimes and the other configs (off: a plain run does the timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--lanes", type=int, default=2, help="concurrent sub-batches of the sampler on separate HIP streams (the sampler's "
                                                         "default: two when the batch allows it; tokens do not depend on it)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side regimes (trained-like weights, zero cond) and the other configs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side regimes (trained-like weights, zero cond) and the "
+                                                            "other configs")
     ap.add_argument("--attention-mode", default=None, choices=["a8", "22", "11", "a12"],
                     help="softmax P format of the sampler's attention (default: the library's, a8 at this length); DESIGN.md section 4")
     ap.add_argument("--trained-like", action="store_true", help="profiling passes only: run the whole bench on weights of a trained-like "
@@ -536,64 +545,65 @@ def main():
             "ranks": {"seconds_max": round(max(rank_s), 4), "seconds_min": round(min(rank_s), 4),
                       "videos_per_s_per_rank": [round(B * args.steps / s_, 4) for s_ in rank_s]},
         }
-        # the two side measurements must never cost the run its JSON line
-        try:
-            line["roofline"], families = rooflines(dm, vq, cond, cf_cond, B, L, 16, device, args.codes, args.grid,
-                                                   regime="trained_like" if args.trained_like else "flat")
-        except Exception as e:                                   # noqa: BLE001
-            line["roofline"], families = {"error": f"{type(e).__name__}: {e}"}, None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:                                                # everything past the headline: only when asked for
+            # the two side measurements must never cost the run its JSON line
             try:
-                line["cpu_baseline"] = cpu_baseline(args, dm, vq, L)
-            except Exception as e:                               # noqa: BLE001
-                line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_extra:
-            # regimes the dominant kernel could be sensitive to, outside the timed headline (same process, one warm + one timed
-            # pass each): the reference-faithful zero conditioning (DiscreteDiffusion.forward zeroes BOTH embeddings,
-            # discrete_diffusion.py:25, :49: the two guidance copies are then the same computation and sample() runs one of them --
-            # zero_cond_guidance_copies says how many ran; the headline's condition differs from the unconditional one and runs
-            # two), one lane instead of two, and weights of a trained-like magnitude (peaky softmax rows); redo_chunks =
-            # overflow-redo events of the attention kernel per timed pass
-            try:
-                def timed(cond_):
-                    nonlocal cond
-                    keep, cond = cond, cond_
-                    one_pass()
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    one_pass()
-                    torch.cuda.synchronize()
-                    d = time.perf_counter() - t1
-                    cond = keep
-                    return round(B / d, 4), dm.attention_redo_events()
-                extra = {"unit": "videos/s", "redo_chunks_headline": headline_redo}
-                if families is not None:
-                    extra["roofline_families"] = families
-                extra["configs"] = other_configs(args, dm, vq, device)
-                extra["zero_cond"], extra["redo_chunks_zero_cond"] = timed(torch.zeros_like(cond))
-                extra["zero_cond_guidance_copies"] = 1 if getattr(dm, "_last_cfg_dedupe", False) else 2
-                other = 1 if lanes_used > 1 else 2
-                dm.sample_lanes = other                        # same tokens either way: the noise key is the global row
-                extra["one_lane" if other == 1 else "two_lanes"], _ = timed(cond)
-                dm.sample_lanes = args.lanes
-                trained_like_weights(dm)
-                extra["trained_like"], extra["redo_chunks_trained_like"] = timed(cond)
+                line["roofline"], families = rooflines(dm, vq, cond, cf_cond, B, L, 16, device, args.codes, args.grid,
+                                                       regime="trained_like" if args.trained_like else "flat")
+            except Exception as e:                                   # noqa: BLE001
+                line["roofline"], families = {"error": f"{type(e).__name__}: {e}"}, None
+            if world == 1 and not args.no_cpu_baseline:
                 try:
-                    roof_t, _ = rooflines(dm, vq, cond, cf_cond, B, L, 16, device, args.codes, args.grid, reps=1, regime="trained_like")
-                    extra["trained_like_attention_ms_per_launch"] = roof_t["ms_per_launch"]
-                    extra["trained_like_attention_counters"] = roof_t["counters"]
-                    extra["trained_like_attention_ms_by_block"] = roof_t["ms_by_block"]       # blocks 1..18 (block 0 is a half batch)
-                except Exception:                                # noqa: BLE001
-                    pass
-                # the same trained-like weights with P = f16 hi only in every tile (attention_mode '11': data-independent cost, the
-                # documented fast mode whose error is pinned by tests/test_gpu_fullsize.py::test_attention_mode_p11_contract)
-                if dm.transformer.attention_mode is None:
-                    dm.transformer.attention_mode = "11"
-                    extra["trained_like_p11"], _ = timed(cond)
-                    dm.transformer.attention_mode = None
-                line["extra"] = extra
-            except Exception as e:                               # noqa: BLE001
-                line["extra"] = {"error": f"{type(e).__name__}: {e}"}
+                    line["cpu_baseline"] = cpu_baseline(args, dm, vq, L)
+                except Exception as e:                               # noqa: BLE001
+                    line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_extra:
+                # regimes the dominant kernel could be sensitive to, outside the timed headline (same process, one warm + one timed
+                # pass each): the reference-faithful zero conditioning (DiscreteDiffusion.forward zeroes BOTH embeddings,
+                # discrete_diffusion.py:25, :49: the two guidance copies are then the same computation and sample() runs one of them --
+                # zero_cond_guidance_copies says how many ran; the headline's condition differs from the unconditional one and runs
+                # two), one lane instead of two, and weights of a trained-like magnitude (peaky softmax rows); redo_chunks =
+                # overflow-redo events of the attention kernel per timed pass
+                try:
+                    def timed(cond_):
+                        nonlocal cond
+                        keep, cond = cond, cond_
+                        one_pass()
+                        torch.cuda.synchronize()
+                        t1 = time.perf_counter()
+                        one_pass()
+                        torch.cuda.synchronize()
+                        d = time.perf_counter() - t1
+                        cond = keep
+                        return round(B / d, 4), dm.attention_redo_events()
+                    extra = {"unit": "videos/s", "redo_chunks_headline": headline_redo}
+                    if families is not None:
+                        extra["roofline_families"] = families
+                    extra["configs"] = other_configs(args, dm, vq, device)
+                    extra["zero_cond"], extra["redo_chunks_zero_cond"] = timed(torch.zeros_like(cond))
+                    extra["zero_cond_guidance_copies"] = 1 if getattr(dm, "_last_cfg_dedupe", False) else 2
+                    other = 1 if lanes_used > 1 else 2
+                    dm.sample_lanes = other                        # same tokens either way: the noise key is the global row
+                    extra["one_lane" if other == 1 else "two_lanes"], _ = timed(cond)
+                    dm.sample_lanes = args.lanes
+                    trained_like_weights(dm)
+                    extra["trained_like"], extra["redo_chunks_trained_like"] = timed(cond)
+                    try:
+                        roof_t, _ = rooflines(dm, vq, cond, cf_cond, B, L, 16, device, args.codes, args.grid, reps=1, regime="trained_like")
+                        extra["trained_like_attention_ms_per_launch"] = roof_t["ms_per_launch"]
+                        extra["trained_like_attention_counters"] = roof_t["counters"]
+                        extra["trained_like_attention_ms_by_block"] = roof_t["ms_by_block"]       # blocks 1..18 (block 0 is a half batch)
+                    except Exception:                                # noqa: BLE001
+                        pass
+                    # the same trained-like weights with P = f16 hi only in every tile (attention_mode '11': data-independent cost, the
+                    # documented fast mode whose error is pinned by tests/test_gpu_fullsize.py::test_attention_mode_p11_contract)
+                    if dm.transformer.attention_mode is None:
+                        dm.transformer.attention_mode = "11"
+                        extra["trained_like_p11"], _ = timed(cond)
+                        dm.transformer.attention_mode = None
+                    line["extra"] = extra
+                except Exception as e:                               # noqa: BLE001
+                    line["extra"] = {"error": f"{type(e).__name__}: {e}"}
         print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist

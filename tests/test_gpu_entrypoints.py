@@ -143,3 +143,30 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 8 and line["scaling"] == "weak"
     assert len(line["ranks"]["videos_per_s_per_rank"]) == 2 and line["ranks"]["seconds_max"] >= line["ranks"]["seconds_min"] > 0
     assert abs(line["value"] - 8 / line["ranks"]["seconds_max"]) < 0.05 * line["value"]          # (the seconds are rounded to 1e-4)
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_the_side_measurements(tmp_path):
+    """A plain `bench.py` run prints the headline fields only; `--full` adds the in-situ rooflines after the timed steps (toy size,
+    `--no-extra --no-cpu-baseline` keep it short), and neither changes what the timed steps return (`--dump-outputs`)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from src.train import ROOT
+    toy = ["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "4", "--grid", "2", "4", "4", "--codes", "64", "--layers", "2",
+           "--diffusion-steps", "8"]
+    lines = {}
+    for name, more in (("plain", []), ("full", ["--full", "--no-extra", "--no-cpu-baseline"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + toy + more + ["--dump-outputs", str(tmp_path / name)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[name] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == 1 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert {"metric", "unit", "higher_is_better", "dtype"} <= set(line)
+    assert not {"roofline", "extra", "cpu_baseline"} & set(plain)
+    assert "roofline" in full and "error" not in full["roofline"] and full["roofline"]["ms_per_launch"] > 0
+    assert not {"extra", "cpu_baseline"} & set(full)
+    for f in ("clips.npy", "content_token.npy"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f))

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for tag in "$@"; do
   for regime in "" "--trained-like"; do
-    GSDD_LIB_PATH=$PWD/ab/libgsdd_$tag.so python3 bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline $regime 2>/dev/null | python3 -c "
+    GSDD_LIB_PATH=$PWD/ab/libgsdd_$tag.so python3 bench.py --steps 2 --warmup 1 --full --no-extra --no-cpu-baseline $regime 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

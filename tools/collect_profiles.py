@@ -24,7 +24,7 @@ copy("nearest.bygrid.csv", "nearest_code_kernel_stats.csv")
 copy("train.summary.csv", "d3pm_train_kernel_stats.csv")
 if os.path.exists(os.path.join(P, "vqtrain.summary.csv")):
     copy("vqtrain.summary.csv", "vqvae_train_kernel_stats.csv")
-BENCH = ("python3 bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra   (the program started directly after `--`; tools/profile_round.sh); "
+BENCH = ("python3 bench.py --steps 1 --warmup 0 --no-graph --full --no-cpu-baseline --no-extra   (the program started directly after `--`; tools/profile_round.sh); "
          "training kernels (attn_bwd_*; d3pm_train_bwd; rows_linear; wgrad; ln_bwd): the same passes over python3 tools/bench_train.py 16 4 with GSDD_TRAIN_GRAPH=0")
 copy("traffic.csv", "pmc_traffic.csv", (
     "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- " + BENCH + "; tools/make_traffic_csv.py",

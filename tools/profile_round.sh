@@ -2,15 +2,15 @@
 # The rocprofv3 passes behind profiles/rN_*: kernel-trace stats and PMC counters are separate runs (the pool refuses mixed ones),
 # each program is started directly after `--`.  Run from the repository root on the GPU box; results land in gpurun_out/prof/.
 # Since round 4 every counter of the sampler's kernels comes from bench.py ITSELF (not from the microbenchmarks): the PMC passes run
-# `bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline` -- the 100-step loop eagerly as one full batch, then rooflines(), then
-# extra.configs (C5 per rank, C4, C2: so the training kernels are in the same passes).
+# `bench.py --steps 1 --warmup 0 --no-graph --full --no-cpu-baseline` -- the 100-step loop eagerly as one full batch, then rooflines(),
+# then extra.configs (C5 per rank, C4, C2: so the training kernels are in the same passes).
 set -e
 R="$(cd "$(dirname "$0")/.." && pwd)"
 O="$R/gpurun_out/prof"
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 rm -rf "$O"/bench "$O"/train "$O"/vqtrain "$O"/nearest "$O"/sqb_flat "$O"/sqb_trained "$O"/fetch "$O"/write
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench" -- python3 "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-extra > "$O/bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench" -- python3 "$R/bench.py" --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra > "$O/bench.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/train" -- python3 "$R/tools/bench_train.py" 16 8 > "$O/train.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/vqtrain" -- python3 "$R/tools/bench_vqvae_train.py" 64 3 > "$O/vqtrain.log" 2>&1
 export GSDD_NEAREST_M=32768
@@ -28,7 +28,7 @@ fi
 # launch by launch (GSDD_TRAIN_GRAPH=0: the PMC passes serialise dispatches anyway).
 export GSDD_TRAIN_GRAPH=0
 CTR="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"
-BENCH="$R/bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra"
+BENCH="$R/bench.py --steps 1 --warmup 0 --no-graph --full --no-cpu-baseline --no-extra"
 TRAIN="$R/tools/bench_train.py 16 4"
 rm -rf "$O"/sq_train "$O"/fetch_train "$O"/write_train
 rocprofv3 --kernel-trace --pmc $CTR --output-format csv -d "$O/sqb_flat" -- python3 $BENCH > "$O/sqb_flat.log" 2>&1
