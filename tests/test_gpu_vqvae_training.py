@@ -352,3 +352,99 @@ def test_axial_attention_forward_backward_vs_fp64(G, dims, C_):
     ref.backward(datt.double())
     torch.testing.assert_close(out.double(), ref.detach(), atol=2e-5, rtol=0)
     torch.testing.assert_close(dqkv.double(), ref_in.grad, atol=5e-5, rtol=0)
+
+
+def _axial_reference_with_bars(qkv, datt, dims, C_, n_head):
+    """fp64 forward and backward of the axial attention, written out (no autograd), with per-element bars for kernels that work in f32
+    throughout (exact-f32 matrix pipe or fmaf, expf, one reciprocal per row) -> (out, bar_out, dqkv, bar_dqkv).
+    U = 2^-24, gamma(k) = U (8 + 2 sqrt(k)) for a sum of k terms (test_gpu_gemm_family); S keys per line, head width d, c = 1 / sqrt(d).
+      score s_ij = c q_i . k_j: e_s = (gamma(d) + 3 U) c sum_f |q_if k_jf|; E_i = max_j e_s (the row maximum is subtracted from both the
+      numerator and the denominator: only its rounding in the exponent's argument counts).  exp(s_ij - max): relative rho_ij = E_i + U |s_ij -
+      max_i| + 4 U (expf at 2 ulp); the row sum gamma(S) and the weighted mean of rho; reciprocal and product 6 U:
+      eP_ij = P_ij (rho_ij + sum_j P_ij rho_ij + gamma(S) + 6 U).
+      out_if = sum_j P_ij v_jf: sum_j eP_ij |v_jf| + gamma(S) sum_j P_ij |v_jf|.
+      dP_ij = dO_i . v_j: gamma(d) aP_ij, aP_ij = sum_f |dO_if v_jf|;  delta_i = sum_j P_ij dP_ij (or dO_i . out_i: the same bound covers
+      both): e_delta = sum_j eP_ij aP_ij + (gamma(S) + gamma(d)) sum_j P_ij aP_ij.
+      dS_ij = P_ij (dP_ij - delta_i): A_ij = eP_ij |dP_ij - delta_i| + P_ij (gamma(d) aP_ij + e_delta_i + 2 U (|dP_ij| + |delta_i|)) + 2 U |dS_ij|.
+      dq = c dS k: c (A |k| + (gamma(S) + 2 U) |dS| |k|);  dk = c dS^T q likewise;  dv = P^T dO: eP^T |dO| + gamma(S) P^T |dO|."""
+    U = 2.0 ** -24
+    gam = lambda k: U * (8 + 2 * k ** 0.5)
+    N, T, H, W = dims
+    d = C_ // n_head
+    c = d ** -0.5
+    x = qkv.double().view(N, T, H, W, 3, 3, n_head, d)
+    go_all = datt.double().view(N, T, H, W, 3, n_head, d)
+    outs, bouts, grads, bgrads = [], [], [], []
+    for axis, dim in ((0, 3), (1, 2), (2, 1)):          # attend along w, h, t
+        fwd = lambda t: t.movedim(dim, -3).movedim(-2, -4)                  # (..., head, ., S, d)
+        inv = lambda t: t.movedim(-4, -2).movedim(-3, dim).reshape(N, T, H, W, C_)
+        q, k, v = (fwd(x[:, :, :, :, axis, j]) for j in range(3))
+        go = fwd(go_all[:, :, :, :, axis])
+        S = q.shape[-2]
+        s = (q @ k.transpose(-1, -2)) * c
+        e_s = (gam(d) + 3 * U) * c * (q.abs() @ k.abs().transpose(-1, -2))
+        mx = s.amax(-1, keepdim=True)
+        P = torch.softmax(s, dim=-1)
+        rho = e_s.amax(-1, keepdim=True) + U * (s - mx).abs() + 4 * U
+        eP = P * (rho + (P * rho).sum(-1, keepdim=True) + gam(S) + 6 * U)
+        outs.append(inv(P @ v))
+        bouts.append(inv(eP @ v.abs() + gam(S) * (P @ v.abs())))
+        dP = go @ v.transpose(-1, -2)
+        aP = go.abs() @ v.abs().transpose(-1, -2)
+        delta = (P * dP).sum(-1, keepdim=True)
+        e_delta = (eP * aP).sum(-1, keepdim=True) + (gam(S) + gam(d)) * (P * aP).sum(-1, keepdim=True)
+        dS = P * (dP - delta)
+        A = eP * (dP - delta).abs() + P * (gam(d) * aP + e_delta + 2 * U * (dP.abs() + delta.abs())) + 2 * U * dS.abs()
+        gq, bq = c * (dS @ k), c * (A @ k.abs() + (gam(S) + 2 * U) * (dS.abs() @ k.abs()))
+        gk, bk = c * (dS.transpose(-1, -2) @ q), c * (A.transpose(-1, -2) @ q.abs() + (gam(S) + 2 * U) * (dS.abs().transpose(-1, -2) @ q.abs()))
+        gv, bv = P.transpose(-1, -2) @ go, eP.transpose(-1, -2) @ go.abs() + gam(S) * (P.transpose(-1, -2) @ go.abs())
+        grads.append(torch.stack([inv(t) for t in (gq, gk, gv)], dim=4))
+        bgrads.append(torch.stack([inv(t) for t in (bq, bk, bv)], dim=4))
+    M = N * T * H * W
+    pack = lambda ts: torch.stack(ts, dim=4).reshape(M, -1)
+    return pack(outs), pack(bouts), pack(grads), pack(bgrads), float(torch.stack([o.abs().amax() for o in outs]).max())
+
+
+@pytest.mark.parametrize("valu", [False, True], ids=["auto", "valu"])
+@pytest.mark.parametrize("kind", ["peaked", "hot_key"])
+def test_axial_attention_peaked_and_hot_key_vs_fp64(G, kind, valu):
+    """The training shape (2,16,16,16) x 256 with softmax rows far from flat, held element by element to bars derived from the kernels'
+    f32 arithmetic (see _axial_reference_with_bars): "peaked" has scores of standard deviation 4 (q, k = 2 randn), "hot_key" one key
+    per line that every query of the line is aligned with (its probability is ~1).  Both the default kernels (register-resident MFMA at
+    this shape) and the LDS / vector kernels (valu)."""
+    from tests.conftest import parity_report
+    dims, C_ = (2, 16, 16, 16), 256
+    N, T, H, W = dims
+    M = N * T * H * W
+    g = torch.Generator().manual_seed(17 + (kind == "peaked"))
+    if kind == "peaked":
+        qkv = torch.randn(M, 9 * C_, generator=g)
+        v6 = qkv.view(N, T, H, W, 3, 3, C_)
+        v6[..., :2, :] *= 2.0
+    else:
+        qkv = torch.randn(M, 9 * C_, generator=g) * 0.7
+        v6 = qkv.view(N, T, H, W, 3, 3, C_)
+        v6[..., 0, :] += 1.0                                                # every query has the offset (1, ..., 1)
+        t, h, w = torch.meshgrid(torch.arange(T), torch.arange(H), torch.arange(W), indexing="ij")
+        for axis, hot in ((0, w == (t + h) % W), (1, h == (t + w) % H), (2, t == (h + w) % T)):
+            v6[:, :, :, :, axis, 1, :] += hot[None, :, :, :, None].float()   # ... and so has one key of each line: q . k / sqrt(d) ~ 11
+    qkv = qkv.cuda().contiguous()
+    datt = torch.randn(M, 3 * C_, generator=g).cuda()
+    out = torch.empty_like(datt)
+    G.ops.axial_attention(qkv, dims, C_, 2, out, valu=valu)
+    dqkv = G.ops.axial_attention_bwd(qkv, datt, dims, C_, 2, valu=valu)
+    want_o, bar_o, want_g, bar_g, _ = _axial_reference_with_bars(qkv, datt, dims, C_, 2)
+    x = qkv.double().view(N, T, H, W, 3, 3, 2, C_ // 2)
+    pmax = max(float(torch.softmax((x[..., a, 0, :, :].movedim(dm, -3).movedim(-2, -4) @ x[..., a, 1, :, :].movedim(dm, -3).movedim(-2, -4)
+                                    .transpose(-1, -2)) * (C_ // 2) ** -0.5, -1).amax(-1).mean()) for a, dm in ((0, 3), (1, 2), (2, 1)))
+
+    def worst(got, want, bar):
+        got = got.double()
+        assert bool(torch.isfinite(got).all())
+        err = (got - want).abs()
+        return float(torch.where(err == 0, 0.0, err / bar).max())
+    r_o, r_g = worst(out, want_o, bar_o), worst(dqkv, want_g, bar_g)
+    parity_report(f"vqvae_train_kernels::axial_attention[{kind}_{'valu' if valu else 'auto'}]",
+                  {"mean_row_max_probability": pmax, "out_ratio": r_o, "dqkv_ratio": r_g, "out_max_abs_err": float((out.double() - want_o).abs().max()),
+                   "dqkv_max_abs_err": float((dqkv.double() - want_g).abs().max()), "worst_ratio": max(r_o, r_g)})
+    assert r_o <= 1 and r_g <= 1, (r_o, r_g)
