@@ -18,6 +18,7 @@ EXPORTS = [
     "gsdd_d3pm_attention", "gsdd_d3pm_attention_workspace_bytes", "gsdd_d3pm_layer", "gsdd_d3pm_layer_pack", "gsdd_d3pm_layer_pack_h2", "gsdd_rows_linear_pack_many", "gsdd_rows_linear", "gsdd_d3pm_logits", "gsdd_d3pm_cross_attention", "gsdd_d3pm_step", "gsdd_d3pm_q_sample", "gsdd_d3pm_train_loss", "gsdd_d3pm_train_loss_bwd", "gsdd_d3pm_train_loss_grad", "gsdd_gelu2", "gsdd_ln_fwd", "gsdd_ln_bwd", "gsdd_wgrad",
     "gsdd_batch_rowsum", "gsdd_colsum", "gsdd_d3pm_attention_train", "gsdd_d3pm_attention_bwd", "gsdd_d3pm_attention_bwd_workspace_bytes", "gsdd_d3pm_embed_bwd", "gsdd_small_linear_bwd",
     "gsdd_adaln_bwd", "gsdd_adam", "gsdd_adam_multi", "gsdd_adam_multi_dev", "gsdd_advance", "gsdd_advance_floor",
+    "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
 ]
@@ -49,6 +50,22 @@ class StepDesc(C.Structure):
         ("post_dbg", _p), ("x0_dbg", _p), ("occupancy", _i),
         # (post_skip sits in the struct's tail padding: gsdd_abi_sizeof cannot see it missing -- keep it in step with gsdd.h by hand)
         ("post_skip", _i),
+    ]
+
+
+class PurityDesc(C.Structure):
+    _fields_ = [
+        ("logits_c", _p), ("logits_u", _p), ("B", _i), ("L", _i), ("K", _i), ("guidance", C.c_float),
+        ("prior_rule", _i), ("prior_weight", C.c_float), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
+        ("score", _p), ("smax", _p), ("cand", _p), ("recon_dbg", _p), ("prob_dbg", _p), ("score_dbg", _p),
+    ]
+
+
+class PuritySelectDesc(C.Structure):
+    _fields_ = [
+        ("tok_in", _p), ("tok_out", _p), ("cand", _p), ("score", _p), ("smax", _p),
+        ("B", _i), ("L", _i), ("K", _i), ("prior_rule", _i), ("n_dev", _p), ("seed", C.c_uint64), ("stream_dev", _p),
+        ("stream_add", _i64), ("row0", _i64), ("key_dbg", _p),
     ]
 
 
@@ -97,7 +114,8 @@ def lib():
             raise GsddError(f"{LIB_PATH} predates this binding (no gsdd_abi_sizeof): rebuild it with ./build.sh")
         L.gsdd_abi_sizeof.argtypes, L.gsdd_abi_sizeof.restype = [_i], _i64
         for which, (name, cls) in enumerate((("gsdd_gemm_desc", GemmDesc), ("gsdd_layer_desc", LayerDesc), ("gsdd_step_desc", StepDesc),
-                                             ("gsdd_train_desc", TrainDesc))):
+                                             ("gsdd_train_desc", TrainDesc), ("gsdd_purity_desc", PurityDesc),
+                                             ("gsdd_purity_select_desc", PuritySelectDesc))):
             if L.gsdd_abi_sizeof(which) != C.sizeof(cls):
                 raise GsddError(f"{LIB_PATH} was built from another revision of include/gsdd.h: sizeof({name}) is {L.gsdd_abi_sizeof(which)} "
                                 f"there and {C.sizeof(cls)} in this binding -- rebuild it with ./build.sh")
@@ -159,6 +177,9 @@ def lib():
         L.gsdd_adam_multi_dev.argtypes = [_p, _i, C.c_float, C.c_float, C.c_float, C.c_float, _p, _p]
         L.gsdd_advance.argtypes = [_p, _i, _i64, _p, _i64, _p]
         L.gsdd_advance_floor.argtypes = [_p, _i, _i64, _i64, _p, _i64, _p]
+        L.gsdd_d3pm_purity_step.argtypes = [C.POINTER(PurityDesc), _p]
+        L.gsdd_d3pm_purity_select.argtypes = [C.POINTER(PuritySelectDesc), _p]
+        L.gsdd_advance_plan.argtypes = [_p, _p, _p, _i64, _p, _i, _p, _p, _i64, _p]
         L.gsdd_philox_uniform.argtypes = [C.c_uint64, _i64, _i64, _i64, _i, _p, _p]
         L.gsdd_graph_begin.argtypes = [_p]
         L.gsdd_graph_end.argtypes = [_p, C.POINTER(_p)]

@@ -9,132 +9,9 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "d3pm_rows.hpp"
 
 namespace gsdd {
-
-constexpr float LOG_ZERO = -69.07755278982137f;  // log(1e-30)
-
-// expf / logf restricted to the argument ranges this file feeds them.  Both run the device library's own
-// arithmetic (two-constant log2(e) / ln 2 products around v_exp_f32 / v_log_f32, same constants, same order), so
-// results are bit-identical to expf / logf on those ranges; what is dropped is the library's range plumbing
-// (two compare+select pairs per expf, denormal pre-scaling and the inf/nan select per logf), which costs more issue
-// slots than the arithmetic itself (tools/rate_probe6.hip: compares and selects issue at half the f32 add/mul rate).
-//   exp_le0(x): x <= 0 (or -inf).  The lower clamp stands in for the library's "x < -103.28 -> 0" select:
-//               exp(-104) < 2^-150 rounds to 0 in v_ldexp_f32, and it keeps a -inf / absurdly negative
-//               argument away from the hi/lo product.
-//   log_norm(x): x finite and >= 2^-126 (here always >= 1e-30).
-//               CLAMP = false where the argument is known to be finite and of moderate size (differences of clamped
-//               log-probabilities and schedule constants): the clamp is one more half-rate instruction.
-template <bool CLAMP = true>
-__device__ __forceinline__ float exp_le0(float x) {
-    const float L2E_HI = __builtin_bit_cast(float, 0x3fb8aa3bu), L2E_LO = __builtin_bit_cast(float, 0x32a5705fu);
-    if (CLAMP) x = fmaxf(x, -104.f);
-    const float ph = x * L2E_HI;
-    float pl = fmaf(x, L2E_HI, -ph);
-    const float e = rintf(ph);
-    pl = fmaf(x, L2E_LO, pl);
-    const float a = (ph - e) + pl;
-    return ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
-}
-// exp(d), d <= 0 (or -inf), for the TERMS OF A SUM over classes: one product and v_exp_f32 (relative error ~ |d| * 1.7e-7, i.e. small
-// exactly where the term is not).  A log-sum-exp enters every class of its row as the same additive constant, which the arg-max at
-// the end of the step does not see; what its accuracy decides is how often x - lse rounds to the neighbouring float.  With these
-// terms the fp64 sum over a row is accurate to ~1e-9 relative (the largest term is exp(0) = 1 exactly), the same as with the
-// 12-instruction exp_le0, which is kept for the per-class values (log_add_exp), where every class has its own error.
-#ifdef GSDD_DEV_EXACT_SUM_EXP      // development A/B only (tools/neartie_diff.py): the sum terms on the library-exact exponential, as before 2f17ed5
-__device__ __forceinline__ float exp_term(float d) { return exp_le0(d); }
-#else
-__device__ __forceinline__ float exp_term(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896340736f); }
-#endif
-__device__ __forceinline__ float log_norm(float x) {
-    const float LN2_HI = __builtin_bit_cast(float, 0x3f317217u), LN2_LO = __builtin_bit_cast(float, 0x3377d1cfu);
-    const float r = __builtin_amdgcn_logf(x);
-    const float ph = r * LN2_HI;
-    float pl = fmaf(r, LN2_HI, -ph);
-    pl = fmaf(r, LN2_LO, pl);
-    return ph + pl;
-}
-
-// reference log_add_exp (:32-34): m + log(exp(a - m) + exp(b - m)), m = max(a, b).  One of the two exponentials is
-// exp(0) = 1 exactly and the other one's argument is -|a - b| exactly, so a single exp gives the same bits.
-__device__ __forceinline__ float lae(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m + log_norm(1.f + exp_le0(-fabsf(a - b)));   // clamped: a schedule constant may be log(0) = -inf (t - 1 wrap)
-}
-__device__ __forceinline__ float clamp70(float v) { return fminf(fmaxf(v, -70.f), 0.f); }
-
-struct StepSched {
-    float la, lb, lc, l1mc;          // per-step at t
-    float lca, lcb, lcc, l1mcc;      // cumulative at t
-    float pca, pcb, pcc, p1mcc;      // cumulative at t-1 (wrapped)
-};
-
-__device__ __forceinline__ StepSched load_sched(const float* const* s, int64_t t, int T) {
-    StepSched r;
-    r.la = s[0][t]; r.lb = s[1][t]; r.lc = s[2][t]; r.l1mc = s[3][t];
-    r.lca = s[4][t]; r.lcb = s[5][t]; r.lcc = s[6][t]; r.l1mcc = s[7][t];
-    const int64_t tp = (t - 1 + (T + 1)) % (T + 1);
-    r.pca = s[4][tp]; r.pcb = s[5][tp]; r.pcc = s[6][tp]; r.p1mcc = s[7][tp];
-    return r;
-}
-
-struct SchedPtrs { const float* p[8]; };
-
-// log_softmax over the wave's row (fp64 sum/log), clamp to [-70,0]   (predict_start, :231-236)
-template <int J>
-__device__ __forceinline__ void log_softmax_clamp(float (&x)[J][4]) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, x[j][e]);
-    mx = wave_max(mx);
-    double se = 0.0;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) se += (double)exp_term(x[j][e] - mx);
-    se = wave_sum(se);
-    const double lse = (double)mx + log(se);
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[j][e] = clamp70((float)((double)x[j][e] - lse));
-}
-
-// CLAMP = false: every slot holds a finite, bounded value (FULL rows of clamped log-probabilities)
-template <int J, bool CLAMP = true>
-__device__ __forceinline__ float wave_logsumexp(const float (&x)[J][4], float extra, bool has_extra) {
-    float mx = has_extra ? extra : -INFINITY;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, x[j][e]);
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) se += exp_term(x[j][e] - mx);
-    se = wave_sum(se);
-    if (has_extra) se += exp_le0(extra - mx);
-    return mx + logf(se);
-}
-
-__device__ __forceinline__ float gumbel(float u) {  // log_sample_categorical (:355-356); u in [0, 1)
-    return -log_norm(-log_norm(u + 1e-30f) + 1e-30f);
-}
-
-// arg-max of (val, idx) over the wave, first index wins ties (torch.argmax)
-__device__ __forceinline__ int wave_argmax(float v, int idx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    return idx;
-}
 
 // FULL: K == 256 * J, every register slot holds a class (no validity selects).  DBG: the posterior / x0 test hooks
 // are compiled in; the production instantiation has none, so the unrolled class loops are single basic blocks.

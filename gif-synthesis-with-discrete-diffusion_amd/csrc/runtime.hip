@@ -16,6 +16,8 @@ extern "C" int64_t gsdd_abi_sizeof(int which) {
         case 1: return (int64_t)sizeof(gsdd_layer_desc);
         case 2: return (int64_t)sizeof(gsdd_step_desc);
         case 3: return (int64_t)sizeof(gsdd_train_desc);
+        case 4: return (int64_t)sizeof(gsdd_purity_desc);
+        case 5: return (int64_t)sizeof(gsdd_purity_select_desc);
         default: return -1;
     }
 }

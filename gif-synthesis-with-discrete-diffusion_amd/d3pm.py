@@ -429,6 +429,60 @@ def plan_timesteps(plan):
     return out
 
 
+PurityPlan = collections.namedtuple("PurityPlan", "calls final rule weight")
+PurityPlan.__doc__ = """A purity-prior chain (sample() with prior_rule 1 / 2): the (t, n) of every p_sample call at t > 0 -- denoiser at t, reveal n
+[MASK] positions per sample -- whether a plain reverse step at t = 0 closes it, the rule and the prior weight r."""
+
+
+def reference_n_sample(T, prior_ps=1024):
+    """The reveal schedules DiffusionTransformer.update_n_sample carries (diffusion_transformer.py:166-179), written for 1024 tokens;
+    None for a T it has no list for."""
+    if T == 100:
+        return [1, 6] + [11, 10, 10] * 32 + [11, 15] if prior_ps <= 10 else [1, 10] + [11, 10, 10] * 32 + [11, 11]
+    if T == 50:
+        return [10] + [21, 20] * 24 + [30]
+    if T == 25:
+        return [21] + [41] * 23 + [60]
+    if T == 10:
+        return [69] + [102] * 8 + [139]
+    if T == 200:
+        return [1, 3] + [6, 6, 4, 4] * 49 + [6, 9]
+    return None
+
+
+def purity_plan(n_sample, prior_ps, T):
+    """-> [(t, n)]: the p_sample calls of the reference's loop (diffusion_transformer.py:621-626 with :336-340) for a reveal schedule,
+    host-side and pure.  At t >= 1 a call reveals n = min(n_sample[t] - sampled, prior_ps) positions, a single left-over one folded
+    into it, until n_sample[t] are revealed; a timestep with n_sample[t] == 0 makes no call (and runs no denoiser pass).  `sampled`
+    grows by exactly n per call: a candidate token is never [MASK] (its row is -70, out of a 24-bit uniform's Gumbel reach).  The
+    last entry is (0, n_sample[0]) when n_sample[0] > 0: the ordinary reverse step at t = 0, which resamples every position."""
+    calls = []
+    for t in range(T - 1, 0, -1):
+        sampled = 0
+        while sampled < n_sample[t]:
+            n = min(n_sample[t] - sampled, prior_ps)
+            if n_sample[t] - sampled - n == 1:
+                n = n_sample[t] - sampled
+            calls.append((t, n))
+            sampled += n
+    if n_sample[0] > 0:
+        calls.append((0, n_sample[0]))
+    return calls
+
+
+def scaled_n_sample(n_sample, L, L_ref=1024):
+    """A reveal schedule written for L_ref tokens, rescaled to L by cumulative rounding over t = T-1 ... 1 (the order the chain runs
+    in): same length, entry 0 kept, sum over t >= 1 equal to round(sum * L / L_ref), the identity at L == L_ref."""
+    out = list(n_sample)
+    acc = done = 0
+    for t in range(len(n_sample) - 1, 0, -1):
+        acc += n_sample[t]
+        upto = (2 * acc * L + L_ref) // (2 * L_ref)          # round half up, in integers
+        out[t] = upto - done
+        done = upto
+    return out
+
+
 SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct",
                "log_1_min_cumprod_ct")
 
@@ -467,6 +521,11 @@ class DiffusionTransformer(nn.Module):
         self.register_buffer("Lt_history", torch.zeros(self.num_timesteps))
         self.register_buffer("Lt_count", torch.zeros(self.num_timesteps))
         self.empty_text_embed = nn.Parameter(torch.randn(size=(77, 512), dtype=torch.float64))
+        self.prior_rule = 0          # 0: plain sampling; 1: high-quality inference only; 2: purity prior (diffusion_transformer.py:157-161)
+        self.prior_ps = 1024         # most positions one call reveals
+        self.prior_weight = 0        # r of Eq. 11, Improved VQ-Diffusion
+        self.n_sample = None         # reveals per timestep (update_n_sample; None: the reference has no list for this T)
+        self.update_n_sample()
         self.learnable_cf = learnable_cf
         self.guidance_scale = guidance_scale
         self.noise_seed = 0          # Philox key; the stream id advances with every draw
@@ -486,6 +545,42 @@ class DiffusionTransformer(nn.Module):
     def _sched(self):
         return [getattr(self, n) for n in SCHED_ORDER]
 
+    def update_n_sample(self):
+        """diffusion_transformer.py:166-179: the reference's list for this num_timesteps / prior_ps (unchanged for any other T)."""
+        ns = reference_n_sample(self.num_timesteps, self.prior_ps)
+        if ns is not None:
+            self.n_sample = ns
+
+    def _purity_plan(self, start_step):
+        """Validates the prior attributes and returns the PurityPlan sample() runs (prior_rule 1 / 2)."""
+        T, L = self.num_timesteps, self.shape
+        is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if start_step != 0:
+            raise GsddError("prior_rule > 0 samples from all-[MASK] only: filter_ratio must give start_step 0 (the reference's "
+                            "filter_ratio > 0 loop raises with any prior_rule, diffusion_transformer.py:636)")
+        if not is_int(self.prior_ps) or self.prior_ps < 1:
+            raise GsddError(f"prior_ps must be an int >= 1, got {self.prior_ps!r}")
+        if isinstance(self.prior_weight, bool) or not isinstance(self.prior_weight, numbers.Real) or not self.prior_weight >= 0:
+            raise GsddError(f"prior_weight must be a number >= 0, got {self.prior_weight!r}")
+        ns = self.n_sample
+        if ns is None or len(ns) != T:
+            raise GsddError(f"n_sample must list one reveal count per timestep: len(n_sample) = {None if ns is None else len(ns)}, "
+                            f"num_timesteps = {T}")
+        if not all(is_int(v) for v in ns):
+            raise GsddError("n_sample entries must be ints")
+        if min(ns) < 0:
+            raise GsddError(f"negative entry in n_sample: {min(ns)}")
+        if ns[0] > 1024:
+            raise GsddError(f"n_sample[0] = {ns[0]} > 1024: the reference's loop never ends there (diffusion_transformer.py:350, :625)")
+        if sum(ns[1:]) > L:
+            raise GsddError(f"n_sample reveals {sum(ns[1:])} positions over t >= 1 but the sequence has {L}: over-subscribed schedule "
+                            "(the reference then overwrites decoded tokens); rescale it with scaled_n_sample")
+        if L > 4096:
+            raise GsddError(f"prior_rule > 0 needs content_seq_len <= 4096 (the selection kernel's limit), got {L}")
+        calls = purity_plan([int(v) for v in ns], int(self.prior_ps), T)
+        final = bool(calls) and calls[-1][0] == 0
+        return PurityPlan(tuple(calls[:-1] if final else calls), final, int(self.prior_rule), float(self.prior_weight))
+
     # ------------------------------------------------------------------ sampling (diffusion_transformer.py:568-713)
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
@@ -495,8 +590,16 @@ class DiffusionTransformer(nn.Module):
         on the bf16x3 layer kernel if an activation left the f16 operand range.
         filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
         (diffusion_transformer.py:590-592, :626-634; the reference's own loop there passes p_sample four of its six positional
-        parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step)."""
+        parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step).
+        prior_rule 1 / 2 (attributes, as in the reference): the purity-prior chain of `purity_plan` -- every call at t > 0 runs the
+        denoiser, draws a candidate per position and reveals the n most trusted [MASK] positions (two noise streams per call);
+        the step at t = 0 is the ordinary one."""
         start_step = int(self.num_timesteps * filter_ratio)
+        if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
+            raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
+        if self.prior_rule != 0:        # purity-prior inference (:304-346): reveal n_sample[t] trusted positions per timestep
+            return self._sample_checked(self._purity_plan(start_step), condition_token, condition_embed, cf_condition_embed,
+                                        return_logits=return_logits, use_graph=use_graph, trace=trace, **kwargs)
         if start_step != 0 and content_token is None:
             raise GsddError("filter_ratio > 0 needs content_token (the tokens to start from)")
         return self._sample_checked(sample_plan(self.num_timesteps, start_step=start_step), condition_token, condition_embed,
@@ -555,9 +658,12 @@ class DiffusionTransformer(nn.Module):
         # through the same arithmetic as the stacked pass, at half the denoiser work.  (One host comparison per sample() call;
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
         same_cond = (guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape and bool(torch.equal(cond, cf)))
-        n_steps = plan.n_steps
-        stream0 = self.noise_stream + (1 if plan.q_sample else 0)      # the partially noised start spends one draw on q_sample
-        if plan.q_sample:
+        purity = isinstance(plan, PurityPlan)       # prior_rule 1 / 2: the calls at t > 0 come from device plan arrays; the rest is shared
+        q_sample = not purity and plan.q_sample
+        n_steps = len(plan.calls) if purity else plan.n_steps
+        t0 = (plan.calls[0][0] if plan.calls else 0) if purity else plan.t0
+        stream0 = self.noise_stream + (1 if q_sample else 0)           # the partially noised start spends one draw on q_sample
+        if q_sample:
             x0_start = content_token.to(dev).long().reshape(B, L).contiguous()
             if int(x0_start.min()) < 0 or int(x0_start.max()) > K:
                 raise GsddError("content_token outside [0, num_embed]")
@@ -576,7 +682,7 @@ class DiffusionTransformer(nn.Module):
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(lanes)]
         self._stream = self._streams[0]
         Bs = B // lanes
-        toks, graphs, redo_counters, range_flags = [], [], [], []
+        toks, graphs, finals, redo_counters, range_flags = [], [], [], [], []
         cur = torch.cuda.current_stream()
         tr.packed()                                 # packed weights, AdaLN tables and the fragment images are (re)built HERE, on the
         tr.fragment_images()                        # caller's stream: each lane's wait_stream(cur) below then orders its reads after them
@@ -591,12 +697,12 @@ class DiffusionTransformer(nn.Module):
                 ws = tr.workspace(rep * Bs, L, dev, rep=rep)
                 redo_counters.append(ws["redo"])
                 range_flags.append(ws["range"])
-                t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
+                t2 = torch.full((rep * Bs,), t0, dtype=torch.int64, device=dev)
                 sid = torch.tensor([stream0], dtype=torch.int64, device=dev)
                 sched = self._sched()
                 M = Bs * L
                 row0 = (self.row_offset + ln * Bs) * L
-                if not plan.q_sample:
+                if not q_sample:
                     tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)           # all [MASK] (:613-618)
                 else:                                                                    # q_sample at t = start_step - 1 (:628-630)
                     tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
@@ -604,16 +710,43 @@ class DiffusionTransformer(nn.Module):
                                       torch.tensor([self.noise_stream], dtype=torch.int64, device=dev), K=K, T=T,
                                       seed=self.noise_seed, row0=row0, stream=st)
 
-                def one_step(tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st):
+                def plain_step(post_skip, tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st):
                     logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
                     ops.d3pm_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, tok, tok, sched, t2, sid, K=K, T=T,
-                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=plan.post_skip, stream=st)
-                    if plan.dt == 1:
-                        ops.advance(t2, -1, sid, 1, stream=st)
-                    else:                       # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
-                        ops.advance_floor(t2, -plan.dt, 0, sid, 1, stream=st)
+                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st)
 
-                if use_graph and trace is None:
+                if purity:
+                    # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
+                    i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+                    plan_t, plan_n = i64([t for t, _ in plan.calls] + [0]), i64([n for _, n in plan.calls] + [0])
+                    step_dev, n_dev = i64([0]), i64([plan.calls[0][1] if plan.calls else 0])
+                    score = torch.empty((Bs, L), dtype=torch.float32, device=dev)
+                    smax = torch.empty((Bs,), dtype=torch.float32, device=dev)
+                    cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
+
+                    def one_step(tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st, plan_t=plan_t, plan_n=plan_n,
+                                 step_dev=step_dev, n_dev=n_dev, score=score, smax=smax, cand=cand):
+                        logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
+                        ops.d3pm_purity_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, score, smax, cand, sid,
+                                             K=K, guidance=float(self.guidance_scale), prior_rule=plan.rule, prior_weight=plan.weight,
+                                             seed=self.noise_seed, row0=row0, stream=st)
+                        ops.d3pm_purity_select(tok, tok, cand, score, smax, n_dev, sid, K=K, prior_rule=plan.rule, seed=self.noise_seed,
+                                               stream_add=1, row0=row0, stream=st)
+                        ops.advance_plan(step_dev, plan_t, plan_n, t2, n_dev, sid, 2, stream=st)
+
+                    if plan.final:
+                        finals.append((st, lambda plain_step=plain_step: plain_step(0)))
+                else:
+                    def one_step(plain_step=plain_step, t2=t2, sid=sid, st=st):
+                        plain_step(plan.post_skip)
+                        if plan.dt == 1:
+                            ops.advance(t2, -1, sid, 1, stream=st)
+                        else:                   # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
+                            ops.advance_floor(t2, -plan.dt, 0, sid, 1, stream=st)
+
+                if n_steps == 0:                # (a purity schedule that reveals nothing at t >= 1)
+                    pass
+                elif use_graph and trace is None:
                     one_step()                  # eager first step (validates arguments outside capture)
                     g = ops.Graph()
                     g.begin(st)
@@ -632,6 +765,11 @@ class DiffusionTransformer(nn.Module):
                     g.launch(self._streams[ln])
             self._last_graph = graphs[0]
             self._last_graphs = graphs
+        for st, final_step in finals:           # the purity chain's ordinary reverse step at t = 0, after the lane's replays
+            with torch.cuda.stream(st):
+                final_step()
+                if trace is not None:           # (a trace runs in one lane)
+                    trace.append(toks[0].clone())
         for ln in range(lanes):
             cur.wait_stream(self._streams[ln])
             toks[ln].record_stream(cur)
@@ -640,7 +778,7 @@ class DiffusionTransformer(nn.Module):
         self._range_flags = range_flags
         self._last_lanes = lanes
         self._last_plan = plan
-        self._last_draws = n_steps + (1 if plan.q_sample else 0)
+        self._last_draws = (2 * n_steps + (1 if plan.final else 0)) if purity else n_steps + (1 if q_sample else 0)
         self.noise_stream += self._last_draws
         out = {"content_token": tok}
         if return_logits:
@@ -809,9 +947,13 @@ class DiscreteDiffusion(nn.Module):
 
     zero_text_emb=True is the reference as written: both text embeddings are replaced by zeros (discrete_diffusion.py:25, :49).
     False lets the captions condition the denoiser.
-    sample_skip_step=None samples with DiffusionTransformer.sample (every timestep); an int s samples with sample_fast(skip_step=s)."""
+    sample_skip_step=None samples with DiffusionTransformer.sample (every timestep); an int s samples with sample_fast(skip_step=s).
+    sample_prior_rule / sample_prior_weight / sample_prior_ps: when not None, set the diffusion model's prior_rule / prior_weight /
+    prior_ps before sampling (purity-prior inference; prior_ps also reloads the reference's n_sample list);
+    sample_prior_scale_schedule=True rescales that list from 1024 tokens to the model's content_seq_len (scaled_n_sample)."""
 
-    def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, **kwargs):
+    def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
+                 sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, **kwargs):
         super().__init__()
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -824,6 +966,23 @@ class DiscreteDiffusion(nn.Module):
                                              or sample_skip_step < 0):
             raise GsddError(f"sample_skip_step must be null or a non-negative int, got {sample_skip_step!r}")
         self.sample_skip_step = None if sample_skip_step is None else int(sample_skip_step)
+        is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if sample_prior_rule is not None and not (is_int(sample_prior_rule) and sample_prior_rule in (0, 1, 2)):
+            raise GsddError(f"sample_prior_rule must be null, 0, 1 or 2, got {sample_prior_rule!r}")
+        if sample_prior_weight is not None and (isinstance(sample_prior_weight, bool) or not isinstance(sample_prior_weight, numbers.Real)
+                                                or not sample_prior_weight >= 0):
+            raise GsddError(f"sample_prior_weight must be null or a number >= 0, got {sample_prior_weight!r}")
+        if sample_prior_ps is not None and not (is_int(sample_prior_ps) and sample_prior_ps >= 1):
+            raise GsddError(f"sample_prior_ps must be null or an int >= 1, got {sample_prior_ps!r}")
+        if not isinstance(sample_prior_scale_schedule, bool):
+            raise GsddError(f"sample_prior_scale_schedule must be true or false, got {sample_prior_scale_schedule!r}")
+        if sample_prior_rule and self.sample_skip_step is not None:
+            raise GsddError("sample_prior_rule > 0 and sample_skip_step cannot be combined: sample_fast has no purity prior "
+                            "(diffusion_transformer.py:648-713)")
+        self.sample_prior_rule = None if sample_prior_rule is None else int(sample_prior_rule)
+        self.sample_prior_weight = None if sample_prior_weight is None else float(sample_prior_weight)
+        self.sample_prior_ps = None if sample_prior_ps is None else int(sample_prior_ps)
+        self.sample_prior_scale_schedule = sample_prior_scale_schedule
 
     def _text(self, texts, dev):
         emb = self.textencoder(texts)
@@ -891,6 +1050,19 @@ class DiscreteDiffusion(nn.Module):
         if text_emb is None:
             text_emb = self._text(texts, dev)
         cf_emb = self._text([""] * B, dev)                                              # :46-49
+        dm = self.diffusion_model
+        if self.sample_prior_rule is not None:
+            dm.prior_rule = self.sample_prior_rule
+        if self.sample_prior_weight is not None:
+            dm.prior_weight = self.sample_prior_weight
+        if self.sample_prior_ps is not None:
+            dm.prior_ps = self.sample_prior_ps
+            dm.update_n_sample()
+        if self.sample_prior_scale_schedule and self.sample_skip_step is None and dm.prior_rule:
+            ref = reference_n_sample(dm.num_timesteps, dm.prior_ps)
+            if ref is None:
+                raise GsddError(f"sample_prior_scale_schedule: the reference has no n_sample list for num_timesteps = {dm.num_timesteps}")
+            dm.n_sample = scaled_n_sample(ref, dm.shape)
         if self.sample_skip_step is None:
             out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=None, filter_ratio=0)
         else:

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib as abi
-from ._lib import GemmDesc, GsddError, LayerDesc, StepDesc, TrainDesc, check, lib, ptr, stream_ptr
+from ._lib import GemmDesc, GsddError, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, check, lib, ptr, stream_ptr
 
 ACT_NONE, ACT_RELU, ACT_GELU2 = 0, 1, 2
 
@@ -417,6 +417,42 @@ def advance_floor(t_dev, dt, t_min, stream_dev, ds, stream=None):
     """t = max(t + dt, t_min), stream += ds on the device (the skip-step sampler's loop counter)."""
     B = 0 if t_dev is None else t_dev.numel()
     check(lib().gsdd_advance_floor(ptr(t_dev), B, dt, t_min, ptr(stream_dev), ds, stream_ptr(stream)))
+
+
+def d3pm_purity_step(logits_c, logits_u, score, smax, cand, stream_dev, *, K, guidance, prior_rule, prior_weight, seed, row0=0,
+                     recon_dbg=None, prob_dbg=None, score_dbg=None, stream=None):
+    """First half of a purity-prior call (gsdd_d3pm_purity_step): raw scores (B, L), their per-sample maximum (B,) and the candidate
+    tokens (B, L) from the denoiser's logits."""
+    B, L = cand.shape
+    d = PurityDesc()
+    d.logits_c, d.logits_u = ptr(logits_c), ptr(logits_u)
+    d.B, d.L, d.K = B, L, K
+    d.guidance, d.prior_rule, d.prior_weight = guidance, int(prior_rule), float(prior_weight)
+    d.seed, d.stream_dev, d.row0 = seed, ptr(stream_dev), row0
+    d.score, d.smax, d.cand = ptr(score), ptr(smax), ptr(cand)
+    d.recon_dbg, d.prob_dbg, d.score_dbg = ptr(recon_dbg), ptr(prob_dbg), ptr(score_dbg)
+    check(lib().gsdd_d3pm_purity_step(C.byref(d), stream_ptr(stream)))
+    return cand
+
+
+def d3pm_purity_select(tok_in, tok_out, cand, score, smax, n_dev, stream_dev, *, K, prior_rule, seed, stream_add=0, row0=0,
+                       key_dbg=None, stream=None):
+    """Second half (gsdd_d3pm_purity_select): reveal n_dev[0] of each sample's [MASK] positions, Gumbel-top-n on the (B, L) draw at
+    stream stream_dev[0] + stream_add."""
+    B, L = tok_in.shape
+    d = PuritySelectDesc()
+    d.tok_in, d.tok_out, d.cand, d.score, d.smax = ptr(tok_in), ptr(tok_out), ptr(cand), ptr(score), ptr(smax)
+    d.B, d.L, d.K, d.prior_rule = B, L, K, int(prior_rule)
+    d.n_dev, d.seed, d.stream_dev, d.stream_add, d.row0 = ptr(n_dev), seed, ptr(stream_dev), int(stream_add), row0
+    d.key_dbg = ptr(key_dbg)
+    check(lib().gsdd_d3pm_purity_select(C.byref(d), stream_ptr(stream)))
+    return tok_out
+
+
+def advance_plan(step_dev, plan_t, plan_n, t_dev, n_dev, stream_dev, ds, stream=None):
+    """step += 1; t[:] = plan_t[min(step, len - 1)], n = plan_n[...]; stream += ds -- on the device (the purity chain's counter)."""
+    check(lib().gsdd_advance_plan(ptr(step_dev), ptr(plan_t), ptr(plan_n), plan_t.numel(), ptr(t_dev), t_dev.numel(), ptr(n_dev),
+                                  ptr(stream_dev), ds, stream_ptr(stream)))
 
 
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):

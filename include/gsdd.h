@@ -33,7 +33,7 @@ extern "C" {
 const char* gsdd_last_error(void);
 int gsdd_version(void);
 /* sizeof of a descriptor struct as this build of the library sees it (which: 0 gsdd_gemm_desc, 1 gsdd_layer_desc, 2 gsdd_step_desc,
- * 3 gsdd_train_desc; anything else: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
+ * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc; anything else: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
  * library built from another revision of this header fails at load time instead of misreading a descriptor. */
 int64_t gsdd_abi_sizeof(int which);
 
@@ -326,6 +326,64 @@ typedef struct {
 } gsdd_step_desc;
 int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream);
 
+/* Purity-prior reverse step, device half 1 of 2 (p_sample with prior_rule 1 / 2 at t > 0, diffusion_transformer.py:304-326; Improved
+ * VQ-Diffusion's high-quality inference).  Per position: log_x_recon = the guided cf_predict_start row exactly as gsdd_d3pm_step
+ * computes it (no posterior: that branch drops it), then
+ *   score[pos] = exp(max_k log_x_recon)  (prior_rule 2)   or 1  (prior_rule 1)                              -- the RAW score (:316)
+ *   smax[b]    = max_l score[b][l]
+ *   cand[pos]  = Gumbel arg-max (first index on ties) of `prob` over the K+1 rows, with
+ *                prob = log_x_recon                                                        (rule 1, or prior_weight == 0)
+ *                prob = log softmax((1 + prior_weight * score / (smax + 1e-10)) * log_x_recon), clamped to [-70, 0]   (rule 2, Eq. 11)
+ * The uniforms are the (B, K+1, L) Philox draw of gsdd_d3pm_step at stream stream_dev[0].  Rule 2 with prior_weight > 0 reads the
+ * logits twice (scores, smax, draw); otherwise once.  score: float[B*L], smax: float[B], cand: int64[B*L] are outputs that
+ * gsdd_d3pm_purity_select consumes.  recon_dbg / prob_dbg: optional [B][K+1][L]; score_dbg: optional [B*L], the normalised score
+ * score / (smax + 1e-10) (test hooks, compiled into a separate instantiation). */
+typedef struct {
+    const float* logits_c;
+    const float* logits_u;      /* may be NULL: no guidance                                  */
+    int B, L, K;
+    float guidance;
+    int prior_rule;             /* 1 or 2                                                    */
+    float prior_weight;         /* r of Eq. 11, >= 0                                         */
+    uint64_t seed;
+    const int64_t* stream_dev;
+    int64_t row0;               /* global row (position) offset of this shard                */
+    float* score;
+    float* smax;
+    int64_t* cand;
+    float* recon_dbg;
+    float* prob_dbg;
+    float* score_dbg;
+} gsdd_purity_desc;
+int gsdd_d3pm_purity_step(const gsdd_purity_desc* d, void* stream);
+
+/* Purity-prior reverse step, device half 2 of 2 (:329-346): per sample, reveal n of the [MASK] positions of tok_in, drawn without
+ * replacement with weights w_l = score_l / (smax_b + 1e-10) (rule 2) or 1 (rule 1) -- torch.multinomial(_score[i], n) restated as
+ * Gumbel-top-n:
+ *   key_l = logf(w_l) - logf(-logf(u_l + 1e-30) + 1e-30)   on positions with tok_in == K; the n largest keys win, ties to the lower l;
+ *   tok_out[l] = cand[l] there, tok_in[l] elsewhere (tok_out may alias tok_in).
+ * u is ONE (B, L) Philox draw at stream stream_dev[0] + stream_add: counter = row * ceil(L / 4) + (l >> 2), word l & 3, where row is the
+ * GLOBAL sample index row0 / L + b (row0 as in gsdd_purity_desc, a multiple of L) -- the layout of oracle/philox.py uniform_rows(seed,
+ * stream, B, L, row0 / L) -- so the selection does not depend on how a batch is split over lanes or GPUs.
+ * n = n_dev[0], read on the device (clamped to [0, L]; when fewer [MASK] positions are left, all of them are revealed and nothing else
+ * changes).  L <= 4096 (one sample is sorted in LDS); larger L is GSDD_E_ARG.  key_dbg: optional float[B*L], the keys (test hook). */
+typedef struct {
+    const int64_t* tok_in;
+    int64_t* tok_out;
+    const int64_t* cand;
+    const float* score;         /* rule 2 only                                               */
+    const float* smax;          /* rule 2 only                                               */
+    int B, L, K;
+    int prior_rule;
+    const int64_t* n_dev;
+    uint64_t seed;
+    const int64_t* stream_dev;
+    int64_t stream_add;
+    int64_t row0;
+    float* key_dbg;
+} gsdd_purity_select_desc;
+int gsdd_d3pm_purity_select(const gsdd_purity_select_desc* d, void* stream);
+
 /* q_sample for training: tok_out = Gumbel-argmax(q_pred(onehot(x0), t)), diffusion_transformer.py:361-366 */
 int gsdd_d3pm_q_sample(const int64_t* x0, int64_t* xt, int B, int L, int K, int T,
                        const float* const* sched, const int64_t* t_dev, uint64_t seed,
@@ -427,6 +485,12 @@ int gsdd_adam_multi_dev(const int64_t* table, int n_blocks, float lr, float beta
 int gsdd_advance(int64_t* t_dev, int B, int64_t dt, int64_t* stream_dev, int64_t ds, void* stream);
 /* t[b] = max(t[b] + dt, t_min) ; stream[0] += ds   (the skip-step sampler's counter: t moves by -(1 + s) and stops at 0) */
 int gsdd_advance_floor(int64_t* t_dev, int B, int64_t dt, int64_t t_min, int64_t* stream_dev, int64_t ds, void* stream);
+
+/* The purity chain's counter: step[0] += 1; i = min(step[0], n_calls - 1); t[b] = plan_t[i] (b < B); n[0] = plan_n[i]; stream[0] += ds.
+ * plan_t / plan_n: device int64[n_calls], the (t, n) of every purity call (d3pm.purity_plan); placed after a call inside the captured
+ * graph it loads the next call's timestep and reveal count, so that one graph replays the whole chain. */
+int gsdd_advance_plan(int64_t* step_dev, const int64_t* plan_t, const int64_t* plan_n, int64_t n_calls, int64_t* t_dev, int B,
+                      int64_t* n_dev, int64_t* stream_dev, int64_t ds, void* stream);
 
 /* uniform Philox floats, layout of oracle/philox.py uniform_rows (test hook) */
 int gsdd_philox_uniform(uint64_t seed, int64_t stream_id, int64_t row0, int64_t n_rows, int n_cols,

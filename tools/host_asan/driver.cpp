@@ -158,6 +158,51 @@ int main() {
         d.K = K; d.sched[3] = nullptr;
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
         EXPECT(gsdd_d3pm_q_sample(devp<int64_t>(), devp<int64_t>(), B, L, K, T, sched, devp<int64_t>(), 1, devp<int64_t>(), 0, st), GSDD_OK, true);
+        {   // purity-prior step: scores + candidates, selection, plan counter
+            gsdd_purity_desc p;
+            std::memset(&p, 0, sizeof p);
+            p.logits_c = devp(); p.logits_u = devp(); p.B = B; p.L = L; p.K = K; p.guidance = 2.f; p.prior_rule = 2; p.seed = 1;
+            p.stream_dev = devp<int64_t>(); p.score = devp(); p.smax = devp(); p.cand = devp<int64_t>();
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // one pass
+            p.prior_weight = 1.f;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // scores, smax, draw
+            p.recon_dbg = devp(); p.prob_dbg = devp(); p.score_dbg = devp();
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // the hooked instantiation
+            p.recon_dbg = p.prob_dbg = p.score_dbg = nullptr;
+            p.prior_rule = 1; p.logits_u = nullptr;
+            for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { p.K = k; EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true); }
+            p.K = 30;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_E_ARG, false);
+            p.K = K; p.prior_rule = 0;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_E_ARG, false);
+            p.prior_rule = 2; p.prior_weight = -1.f;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_E_ARG, false);
+            p.prior_weight = 0.f; p.smax = nullptr;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_purity_step(nullptr, st), GSDD_E_ARG, false);
+            gsdd_purity_select_desc s;
+            std::memset(&s, 0, sizeof s);
+            s.tok_in = devp<int64_t>(); s.tok_out = devp<int64_t>(); s.cand = devp<int64_t>(); s.score = devp(); s.smax = devp();
+            s.B = B; s.L = L; s.K = K; s.prior_rule = 2; s.n_dev = devp<int64_t>(); s.seed = 1; s.stream_dev = devp<int64_t>();
+            s.stream_add = 1; s.row0 = 3 * (int64_t)L;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_OK, true);
+            s.prior_rule = 1; s.score = nullptr; s.smax = nullptr;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_OK, true);
+            s.prior_rule = 2;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_E_ARG, false);            // rule 2 needs the scores
+            s.prior_rule = 1; s.row0 = 5;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_E_ARG, false);            // row0 is a multiple of L
+            s.row0 = 0; s.L = 4097;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_E_ARG, false);            // one sample is sorted in LDS
+            s.L = L; s.n_dev = nullptr;
+            EXPECT(gsdd_d3pm_purity_select(&s, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_advance_plan(devp<int64_t>(), devp<int64_t>(), devp<int64_t>(), 42, devp<int64_t>(), B, devp<int64_t>(),
+                                     devp<int64_t>(), 2, st), GSDD_OK, true);
+            EXPECT(gsdd_advance_plan(devp<int64_t>(), devp<int64_t>(), devp<int64_t>(), 0, devp<int64_t>(), B, devp<int64_t>(),
+                                     devp<int64_t>(), 2, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_advance_plan(devp<int64_t>(), nullptr, devp<int64_t>(), 42, devp<int64_t>(), B, devp<int64_t>(), nullptr, 2, st),
+                   GSDD_E_ARG, false);
+        }
         gsdd_train_desc t;
         std::memset(&t, 0, sizeof t);
         t.logits = devp(); t.x0 = devp<int64_t>(); t.xt = devp<int64_t>(); t.t_dev = devp<int64_t>(); t.pt = devp();
