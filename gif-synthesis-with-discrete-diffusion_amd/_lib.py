@@ -49,7 +49,7 @@ class StepDesc(C.Structure):
         ("sched", _p * 8), ("t_dev", _p), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
         ("post_dbg", _p), ("x0_dbg", _p), ("occupancy", _i),
         # (post_skip sits in the struct's tail padding: gsdd_abi_sizeof cannot see it missing -- keep it in step with gsdd.h by hand)
-        ("post_skip", _i),
+        ("post_skip", _i), ("trunc_rate", C.c_float),
     ]
 
 
@@ -58,6 +58,7 @@ class PurityDesc(C.Structure):
         ("logits_c", _p), ("logits_u", _p), ("B", _i), ("L", _i), ("K", _i), ("guidance", C.c_float),
         ("prior_rule", _i), ("prior_weight", C.c_float), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
         ("score", _p), ("smax", _p), ("cand", _p), ("recon_dbg", _p), ("prob_dbg", _p), ("score_dbg", _p),
+        ("trunc_rate", C.c_float),
     ]
 
 

@@ -21,8 +21,11 @@ namespace gsdd {
 //         The debug hooks exist in this mode only (the host runs MODE 1 -> smax -> MODE 2 whenever a hook is set).
 // FULL / OCC as in d3pm_step_kernel: at K = 4096 two 64-register rows are live through the guidance mix, which needs the 256-VGPR
 // budget of two waves per SIMD to stay out of scratch memory.
-template <int J, bool FULL, int MODE, bool DBG, int OCC = 3>
-__global__ __launch_bounds__(256, OCC) void d3pm_purity_kernel(gsdd_purity_desc d) {
+// TRUNC: top-r truncation of log_x_recon (truncate_row) before the score and `prob`, in a kernel family of its own
+// (d3pm_purity_trunc_kernel); the plain kernels compile the body with TRUNC = false.  The row maximum is always kept, so the score
+// of a truncated call is the plain call's.
+template <int J, bool FULL, int MODE, bool DBG, bool TRUNC>
+__device__ __forceinline__ void d3pm_purity_body(const gsdd_purity_desc& d) {
     const int lane = threadIdx.x & 63;
     const int64_t pos = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (pos >= (int64_t)d.B * d.L) return;
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(256, OCC) void d3pm_purity_kernel(gsdd_purity_desc 
             for (int e = 0; e < 4; ++e) x0[j][e] = valid ? clamp70(x0[j][e] - lse) : NEG;
         }
     }
+    if (TRUNC && MODE != 1) truncate_row<J, FULL>(x0, d.trunc_rate, lane, K);     // (the score pass reads the maximum only)
     if (DBG && d.recon_dbg != nullptr) {
 #pragma unroll
         for (int j = 0; j < J; ++j)
@@ -155,6 +159,16 @@ __global__ __launch_bounds__(256, OCC) void d3pm_purity_kernel(gsdd_purity_desc 
     if (lane == 0) d.cand[pos] = win;
 }
 
+template <int J, bool FULL, int MODE, bool DBG, int OCC = 3>
+__global__ __launch_bounds__(256, OCC) void d3pm_purity_kernel(gsdd_purity_desc d) {
+    d3pm_purity_body<J, FULL, MODE, DBG, false>(d);
+}
+
+template <int J, bool FULL, int MODE, bool DBG>
+__global__ __launch_bounds__(256, 2) void d3pm_purity_trunc_kernel(gsdd_purity_desc d) {
+    d3pm_purity_body<J, FULL, MODE, DBG, true>(d);
+}
+
 // smax[b] = max_l score[b][l]   (scores are in (0, 1])
 __global__ __launch_bounds__(256) void purity_smax_kernel(const float* score, int L, float* smax) {
     __shared__ float red[4];
@@ -169,12 +183,6 @@ __global__ __launch_bounds__(256) void purity_smax_kernel(const float* score, in
 
 constexpr int SELECT_MAX_L = 4096;
 constexpr int SELECT_THREADS = 1024;
-
-// order-preserving bits of a float: a < b  <=>  ordered(a) < ordered(b); every float (-inf included) maps above 0
-__device__ __forceinline__ uint32_t ordered_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // Weighted selection without replacement (torch.multinomial(_score[i], n), :341) as Gumbel-top-n: key_l = log w_l + Gumbel(u_l) on the
 // [MASK] positions, the n largest keys win, ties go to the lower index.  The pairs (ordered key bits, ~l) are sorted in LDS, largest
@@ -255,6 +263,7 @@ extern "C" int gsdd_d3pm_purity_step(const gsdd_purity_desc* d, void* stream) {
     GSDD_CHECK_ARG(d->K >= 4 && d->K % 4 == 0 && d->K <= 8192, "K must be a multiple of 4 in [4, 8192]");
     GSDD_CHECK_ARG(d->prior_rule == 1 || d->prior_rule == 2, "prior_rule must be 1 or 2 (0 is the plain step: gsdd_d3pm_step)");
     GSDD_CHECK_ARG(d->prior_weight >= 0.f, "prior_weight must be >= 0");
+    GSDD_CHECK_ARG(d->trunc_rate == 0.f || (d->trunc_rate > 0.f && d->trunc_rate < 1.f), "trunc_rate must be 0 (off) or in (0, 1)");
     const int64_t npos = (int64_t)d->B * d->L;
     const dim3 grid((unsigned)((npos + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -262,7 +271,25 @@ extern "C" int gsdd_d3pm_purity_step(const gsdd_purity_desc* d, void* stream) {
     const bool dbg = d->recon_dbg != nullptr || d->prob_dbg != nullptr || d->score_dbg != nullptr;
     const bool two_pass = dbg || (d->prior_rule == 2 && d->prior_weight > 0.f);
     // pass: 0 = the fused score + draw, 1 = scores, 2 = draw
+    const bool trunc = d->trunc_rate != 0.f;
     auto launch = [&](int mode) {
+        if (trunc && mode != 1) {                    // top-r truncation: the d3pm_purity_trunc_kernel family (the score pass has no use for it)
+#define GSDD_PURITY_TRUNC_LAUNCH(JJ, FF)                                                                                     \
+    do {                                                                                                                     \
+        if (mode == 0) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 0, false>), grid, block, 0, st, *d);            \
+        else if (!dbg) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 2, false>), grid, block, 0, st, *d);            \
+        else hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 2, true>), grid, block, 0, st, *d);                       \
+    } while (0)
+            if (d->K == 4096) GSDD_PURITY_TRUNC_LAUNCH(16, true);
+            else if (J <= 1) GSDD_PURITY_TRUNC_LAUNCH(1, false);
+            else if (J <= 2) GSDD_PURITY_TRUNC_LAUNCH(2, false);
+            else if (J <= 4) GSDD_PURITY_TRUNC_LAUNCH(4, false);
+            else if (J <= 8) GSDD_PURITY_TRUNC_LAUNCH(8, false);
+            else if (J <= 16) GSDD_PURITY_TRUNC_LAUNCH(16, false);
+            else GSDD_PURITY_TRUNC_LAUNCH(32, false);
+#undef GSDD_PURITY_TRUNC_LAUNCH
+            return;
+        }
         if (d->K == 4096 && !dbg) {                  // the production shape: every slot holds a class, no hooks, no scratch
             if (mode == 0) hipLaunchKernelGGL((d3pm_purity_kernel<16, true, 0, false, 2>), grid, block, 0, st, *d);
             else if (mode == 1) hipLaunchKernelGGL((d3pm_purity_kernel<16, true, 1, false, 2>), grid, block, 0, st, *d);

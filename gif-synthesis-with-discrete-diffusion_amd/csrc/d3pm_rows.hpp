@@ -1,6 +1,6 @@
 // Register-resident class rows of the D3PM kernels (d3pm_step.hip, d3pm_purity.hip): one wave64 owns one token position, lane owns
 // quads k = 4*lane + 256*j; the restricted-range expf / logf, the reference's log_add_exp, the fp64-sum log_softmax, the wave
-// log-sum-exp, the Gumbel transform and the first-index arg-max they share.
+// log-sum-exp, the top-r truncation, the Gumbel transform and the first-index arg-max they share.
 #pragma once
 #include "common.hpp"
 
@@ -113,6 +113,56 @@ __device__ __forceinline__ float wave_logsumexp(const float (&x)[J][4], float ex
     se = wave_sum(se);
     if (has_extra) se += exp_le0(extra - mx);
     return mx + logf(se);
+}
+
+// order-preserving bits of a float: a < b  <=>  ordered(a) < ordered(b); every float (-inf included) maps above 0
+__device__ __forceinline__ uint32_t ordered_bits(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(uint32_t o) {       // the inverse
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// Top-r truncation of a final log p(x0 | x_t) row (VQ-Diffusion's predict_start_with_truncation, "top0.86r"): class k is kept iff
+// the probability mass strictly above it, sum_{x_j > x_k} exp(x_j), is below rate; every other class drops to -70 (no renormalising:
+// the posterior normalises itself).  Equal values are kept or cut together, the row maximum is always kept, and an entry already at
+// -70 does not change either way.  No sort: the mass above a value v is non-increasing in v, so the cut value -- the smallest c with
+// mass_above(c) < rate -- is found by bisection on the order-preserving integer image of the floats in [-70, 0] (at most 31 probes,
+// each one compare-and-accumulate over the lane's slots on the exponentials kept in registers, plus one wave reduction).  The lane
+// sums are fp32 in slot order, the sum across lanes is fp64: the 64 lane sums enter as the same binary tree whatever the lane.
+// The probe loop's bounds and verdict are wave-uniform (scalar registers, scalar branch).  An empty slot (-inf, K < 256 J) stays -inf.
+template <int J, bool FULL>
+__device__ __forceinline__ void truncate_row(float (&x)[J][4], float rate, int lane, int K) {
+    float p[J][4];
+    float mx = -70.f;
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            p[j][e] = exp_le0(x[j][e]);                         // (an empty slot: exp(-inf) = 0)
+            mx = fmaxf(mx, x[j][e]);
+        }
+    uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_bits(wave_max(mx)));   // mass_above(row maximum) = 0 < rate
+    uint32_t lo = ordered_bits(-70.f) - 1u;                     // below every entry: "mass_above >= rate" by convention
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const float v = ordered_float(mid);
+        float m = 0.f;
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m += (x[j][e] > v) ? p[j][e] : 0.f;
+        const bool below = (float)wave_sum((double)m) < rate;
+        if (__builtin_amdgcn_readfirstlane((int)below)) hi = mid; else lo = mid;
+    }
+    const float cut = ordered_float(hi);
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const bool valid = FULL || (4 * lane + 256 * j) < K;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[j][e] = valid ? ((x[j][e] >= cut) ? x[j][e] : -70.f) : -INFINITY;
+    }
 }
 
 __device__ __forceinline__ float gumbel(float u) {  // log_sample_categorical (:355-356); u in [0, 1)

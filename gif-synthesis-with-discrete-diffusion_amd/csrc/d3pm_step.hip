@@ -21,8 +21,11 @@ namespace gsdd {
 // OCC = waves per SIMD the register budget is sized for: 3 -> 168 VGPRs, 2 -> 256.  At K = 4096 (J = 16) the two 64-register
 // rows plus the temporaries of the unrolled class loops need ~180: with OCC = 3 the compiler parks 8 of them in scratch memory
 // (2 KB written per position, 131 MB per launch at B*L = 65536 -- the WRITE_SIZE of profiles/r1_pmc_traffic.csv); OCC = 2 has none.
-template <int J, bool FULL, bool DBG, int OCC = 3>
-__global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, SchedPtrs sp) {
+// TRUNC: top-r truncation of the guided row (truncate_row, d3pm_rows.hpp) between the guidance mix and the posterior.  It is a
+// kernel family of its own (d3pm_step_trunc_kernel): the plain kernels compile the body with TRUNC = false, instruction for
+// instruction what they were before the option existed.
+template <int J, bool FULL, bool DBG, bool TRUNC>
+__device__ __forceinline__ void d3pm_step_body(const gsdd_step_desc& d, const SchedPtrs& sp) {
     const int lane = threadIdx.x & 63;
     const int64_t pos = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (pos >= (int64_t)d.B * d.L) return;
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, S
             for (int e = 0; e < 4; ++e) x0[j][e] = valid ? clamp70(x0[j][e] - lse) : NEG;
         }
     }
+    if (TRUNC) truncate_row<J, FULL>(x0, d.trunc_rate, lane, K);
     if (DBG && d.x0_dbg != nullptr) {
 #pragma unroll
         for (int j = 0; j < J; ++j)
@@ -153,6 +157,17 @@ __global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, S
     }
     const int win = wave_argmax(best, best_k);
     if (lane == 0) d.tok_out[pos] = win;
+}
+
+template <int J, bool FULL, bool DBG, int OCC = 3>
+__global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, SchedPtrs sp) {
+    d3pm_step_body<J, FULL, DBG, false>(d, sp);
+}
+
+// the truncated family: two waves per SIMD throughout (the exponentials of the row take the 64 registers xu leaves)
+template <int J, bool FULL, bool DBG>
+__global__ __launch_bounds__(256, 2) void d3pm_step_trunc_kernel(gsdd_step_desc d, SchedPtrs sp) {
+    d3pm_step_body<J, FULL, DBG, true>(d, sp);
 }
 
 // q_sample (:361-366): x_t ~ Gumbel-argmax(q_pred(onehot(x0), t))
@@ -648,6 +663,24 @@ extern "C" int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream) {
     const bool dbg = d->post_dbg != nullptr || d->x0_dbg != nullptr;
     GSDD_CHECK_ARG(d->occupancy == 0 || d->occupancy == 2 || d->occupancy == 3, "occupancy: 0 (auto), 2 or 3 waves per SIMD");
     GSDD_CHECK_ARG(d->post_skip >= 0, "post_skip must be >= 0");
+    GSDD_CHECK_ARG(d->trunc_rate == 0.f || (d->trunc_rate > 0.f && d->trunc_rate < 1.f), "trunc_rate must be 0 (off) or in (0, 1)");
+    if (d->trunc_rate != 0.f) {                    // top-r truncated sampling: the d3pm_step_trunc_kernel family (FULL at K = 4096 only)
+#define GSDD_STEP_TRUNC_LAUNCH(JJ, FF)                                                                               \
+    do {                                                                                                             \
+        if (!dbg) hipLaunchKernelGGL((d3pm_step_trunc_kernel<JJ, FF, false>), grid, block, 0, st, *d, sp);           \
+        else hipLaunchKernelGGL((d3pm_step_trunc_kernel<JJ, FF, true>), grid, block, 0, st, *d, sp);                 \
+    } while (0)
+        if (d->K == 4096) GSDD_STEP_TRUNC_LAUNCH(16, true);
+        else if (J <= 1) GSDD_STEP_TRUNC_LAUNCH(1, false);
+        else if (J <= 2) GSDD_STEP_TRUNC_LAUNCH(2, false);
+        else if (J <= 4) GSDD_STEP_TRUNC_LAUNCH(4, false);
+        else if (J <= 8) GSDD_STEP_TRUNC_LAUNCH(8, false);
+        else if (J <= 16) GSDD_STEP_TRUNC_LAUNCH(16, false);
+        else GSDD_STEP_TRUNC_LAUNCH(32, false);
+#undef GSDD_STEP_TRUNC_LAUNCH
+        GSDD_CHECK_LAUNCH();
+        return GSDD_OK;
+    }
     if (J > 8 && J <= 16 && d->K == 4096 && !dbg && d->occupancy != 3) {       // the production shape: no scratch (see the kernel's note)
         hipLaunchKernelGGL((d3pm_step_kernel<16, true, false, 2>), grid, block, 0, st, *d, sp);
         GSDD_CHECK_LAUNCH();

@@ -9,6 +9,7 @@ step, replayed diffusion_step times with the timestep and the Philox stream id l
 import collections
 import collections.abc
 import contextlib
+import ctypes
 import numbers
 import os
 
@@ -483,6 +484,26 @@ def scaled_n_sample(n_sample, L, L_ref=1024):
     return out
 
 
+def check_truncation_rate(rate, name="truncation_rate"):
+    """-> None (no truncation) or the rate as a float.  Top-r truncated sampling (VQ-Diffusion's predict_start_with_truncation,
+    "top0.86r") keeps, per position, the classes whose probability mass strictly above them is below r and drops the rest to -70 before
+    the posterior / the purity draw.  r must be a real number with 0 < r < 1 as the kernel's fp32 sees it."""
+    if rate is None:
+        return None
+    ok = not isinstance(rate, bool) and isinstance(rate, numbers.Real) and 0 < rate < 1
+    if ok:
+        ok = 0 < ctypes.c_float(float(rate)).value < 1
+    if not ok:
+        raise GsddError(f"{name} must be None or a real number in (0, 1), got {rate!r}; 1 is rejected because whether the last class "
+                        f"survives would then depend on rounding -- use None to sample without truncation")
+    return float(rate)
+
+
+def _trunc_kwargs(rate):
+    """The keyword a truncated launch adds to ops.d3pm_step / ops.d3pm_purity_step; nothing at all without truncation."""
+    return {} if rate is None else {"trunc_rate": float(rate)}
+
+
 SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct",
                "log_1_min_cumprod_ct")
 
@@ -526,6 +547,7 @@ class DiffusionTransformer(nn.Module):
         self.prior_weight = 0        # r of Eq. 11, Improved VQ-Diffusion
         self.n_sample = None         # reveals per timestep (update_n_sample; None: the reference has no list for this T)
         self.update_n_sample()
+        self.truncation_rate = None  # None: no truncation; 0 < r < 1: top-r truncated sampling (upstream's "top0.86r" is 0.86)
         self.learnable_cf = learnable_cf
         self.guidance_scale = guidance_scale
         self.noise_seed = 0          # Philox key; the stream id advances with every draw
@@ -594,17 +616,18 @@ class DiffusionTransformer(nn.Module):
         prior_rule 1 / 2 (attributes, as in the reference): the purity-prior chain of `purity_plan` -- every call at t > 0 runs the
         denoiser, draws a candidate per position and reveals the n most trusted [MASK] positions (two noise streams per call);
         the step at t = 0 is the ordinary one."""
+        trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
         if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
             raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
         if self.prior_rule != 0:        # purity-prior inference (:304-346): reveal n_sample[t] trusted positions per timestep
             return self._sample_checked(self._purity_plan(start_step), condition_token, condition_embed, cf_condition_embed,
-                                        return_logits=return_logits, use_graph=use_graph, trace=trace, **kwargs)
+                                        return_logits=return_logits, use_graph=use_graph, trace=trace, truncation_rate=trunc, **kwargs)
         if start_step != 0 and content_token is None:
             raise GsddError("filter_ratio > 0 needs content_token (the tokens to start from)")
         return self._sample_checked(sample_plan(self.num_timesteps, start_step=start_step), condition_token, condition_embed,
                                     cf_condition_embed, content_token=content_token, return_logits=return_logits,
-                                    use_graph=use_graph, trace=trace, **kwargs)
+                                    use_graph=use_graph, trace=trace, truncation_rate=trunc, **kwargs)
 
     @torch.no_grad()
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
@@ -615,6 +638,7 @@ class DiffusionTransformer(nn.Module):
         reference asserts.  The reference passes cf_predict_start three of its four arguments; the
         unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit."""
         T = self.num_timesteps
+        trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         if int(T * filter_ratio) != 0:
             raise GsddError(f"sample_fast starts from all-[MASK] only: int(num_timesteps * filter_ratio) = {int(T * filter_ratio)}, "
                             "must be 0 (diffusion_transformer.py:686)")
@@ -625,7 +649,7 @@ class DiffusionTransformer(nn.Module):
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
         return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
-                                    use_graph=use_graph, trace=trace, **kwargs)
+                                    use_graph=use_graph, trace=trace, truncation_rate=trunc, **kwargs)
 
     def _sample_checked(self, plan, *args, trace=None, **kw):
         """`_sample_once`, then one read of the layer kernel's range flags after the loop (outside graph capture): if an activation left
@@ -643,8 +667,9 @@ class DiffusionTransformer(nn.Module):
         return out
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
-                     use_graph=True, trace=None, **kwargs):
+                     use_graph=True, trace=None, truncation_rate=None, **kwargs):
         dev = self.device
+        trunc_kw = _trunc_kwargs(truncation_rate)   # a launch constant of both step kernels: the captured graph records it
         if dev.type != "cuda":
             raise GsddError("sampling runs on the HIP path only: move the module to a ROCm device")
         B = len(condition_token) if condition_token is not None else kwargs["batch_size"]
@@ -713,7 +738,7 @@ class DiffusionTransformer(nn.Module):
                 def plain_step(post_skip, tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st):
                     logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
                     ops.d3pm_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, tok, tok, sched, t2, sid, K=K, T=T,
-                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st)
+                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st, **trunc_kw)
 
                 if purity:
                     # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
@@ -729,7 +754,7 @@ class DiffusionTransformer(nn.Module):
                         logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
                         ops.d3pm_purity_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, score, smax, cand, sid,
                                              K=K, guidance=float(self.guidance_scale), prior_rule=plan.rule, prior_weight=plan.weight,
-                                             seed=self.noise_seed, row0=row0, stream=st)
+                                             seed=self.noise_seed, row0=row0, stream=st, **trunc_kw)
                         ops.d3pm_purity_select(tok, tok, cand, score, smax, n_dev, sid, K=K, prior_rule=plan.rule, seed=self.noise_seed,
                                                stream_add=1, row0=row0, stream=st)
                         ops.advance_plan(step_dev, plan_t, plan_n, t2, n_dev, sid, 2, stream=st)
@@ -791,9 +816,10 @@ class DiffusionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ single-step pieces (parity tests, training glue)
     @torch.no_grad()
-    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0):
+    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0, truncation_rate=None):
         """One reverse step on tokens (p_sample, diffusion_transformer.py:304-352, prior_rule 0); post_skip > 0: the posterior at
-        t - post_skip for t > post_skip (a sample_fast step, :700-704)."""
+        t - post_skip for t > post_skip (a sample_fast step, :700-704); truncation_rate: top-r truncation of the guided row."""
+        trunc_kw = _trunc_kwargs(check_truncation_rate(truncation_rate))
         dev = tok.device
         B, L = tok.shape
         K, T = self.num_classes - 1, self.num_timesteps
@@ -810,7 +836,7 @@ class DiffusionTransformer(nn.Module):
         M = B * L
         ops.d3pm_step(logits[:M], logits[M:] if guided else None, tok, out, self._sched(), t2, sid, K=K, T=T,
                       guidance=float(self.guidance_scale), seed=self.noise_seed, row0=self.row_offset * L,
-                      post_dbg=post_dbg, x0_dbg=x0_dbg, post_skip=post_skip)
+                      post_dbg=post_dbg, x0_dbg=x0_dbg, post_skip=post_skip, **trunc_kw)
         return out
 
     # ------------------------------------------------------------------ training objective (forward value)
@@ -950,10 +976,13 @@ class DiscreteDiffusion(nn.Module):
     sample_skip_step=None samples with DiffusionTransformer.sample (every timestep); an int s samples with sample_fast(skip_step=s).
     sample_prior_rule / sample_prior_weight / sample_prior_ps: when not None, set the diffusion model's prior_rule / prior_weight /
     prior_ps before sampling (purity-prior inference; prior_ps also reloads the reference's n_sample list);
-    sample_prior_scale_schedule=True rescales that list from 1024 tokens to the model's content_seq_len (scaled_n_sample)."""
+    sample_prior_scale_schedule=True rescales that list from 1024 tokens to the model's content_seq_len (scaled_n_sample).
+    sample_truncation_rate: when not None, sets the diffusion model's truncation_rate before sampling (top-r truncated sampling,
+    0 < r < 1; VQ-Diffusion's inference uses 0.86)."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
-                 sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, **kwargs):
+                 sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
+                 **kwargs):
         super().__init__()
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -983,6 +1012,7 @@ class DiscreteDiffusion(nn.Module):
         self.sample_prior_weight = None if sample_prior_weight is None else float(sample_prior_weight)
         self.sample_prior_ps = None if sample_prior_ps is None else int(sample_prior_ps)
         self.sample_prior_scale_schedule = sample_prior_scale_schedule
+        self.sample_truncation_rate = check_truncation_rate(sample_truncation_rate, "sample_truncation_rate")
 
     def _text(self, texts, dev):
         emb = self.textencoder(texts)
@@ -1058,6 +1088,8 @@ class DiscreteDiffusion(nn.Module):
         if self.sample_prior_ps is not None:
             dm.prior_ps = self.sample_prior_ps
             dm.update_n_sample()
+        if self.sample_truncation_rate is not None:
+            dm.truncation_rate = self.sample_truncation_rate
         if self.sample_prior_scale_schedule and self.sample_skip_step is None and dm.prior_rule:
             ref = reference_n_sample(dm.num_timesteps, dm.prior_ps)
             if ref is None:

@@ -331,10 +331,12 @@ def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None):
 
 
 def d3pm_step(logits_c, logits_u, tok_in, tok_out, sched, t_dev, stream_dev, *, K, T, guidance, seed, row0=0,
-              post_dbg=None, x0_dbg=None, post_skip=0, stream=None):
+              post_dbg=None, x0_dbg=None, post_skip=0, trunc_rate=None, stream=None):
+    """trunc_rate: None (off) or 0 < r < 1, top-r truncation of the guided row before the posterior (gsdd_step_desc.trunc_rate)."""
     B, L = tok_in.shape
     d = StepDesc()
     d.post_skip = int(post_skip)
+    d.trunc_rate = 0.0 if trunc_rate is None else float(trunc_rate)
     d.occupancy = int(os.environ.get("GSDD_STEP_OCC", "0"))
     d.logits_c, d.logits_u = ptr(logits_c), ptr(logits_u)
     d.tok_in, d.tok_out = ptr(tok_in), ptr(tok_out)
@@ -420,9 +422,9 @@ def advance_floor(t_dev, dt, t_min, stream_dev, ds, stream=None):
 
 
 def d3pm_purity_step(logits_c, logits_u, score, smax, cand, stream_dev, *, K, guidance, prior_rule, prior_weight, seed, row0=0,
-                     recon_dbg=None, prob_dbg=None, score_dbg=None, stream=None):
+                     recon_dbg=None, prob_dbg=None, score_dbg=None, trunc_rate=None, stream=None):
     """First half of a purity-prior call (gsdd_d3pm_purity_step): raw scores (B, L), their per-sample maximum (B,) and the candidate
-    tokens (B, L) from the denoiser's logits."""
+    tokens (B, L) from the denoiser's logits.  trunc_rate: None (off) or 0 < r < 1, top-r truncation of log_x_recon."""
     B, L = cand.shape
     d = PurityDesc()
     d.logits_c, d.logits_u = ptr(logits_c), ptr(logits_u)
@@ -431,6 +433,7 @@ def d3pm_purity_step(logits_c, logits_u, score, smax, cand, stream_dev, *, K, gu
     d.seed, d.stream_dev, d.row0 = seed, ptr(stream_dev), row0
     d.score, d.smax, d.cand = ptr(score), ptr(smax), ptr(cand)
     d.recon_dbg, d.prob_dbg, d.score_dbg = ptr(recon_dbg), ptr(prob_dbg), ptr(score_dbg)
+    d.trunc_rate = 0.0 if trunc_rate is None else float(trunc_rate)
     check(lib().gsdd_d3pm_purity_step(C.byref(d), stream_ptr(stream)))
     return cand
 

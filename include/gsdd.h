@@ -323,6 +323,9 @@ typedef struct {
     int post_skip;              /* >= 0; the posterior runs at t' = t - post_skip when t > post_skip, else at t' = t (skip-step */
                                 /* sampling, diffusion_transformer.py:700-704); the denoiser's logits are those of step t.     */
                                 /* 0 = the plain reverse step                                                                  */
+    float trunc_rate;           /* 0 = off, or 0 < r < 1: top-r truncated sampling (VQ-Diffusion's predict_start_with_truncation, */
+                                /* "top0.86r").  Of the guided row, class k is kept iff sum_{x_j > x_k} exp(x_j) < r; every other  */
+                                /* class drops to -70, without renormalising, before the posterior.  x0_dbg shows the cut row.    */
 } gsdd_step_desc;
 int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream);
 
@@ -354,6 +357,8 @@ typedef struct {
     float* recon_dbg;
     float* prob_dbg;
     float* score_dbg;
+    float trunc_rate;           /* 0 = off, or 0 < r < 1: log_x_recon is top-r truncated as in gsdd_step_desc before the score,  */
+                                /* `prob` and the draw (recon_dbg shows the cut row; the score keeps its value: the maximum stays) */
 } gsdd_purity_desc;
 int gsdd_d3pm_purity_step(const gsdd_purity_desc* d, void* stream);
 

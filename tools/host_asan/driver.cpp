@@ -148,6 +148,10 @@ int main() {
         d.post_skip = -1;
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
         d.post_skip = 0;
+        d.trunc_rate = 0.86f;                                                    // top-r truncation: the truncated kernel family
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true);
+        for (float bad : {1.f, -0.5f, 1.5f}) { d.trunc_rate = bad; EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false); }
+        d.trunc_rate = 0.f;
         EXPECT(gsdd_advance_floor(devp<int64_t>(), B, -4, 0, devp<int64_t>(), 1, st), GSDD_OK, true);
         EXPECT(gsdd_advance_floor(devp<int64_t>(), -1, -4, 0, devp<int64_t>(), 1, st), GSDD_E_ARG, false);
         for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { d.K = k; EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true); }
@@ -168,7 +172,13 @@ int main() {
             EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // scores, smax, draw
             p.recon_dbg = devp(); p.prob_dbg = devp(); p.score_dbg = devp();
             EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // the hooked instantiation
+            p.trunc_rate = 0.86f;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);                // hooked and truncated
             p.recon_dbg = p.prob_dbg = p.score_dbg = nullptr;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true);
+            p.trunc_rate = 1.f;
+            EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_E_ARG, false);
+            p.trunc_rate = 0.f;
             p.prior_rule = 1; p.logits_u = nullptr;
             for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { p.K = k; EXPECT(gsdd_d3pm_purity_step(&p, st), GSDD_OK, true); }
             p.K = 30;
