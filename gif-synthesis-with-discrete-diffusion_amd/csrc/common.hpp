@@ -184,6 +184,11 @@ __device__ __forceinline__ float row16_max(float v) {
     v = dpp_max<0x141>(v);       // row_half_mirror
     return dpp_max<0x140>(v);    // row_mirror
 }
+// plain DPP move (lanes whose source falls outside the row read 0)
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
 __device__ __forceinline__ float row16_min(float v) {
     v = dpp_min<0xB1>(v);
     v = dpp_min<0x4E>(v);

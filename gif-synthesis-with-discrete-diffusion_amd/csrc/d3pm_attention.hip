@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
                                                                 const uint4* __restrict__ vp, const float* __restrict__ knorm,
                                                                 const float4* __restrict__ ksum, int B, int L, int H,
                                                                 float* __restrict__ out,
-                                                                float* __restrict__ lse, unsigned long long* __restrict__ redo) {
+                                                                float* __restrict__ lse, unsigned long long* __restrict__ redo, int lean) {
     __shared__ AttnSmem4<KC4> sm;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nqb = (L + 255) / 256;
@@ -489,13 +489,17 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     const int li = lane & 15, lg = lane >> 4;
     const int q0 = qblk * 256 + wave * 64;
 
-    // PM >= 2: the tile norms and key sums of this (b, h), requested first so that their latency hides behind the q splits, the first
-    // chunk's staging and the first 64 keys' score maximum (they are consumed just before the chunk loop)
+    // PM >= 2: the tile norms and key sums of this (b, h), requested first so that their latency hides behind the q splits and the
+    // first chunk's loads.  They are the same numbers in every wave of the workgroup: wave 0 reduces them and hands them to the others
+    // through two unused entries of sm.ones, ahead of the barrier that follows the first chunk's staging.
     float knm = 0.f;
     float4 ks = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (PM >= 2) {
+    bool kn_odd = false;                        // some tile norm is inf or NaN (fmaxf drops a NaN: knm alone would not show it)
+    if (PM >= 2 && wave == 0) {
         for (int i = lane; i < (L >> 5); i += 64) {
-            knm = fmaxf(knm, knh[i]);
+            const float n = knh[i];
+            knm = fmaxf(knm, n);
+            kn_odd = kn_odd || !(n < 3.0e38f);
             const float4 t = ksh[i];
             ks.x += t.x; ks.y += t.y; ks.z += t.z; ks.w += t.w;
         }
@@ -506,6 +510,7 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     const float qscale = 0.5f * 1.4426950408889634f;
     uint4 qfrag[4];
     float rqn[4];                               // PM >= 2: 1 / (||q'|| of query li, rounded up): the score bound's slope
+    float qn[4];                                // PM >= 2: that ||q'||, rounded up
     float4 qsv[4];                              // PM >= 2: q' of query li (log2 domain), for the row-sum lower bound
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -519,7 +524,8 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         const uint4 f0 = pack8(q1, q1), f1 = pack8(q2, q2), f2 = pack8(q1, q3);
         qfrag[j] = lg == 0 ? f0 : (lg == 1 ? f1 : (lg == 2 ? f2 : make_uint4(0u, 0u, 0u, 0u)));
         // 1.0001: the split products, the norms' own rounding and v_rcp/v_log/v_sqrt (1 ulp each) are all below 2^-20 relative
-        rqn[j] = 1.0f / (sqrtf((qs[0] * qs[0] + qs[1] * qs[1]) + (qs[2] * qs[2] + qs[3] * qs[3])) * 1.0001f + 1e-30f);
+        qn[j] = sqrtf((qs[0] * qs[0] + qs[1] * qs[1]) + (qs[2] * qs[2] + qs[3] * qs[3])) * 1.0001f + 1e-30f;
+        rqn[j] = 1.0f / qn[j];
         qsv[j] = make_float4(qs[0], qs[1], qs[2], qs[3]);
     }
 
@@ -527,16 +533,27 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     // chunk staging = plain copy of the pre-split images: K 768 uint4 + V 768 uint4 per 384-key chunk
     uint4 rk0, rk1, rk2, rv0, rv1, rv2;
     float rkn = 0.f, kn_cur = 0.f;              // PM >= 2: lane u < KC4 / 32 holds the norm bound of pair-tile u of the chunk
-    auto load_chunk = [&](int c) {
+    // Each thread copies uint4 tid, tid + 256 and tid + 512 of both images: the chunk's base is wave-uniform (scalar registers) and
+    // the three 32-bit offsets are the same for every chunk and for both images, so a full chunk costs no address arithmetic at all.
+    const unsigned so0 = (unsigned)tid, so1 = (unsigned)tid + 256u, so2 = (unsigned)tid + 512u;
+    auto load_chunk = [&](int c, bool norms) {
         // Unconditional loads from a clamped index: a load under "cond ? p[i] : zero" becomes a *flat* load from either the
         // image or a scratch copy of the zero, and flat loads also count on lgkmcnt, so the first LDS fragment wait of the chunk
         // would wait for global memory.  Rows past a short last chunk are staged but never read (npairs bounds the tile loop).
-        const int last = 2 * min(KC4, L - c * KC4) - 1;           // keys: a multiple of 32
+        // Only a short last chunk needs the clamp at all.
+        const int rem = L - c * KC4;                              // keys left: a multiple of 32
         const uint4* ksrc = kph + (int64_t)c * KC4 * 2;
         const uint4* vsrc = vph + (int64_t)c * (KC4 / 32) * 64;
-        rk0 = ksrc[min(tid, last)]; rk1 = ksrc[min(tid + 256, last)]; rk2 = ksrc[min(tid + 512, last)];
-        rv0 = vsrc[min(tid, last)]; rv1 = vsrc[min(tid + 256, last)]; rv2 = vsrc[min(tid + 512, last)];
-        if (PM >= 2) rkn = knh[min(c * (KC4 / 32) + min(lane, KC4 / 32 - 1), (L >> 5) - 1)];
+        if (2 * KC4 == 768 && rem >= KC4) {                       // (the 256-key development variant stages 512 uint4: always clamped)
+            rk0 = ksrc[so0]; rk1 = ksrc[so1]; rk2 = ksrc[so2];
+            rv0 = vsrc[so0]; rv1 = vsrc[so1]; rv2 = vsrc[so2];
+        } else {
+            const unsigned last = 2u * (unsigned)rem - 1u;
+            const unsigned c0 = min(so0, last), c1 = min(so1, last), c2 = min(so2, last);
+            rk0 = ksrc[c0]; rk1 = ksrc[c1]; rk2 = ksrc[c2];
+            rv0 = vsrc[c0]; rv1 = vsrc[c1]; rv2 = vsrc[c2];
+        }
+        if (PM >= 2 && norms) rkn = knh[min(c * (KC4 / 32) + min(lane, KC4 / 32 - 1), (L >> 5) - 1)];
     };
     auto store_chunk = [&](int buf, int) {
         uint4* kd = &sm.k[buf][0][0];
@@ -555,7 +572,17 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     }
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
-    load_chunk(0);
+    load_chunk(0, true);
+    if (PM >= 2 && wave == 0) {
+        // (after the sm.ones initialisation above: the same wave, and a wave's LDS writes land in program order)
+        knm = wave_max(knm);
+        ks.x = wave_sum(ks.x); ks.y = wave_sum(ks.y); ks.z = wave_sum(ks.z); ks.w = wave_sum(ks.w);
+        const bool odd = __any(kn_odd);
+        if (lane == 0) {
+            sm.ones[2] = make_uint4(__float_as_uint(ks.x), __float_as_uint(ks.y), __float_as_uint(ks.z), __float_as_uint(ks.w));
+            sm.ones[3] = make_uint4(__float_as_uint(knm), odd ? 1u : 0u, 0u, 0u);
+        }
+    }
     store_chunk(0, 0);
     __syncthreads();
     const int slot = ((lg >> 1) ^ (li >> 3)) & 1;
@@ -579,6 +606,7 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     }
 
     bool prescan = false;                       // wave-uniform
+    bool quiet = false;                         // wave-uniform: this wave takes the lean chunk loop (below)
     // PM >= 2: whether this wave tests tiles at all is decided chunk by chunk.  The first chunk has no row sum to compare with; after
     // that a chunk runs the adaptive loop, and if fewer than half of its tiles could skip the lo half the wave goes back to the plain
     // hi + lo loop (no per-tile test, one basic block per pair-tile) and probes again later, each time twice as much later (a row
@@ -595,7 +623,9 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         //     ||q'|| knorm[u] - m < log2(L) - PM - ||q'|| KNmax - m   <=>   knorm[u] < (log2(L) - PM - slack) / ||q'|| - KNmax.
         // With near-flat rows (||q'|| ||k|| << log2(L) - PM = 4 at L = 4096) this clears every tile of every chunk, the first included,
         // and the running-sum form below never has to be computed.
-        knm = wave_max(knm) * 1.0001f;
+        const uint4 shk = sm.ones[2], shn = sm.ones[3];             // wave 0's reductions (the same bits each wave used to compute)
+        knm = __uint_as_float(shn.x) * 1.0001f;
+        ks = make_float4(__uint_as_float(shk.x), __uint_as_float(shk.y), __uint_as_float(shk.z), __uint_as_float(shk.w));
         const float budget = log2f((float)L) - (float)PM - 0.02f;
         // Sharper, and per query: Jensen -- log2 sum_j 2^(q'.k_j) >= log2(L) + q'.kmean, kmean from the per-tile key sums the K image's
         // producer left next to the tile norms (fixed summation order: the same bits in every workgroup and every run).  It is within
@@ -603,19 +633,48 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         // It replaces the a priori row sum in the tile bound, and it gives the measured test a threshold relative to the FINAL row sum from
         // the first chunk on (the running sum after one chunk of eleven is 3.5 bits short of it, which made early chunks of rows that are
         // nowhere near peaked take the lo half: trained-like weights).
-        ks.x = wave_sum(ks.x); ks.y = wave_sum(ks.y); ks.z = wave_sum(ks.z); ks.w = wave_sum(ks.w);
         const float invL = 1.0f / (float)L;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float dx = qsv[j].x * ks.x, dy = qsv[j].y * ks.y, dz = qsv[j].z * ks.z, dw = qsv[j].w * ks.w;
             const float mean = ((dx + dy) + (dz + dw)) * invL, mag = ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw))) * invL;
             jb[j] = log2f((float)L) + mean - 1e-5f * mag - 0.02f;       // slack: the float sums behind kmean and the dot product
-            kbj[j] = row16_min(fmaxf(fmaxf(budget * rqn[j] - knm, (jb[j] - (float)PM) * rqn[j]), 0.f));
+            // (a query with a NaN in it has a NaN output row whatever its tiles do: it must not take the lo-half decision away from
+            // the fifteen queries that share its sub-tile, so it drops out of the minimum)
+            const float kbq0 = fmaxf(fmaxf(budget * rqn[j] - knm, (jb[j] - (float)PM) * rqn[j]), 0.f);
+            kbj[j] = row16_min(qn[j] != qn[j] ? INFINITY : kbq0);
+        }
+        // A "quiet" wave (wave-uniform, decided once): nothing the general loop's bookkeeping guards against can happen in any chunk.
+        //  (a) every tile of the (b, h) is cleared: knm bounds every tile norm from above and the kbj in hand only ever grow, so each
+        //      chunk's masks would come out all ones and each chunk would run the hi-only loop;
+        //  (b) no probability gets near the f16 overflow the screen looks for: every score of query q is at most ||q'|| KNmax
+        //      (Cauchy-Schwarz, the 1.0001 factors cover the roundings), so 2^(s - m) <= 2^15: a full octave below 2^16, and the f32
+        //      accumulators cannot overflow on f16-range products either.  No overflow: no redo, and the offsets m never move.
+        // Both compares are false for a NaN, and an inf or NaN among the tile norms is flagged by wave 0: such waves stay general.
+        if (lean != 0) {
+            bool ok = shn.y == 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ok = ok && (knm < kbj[j]) && (qn[j] * knm - mq[j] <= 15.f);
+            quiet = __all(ok);
         }
     }
+    if (PM >= 2 && quiet) {
+        // The lean chunk loop: the tile sequence of the general loop's cleared chunks (the same MFMAs in the same order, hence the same
+        // bits) without the chunk-start copy, the masks, the tile norms, the overflow screen and the attempt loop.  One barrier per chunk
+        // as in the general loop: quiet and other waves of a workgroup meet at the same barriers.
+        const uint32_t none[4] = {0u, 0u, 0u, 0u};
+        for (int c = 0; c < nchunks; ++c) {
+            const int buf = c & 1;
+            if (c + 1 < nchunks) load_chunk(c + 1, false);
+            const int npairs = min(KC4, L - c * KC4) >> 5;
+            attn_tiles<KC4, 0>(sm, buf, npairs, kbase0 + buf * kbuf, kstep, lg, li, qfrag, acc, none, none);
+            if (c + 1 < nchunks) store_chunk(buf ^ 1, c + 1);
+            __syncthreads();
+        }
+    } else
     for (int c = 0; c < nchunks; ++c) {
         const int buf = c & 1;
-        if (c + 1 < nchunks) load_chunk(c + 1);
+        if (c + 1 < nchunks) load_chunk(c + 1, true);
         const int npairs = min(KC4, L - c * KC4) >> 5;
         const uint4* kb = kbase0 + buf * kbuf;
 #pragma unroll
@@ -708,6 +767,10 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
             }
             moved = true;
             if (lane == 0 && redo != nullptr) atomicAdd(redo, 1ull);
+            // The last attempt keeps what it computed.  Attempts only run out when the screen fires on something no offset can cure --
+            // a NaN or inf that came in with q, k or v -- and restoring the chunk-start copy once more would drop the whole chunk for
+            // all 64 queries of the wave (every row sum 0, every output 0 / 0) instead of leaving the NaN in the rows it belongs to.
+            if (attempt == 15) break;
           }
             // exact maximum of this chunk's scores per query (relative to the current m), then move m so that the chunk maximum lands
             // in (2^2, 2^3]; accumulators restart from the chunk-start copy scaled by 2^-delta.  After an overflow only the queries
@@ -745,21 +808,40 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     }
 
     // ---- epilogue: D[query][col], col on the lane (l&15): out_d = D[d] + D[4+d]/2^11 + D[8+d]/2^22, row sum = D[12]
+    // Lanes li < 4 of each 16-lane row store; their operands sit in the same row at lanes li + 4, li + 8 and 12: DPP row moves, not
+    // the LDS permute path.  The store address is a wave-uniform row base plus one 32-bit lane offset for all sixteen stores.
+    // Byte offsets in 32 bits: a workgroup's 256 output rows span 256 * H * 16 bytes.
+    const unsigned orow = (unsigned)(H * 16);
+    const unsigned ovo = (unsigned)(4 * lg) * orow + (unsigned)(li * 4);
+    char* const ob = reinterpret_cast<char*>(out + ((int64_t)b * L + q0) * (H * 4) + h * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+        if (q0 + 16 * j >= L) break;                                      // (L % 16 == 0: the sub-tile's 16 queries leave together)
+        float a1[4], a2[4], l[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float a = acc[j][r];
-            const int rowbase = lane & 48;
-            const float a1 = __shfl(a, rowbase + (li & 3) + 4);
-            const float a2 = __shfl(a, rowbase + (li & 3) + 8);
-            const float l = __shfl(a, rowbase + 12);
-            const float mrow = __shfl(mq[j], rowbase + 4 * lg + r);       // this row's exponent offset lives on lane (query li)
-            const int qi = q0 + 16 * j + 4 * lg + r;
-            if (li < 4 && qi < L) {
-                const float o = (a + a1 * 0.00048828125f + a2 * 2.384185791015625e-07f) / l;
-                out[((int64_t)b * L + qi) * (H * 4) + h * 4 + li] = o;
-                if (lse != nullptr && li == 0) lse[(int64_t)h * M + (int64_t)b * L + qi] = mrow + log2f(l);   // log2 domain
+        for (int r = 0; r < 4; ++r) {                                       // (every lane takes part in the moves: only then the store lanes split off)
+            a1[r] = dpp_mov<0x104>(acc[j][r]);                              // row_shl:4  lane i <- lane i + 4
+            a2[r] = dpp_mov<0x108>(acc[j][r]);                              // row_shl:8
+            l[r] = dpp_mov<0x10C>(dpp_mov<0x00>(acc[j][r]));                // quad broadcast of lane 12 to 12..15, then row_shl:12
+        }
+        if (li < 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float o = (acc[j][r] + a1[r] * 0.00048828125f + a2[r] * 2.384185791015625e-07f) / l[r];
+                *reinterpret_cast<float*>(ob + (ovo + (unsigned)(16 * j + r) * orow)) = o;
+            }
+        }
+    }
+    if (lse != nullptr) {                                                 // training forward only: a pass of its own keeps the sampler's straight
+        char* const lb = reinterpret_cast<char*>(lse + (int64_t)h * M + (int64_t)b * L + q0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (q0 + 16 * j >= L) break;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float l = dpp_mov<0x10C>(dpp_mov<0x00>(acc[j][r]));
+                const float mrow = __shfl(mq[j], (lane & 48) + 4 * lg + r);   // this row's exponent offset lives on lane (query li)
+                if (li == 0) *reinterpret_cast<float*>(lb + (unsigned)(4 * (16 * j + r) + 16 * lg)) = mrow + log2f(l);   // log2 domain
             }
         }
     }
@@ -825,6 +907,8 @@ int gsdd_attention_valu(const float* q, const float* k, const float* v, int B, i
 extern "C" int gsdd_d3pm_attention(const float* q, const float* k, const float* v, int B, int L, int H, float* out,
                                    void* workspace, int64_t workspace_bytes, uint64_t* redo_events, int mode, void* stream) {
     GSDD_CHECK_ARG(q && out && ((k == nullptr) == (v == nullptr)), "null pointer");
+    const int lean = (mode & GSDD_ATTN_NOLEAN) ? 0 : 1;              // (only the adaptive kernels look at it)
+    mode &= ~GSDD_ATTN_NOLEAN;
     GSDD_CHECK_ARG(mode >= GSDD_ATTN_AUTO && mode <= GSDD_ATTN_KC256, "mode: one of GSDD_ATTN_*");
     GSDD_CHECK_ARG(B > 0 && H > 0 && L > 0, "bad sizes");
     GSDD_CHECK_ARG((int64_t)B * H * ((L + 255) / 256) < (1ll << 31), "grid too large");
@@ -849,11 +933,11 @@ extern "C" int gsdd_d3pm_attention(const float* q, const float* k, const float* 
         const bool kc256 = mode == GSDD_ATTN_KC256;          // development variant: 256-key chunks, hi + lo everywhere
         const int pmode = attn_p_mode(mode, L);
         float* nolse = nullptr;
-        if (kc256) hipLaunchKernelGGL(d3pm_attention_v4_kernel<256>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo);
-        else if (pmode == 0) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 0>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo);
-        else if (pmode == 8) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo);
-        else if (pmode == 12) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 12>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo);
-        else hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo);
+        if (kc256) hipLaunchKernelGGL(d3pm_attention_v4_kernel<256>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 0) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 0>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 8) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 12) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 12>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
+        else hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
     } else {
         hipLaunchKernelGGL(d3pm_attention_kernel, grid, dim3(256), 0, st, q, k, v, B, L, H, out);      // (never redoes a chunk)
     }
@@ -866,6 +950,8 @@ extern "C" int gsdd_d3pm_attention(const float* q, const float* k, const float* 
 int gsdd_attention_v4_with_lse(const float* q, const float* k, const float* v, int B, int L, int H, float* out, float* lse,
                                void* workspace, int64_t workspace_bytes, int mode, void* stream, int* done) {
     *done = 0;
+    const int lean = (mode & GSDD_ATTN_NOLEAN) ? 0 : 1;
+    mode &= ~GSDD_ATTN_NOLEAN;
     GSDD_CHECK_ARG(mode == GSDD_ATTN_AUTO || mode == GSDD_ATTN_P22 || mode == GSDD_ATTN_A8,
                    "training forward: mode is GSDD_ATTN_AUTO, GSDD_ATTN_P22 or GSDD_ATTN_A8");
     if (L % 32 != 0 || workspace == nullptr) return GSDD_OK;
@@ -886,10 +972,10 @@ int gsdd_attention_v4_with_lse(const float* q, const float* k, const float* v, i
     // everywhere, the round-2 behaviour; GSDD_ATTN_A8: adaptive at any L.
     if (mode == GSDD_ATTN_A8 || (mode == GSDD_ATTN_AUTO && L >= 2048))
         hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, ksm,
-                           B, L, H, out, lse, noredo);
+                           B, L, H, out, lse, noredo, lean);
     else
         hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, ksm,
-                           B, L, H, out, lse, noredo);
+                           B, L, H, out, lse, noredo, lean);
     GSDD_CHECK_LAUNCH();
     *done = 1;
     return GSDD_OK;

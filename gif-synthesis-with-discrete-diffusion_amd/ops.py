@@ -51,6 +51,14 @@ def attn_train_mode(mode=None):
     return m
 
 
+def attn_lean_flag():
+    """GSDD_ATTN_LEAN=0: every wave of the adaptive attention kernels takes the general chunk loop (OR-ed into the mode argument)."""
+    v = os.environ.get("GSDD_ATTN_LEAN", "1")
+    if v not in ("0", "1"):
+        raise GsddError(f"GSDD_ATTN_LEAN: {v!r} is not one of '0', '1'")
+    return abi.ATTN_NOLEAN if v == "0" else 0
+
+
 def attn_bwd_variant(variant=None):
     """GSDD_ATTN_BWD = valu | split | fqc64 | fqc128 | nw8 | dbg1 | dbg2 (development variants of the attention backward)."""
     return _pick(_ATTN_BWD_VARIANTS, variant if variant is not None else os.environ.get("GSDD_ATTN_BWD", "auto"), "GSDD_ATTN_BWD")
@@ -253,7 +261,7 @@ def d3pm_attention(q, k, v, B, L, H, out, ws=None, redo=None, mode=None, stream=
     redo: optional int64[1] device counter of the kernel's chunk-redo events (caller-owned; see include/gsdd.h).
     mode: 'auto' | '22' | '11' | 'a8' | 'a12' | 'f32pv' | 'kc256' (GSDD_ATTN_* of include/gsdd.h); None -> the environment, else auto."""
     nbytes = 0 if ws is None else ws.numel() * 4
-    check(lib().gsdd_d3pm_attention(ptr(q), ptr(k), ptr(v), B, L, H, ptr(out), ptr(ws), nbytes, ptr(redo), attn_mode(mode),
+    check(lib().gsdd_d3pm_attention(ptr(q), ptr(k), ptr(v), B, L, H, ptr(out), ptr(ws), nbytes, ptr(redo), attn_mode(mode) | attn_lean_flag(),
                                     stream_ptr(stream)))
     return out
 
@@ -566,7 +574,7 @@ def batch_rowsum(Y, B, L, out=None, stream=None):
 
 def d3pm_attention_train(q, k, v, B, L, H, out, lse, ws=None, mode=None, stream=None):
     check(lib().gsdd_d3pm_attention_train(ptr(q), ptr(k), ptr(v), B, L, H, ptr(out), ptr(lse), ptr(ws),
-                                          0 if ws is None else ws.numel() * ws.element_size(), attn_train_mode(mode), stream_ptr(stream)))
+                                          0 if ws is None else ws.numel() * ws.element_size(), attn_train_mode(mode) | attn_lean_flag(), stream_ptr(stream)))
 
 
 def d3pm_attention_bwd_workspace(B, L, H, device):

@@ -207,7 +207,10 @@ int64_t gsdd_d3pm_attention_workspace_bytes(int B, int L, int H);
  *   GSDD_ATTN_A8     adaptive: lo half only in (16-query, 32-key) tiles that can hold a probability above 2^-8 of the row sum
  *   GSDD_ATTN_A12    the same with threshold 2^-12
  *   GSDD_ATTN_F32PV  the workspace-free kernel (exact-f32 P.V) even when a workspace is given (k, v must be given)
- *   GSDD_ATTN_KC256  development variant: 256-key chunks, hi + lo everywhere */
+ *   GSDD_ATTN_KC256  development variant: 256-key chunks, hi + lo everywhere
+ * GSDD_ATTN_NOLEAN may be OR-ed into any of them (here and in gsdd_d3pm_attention_train): the adaptive kernels then send every wave
+ * through the general chunk loop, also the "quiet" waves whose bounds prove up front that no tile needs a lo half and no f16 can
+ * overflow and which otherwise take a loop without that bookkeeping.  Same bits either way: for tests and A/B timing. */
 #define GSDD_ATTN_AUTO 0
 #define GSDD_ATTN_P22 1
 #define GSDD_ATTN_P11 2
@@ -215,6 +218,7 @@ int64_t gsdd_d3pm_attention_workspace_bytes(int B, int L, int H);
 #define GSDD_ATTN_A12 4
 #define GSDD_ATTN_F32PV 5
 #define GSDD_ATTN_KC256 6
+#define GSDD_ATTN_NOLEAN 256
 int gsdd_d3pm_attention(const float* q, const float* k, const float* v, int B, int L, int H,
                         float* out, void* workspace, int64_t workspace_bytes, uint64_t* redo_events, int mode, void* stream);
 
