@@ -189,6 +189,11 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
+// DPP move into the lanes that BANKS selects (bit b: lanes 4 b .. 4 b + 3 of every row); the other lanes keep `old`
+template <int CTRL, int BANKS>
+__device__ __forceinline__ float dpp_merge(float old, float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xf, BANKS, false));
+}
 __device__ __forceinline__ float row16_min(float v) {
     v = dpp_min<0xB1>(v);
     v = dpp_min<0x4E>(v);

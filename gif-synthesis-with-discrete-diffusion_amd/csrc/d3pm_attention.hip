@@ -509,9 +509,6 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
 
     const float qscale = 0.5f * 1.4426950408889634f;
     uint4 qfrag[4];
-    float rqn[4];                               // PM >= 2: 1 / (||q'|| of query li, rounded up): the score bound's slope
-    float qn[4];                                // PM >= 2: that ||q'||, rounded up
-    float4 qsv[4];                              // PM >= 2: q' of query li (log2 domain), for the row-sum lower bound
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         int qi = q0 + 16 * j + li;
@@ -523,10 +520,20 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         for (int d = 0; d < 4; ++d) split3(qs[d], q1[d], q2[d], q3[d]);
         const uint4 f0 = pack8(q1, q1), f1 = pack8(q2, q2), f2 = pack8(q1, q3);
         qfrag[j] = lg == 0 ? f0 : (lg == 1 ? f1 : (lg == 2 ? f2 : make_uint4(0u, 0u, 0u, 0u)));
+    }
+    // PM >= 2: the bound numbers belong to a query, not to a fragment: lane l computes those of query q0 + l (= sub-tile lg, row li) once,
+    // where the fragment layout above would have the four lanes (li, 0..3) each evaluate the same four queries.
+    float qno = 0.f;                            // ||q'|| of the lane's own query, rounded up
+    float rqno = 0.f;                           // 1 / that: the score bound's slope
+    float4 qso = make_float4(0.f, 0.f, 0.f, 0.f);   // its q' (log2 domain), for the row-sum lower bound
+    if (PM >= 2) {
+        int qi = q0 + lane;
+        qi = qi < L ? qi : L - 1;
+        const float4 qv = *reinterpret_cast<const float4*>(qh + (int64_t)qi * 4);
+        qso = make_float4(qv.x * qscale, qv.y * qscale, qv.z * qscale, qv.w * qscale);
         // 1.0001: the split products, the norms' own rounding and v_rcp/v_log/v_sqrt (1 ulp each) are all below 2^-20 relative
-        qn[j] = sqrtf((qs[0] * qs[0] + qs[1] * qs[1]) + (qs[2] * qs[2] + qs[3] * qs[3])) * 1.0001f + 1e-30f;
-        rqn[j] = 1.0f / qn[j];
-        qsv[j] = make_float4(qs[0], qs[1], qs[2], qs[3]);
+        qno = sqrtf((qso.x * qso.x + qso.y * qso.y) + (qso.z * qso.z + qso.w * qso.w)) * 1.0001f + 1e-30f;
+        rqno = 1.0f / qno;
     }
 
     const int nchunks = (L + KC4 - 1) / KC4;
@@ -590,13 +597,24 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     const int kstep = (lg == 3) ? 0 : 32;
     const int kbuf = (lg == 3) ? 0 : KC4 * 2;
     {   // m = ceil(max over the first 64 keys) - 3, shared by the 4 key groups of a query
+        // (a maximum that starts from -inf does not depend on the order its operands are folded in: a NaN score drops out of every
+        // step, and a zero's sign is gone after ceil(m) - 3.  L >= 64: the four tiles' MFMAs back to back, then two v_max3 per tile.)
         const int nt0 = min(4, L >> 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float m0 = -INFINITY;
-            for (int t = 0; t < nt0; ++t) {
-                const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kbase0[t * kstep]), as_frag(qfrag[j]), zero, 0, 0, 0);
-                m0 = fmaxf(m0, fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+            if (nt0 == 4) {
+                f32x4 s[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kbase0[t * kstep]), as_frag(qfrag[j]), zero, 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) m0 = fmaxf(fmaxf(fmaxf(fmaxf(m0, s[t][0]), s[t][1]), s[t][2]), s[t][3]);
+            } else {
+                for (int t = 0; t < nt0; ++t) {
+                    const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(kbase0[t * kstep]), as_frag(qfrag[j]), zero, 0, 0, 0);
+                    m0 = fmaxf(m0, fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+                }
             }
             m0 = fmaxf(m0, __shfl_xor(m0, 16));
             m0 = fmaxf(m0, __shfl_xor(m0, 32));
@@ -613,7 +631,7 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     // that was not flat after 384 keys seldom becomes flat): chunks 1, 6, 15, 32, ...
     bool adapt = PM >= 2;                       // (the row-sum lower bound below gives the first chunk a threshold too)
     int probe = 1, backoff = 4;
-    float jb[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // log2 of a lower bound of query li's FINAL row sum (absolute scale)
+    float jbo = -INFINITY;                      // log2 of a lower bound of the FINAL row sum of the lane's own query (absolute scale)
     float kbj[4] = {0.f, 0.f, 0.f, 0.f};        // the bound's per-sub-tile numbers (wave-uniform values); 0 = clears nothing
     int kb_next = 1, kb_gap = 1;                // chunk of the next recomputation, and the gap after it
     if (PM >= 2) {
@@ -634,16 +652,16 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         // the first chunk on (the running sum after one chunk of eleven is 3.5 bits short of it, which made early chunks of rows that are
         // nowhere near peaked take the lo half: trained-like weights).
         const float invL = 1.0f / (float)L;
+        const float dx = qso.x * ks.x, dy = qso.y * ks.y, dz = qso.z * ks.z, dw = qso.w * ks.w;
+        const float mean = ((dx + dy) + (dz + dw)) * invL, mag = ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw))) * invL;
+        jbo = log2f((float)L) + mean - 1e-5f * mag - 0.02f;             // slack: the float sums behind kmean and the dot product
+        // (a query with a NaN in it has a NaN output row whatever its tiles do: it must not take the lo-half decision away from
+        // the fifteen queries that share its sub-tile, so it drops out of the minimum)
+        const float kbq0 = fmaxf(fmaxf(budget * rqno - knm, (jbo - (float)PM) * rqno), 0.f);
+        // DPP row j holds the 16 queries of sub-tile j: its minimum, read out of the row's first lane into a scalar register
+        const float kmin = row16_min(qno != qno ? INFINITY : kbq0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float dx = qsv[j].x * ks.x, dy = qsv[j].y * ks.y, dz = qsv[j].z * ks.z, dw = qsv[j].w * ks.w;
-            const float mean = ((dx + dy) + (dz + dw)) * invL, mag = ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw))) * invL;
-            jb[j] = log2f((float)L) + mean - 1e-5f * mag - 0.02f;       // slack: the float sums behind kmean and the dot product
-            // (a query with a NaN in it has a NaN output row whatever its tiles do: it must not take the lo-half decision away from
-            // the fifteen queries that share its sub-tile, so it drops out of the minimum)
-            const float kbq0 = fmaxf(fmaxf(budget * rqn[j] - knm, (jb[j] - (float)PM) * rqn[j]), 0.f);
-            kbj[j] = row16_min(qn[j] != qn[j] ? INFINITY : kbq0);
-        }
+        for (int j = 0; j < 4; ++j) kbj[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kmin), 16 * j));
         // A "quiet" wave (wave-uniform, decided once): nothing the general loop's bookkeeping guards against can happen in any chunk.
         //  (a) every tile of the (b, h) is cleared: knm bounds every tile norm from above and the kbj in hand only ever grow, so each
         //      chunk's masks would come out all ones and each chunk would run the hi-only loop;
@@ -652,9 +670,9 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         //      accumulators cannot overflow on f16-range products either.  No overflow: no redo, and the offsets m never move.
         // Both compares are false for a NaN, and an inf or NaN among the tile norms is flagged by wave 0: such waves stay general.
         if (lean != 0) {
-            bool ok = shn.y == 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ok = ok && (knm < kbj[j]) && (qn[j] * knm - mq[j] <= 15.f);
+            // (per query: the lane's own row minimum and the offset of its own query, mq[lg]; all 64 lanes = all four sub-tiles)
+            const float mqo = lg == 0 ? mq[0] : (lg == 1 ? mq[1] : (lg == 2 ? mq[2] : mq[3]));
+            const bool ok = shn.y == 0u && (knm < kmin) && (qno * knm - mqo <= 15.f);
             quiet = __all(ok);
         }
     }
@@ -668,10 +686,23 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
             if (c + 1 < nchunks) load_chunk(c + 1, false);
             const int npairs = min(KC4, L - c * KC4) >> 5;
             attn_tiles<KC4, 0>(sm, buf, npairs, kbase0 + buf * kbuf, kstep, lg, li, qfrag, acc, none, none);
+            // (staging the next chunk half-way through this one's tiles instead of at the seam -- safe, it goes to the buffer the previous
+            // barrier released -- was measured and changes nothing: DESIGN.md section 4)
             if (c + 1 < nchunks) store_chunk(buf ^ 1, c + 1);
             __syncthreads();
         }
-    } else
+    } else {
+    // The general loop's refresh and threshold code wants the slope and the row-sum bound of query li of each sub-tile j, on all four
+    // lanes (li, 0..3): lane 16 j + li has them.  Only waves that come here pay for the hand-over.
+    float rqn[4] = {0.f, 0.f, 0.f, 0.f};
+    float jb[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (PM >= 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            rqn[j] = __shfl(rqno, 16 * j + li);
+            jb[j] = __shfl(jbo, 16 * j + li);
+        }
+    }
     for (int c = 0; c < nchunks; ++c) {
         const int buf = c & 1;
         if (c + 1 < nchunks) load_chunk(c + 1, true);
@@ -806,31 +837,39 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
         if (c + 1 < nchunks) store_chunk(buf ^ 1, c + 1);
         __syncthreads();
     }
+    }
 
     // ---- epilogue: D[query][col], col on the lane (l&15): out_d = D[d] + D[4+d]/2^11 + D[8+d]/2^22, row sum = D[12]
-    // Lanes li < 4 of each 16-lane row store; their operands sit in the same row at lanes li + 4, li + 8 and 12: DPP row moves, not
-    // the LDS permute path.  The store address is a wave-uniform row base plus one 32-bit lane offset for all sixteen stores.
-    // Byte offsets in 32 bits: a workgroup's 256 output rows span 256 * H * 16 bytes.
+    // All 64 lanes divide and store: lane li = 4 r + d of row lg produces out[query 16 j + 4 lg + r][dim d].  Its four operands are
+    // columns d, d + 4, d + 8 and 12 of accumulator register r, in the same 16-lane row: DPP row moves (not the LDS permute path), each
+    // written under the bank mask of the four lanes 4 r .. 4 r + 3, so the four registers merge into one without selects.  One IEEE
+    // divide and one store per sub-tile; a row's four floats sit on adjacent lanes.  The store address is a wave-uniform row base plus
+    // one 32-bit lane offset.  Byte offsets in 32 bits: a workgroup's 256 output rows span 256 * H * 16 bytes.
     const unsigned orow = (unsigned)(H * 16);
-    const unsigned ovo = (unsigned)(4 * lg) * orow + (unsigned)(li * 4);
+    const unsigned ovo = (unsigned)(4 * lg + (li >> 2)) * orow + (unsigned)((li & 3) * 4);
     char* const ob = reinterpret_cast<char*>(out + ((int64_t)b * L + q0) * (H * 4) + h * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (q0 + 16 * j >= L) break;                                      // (L % 16 == 0: the sub-tile's 16 queries leave together)
-        float a1[4], a2[4], l[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {                                       // (every lane takes part in the moves: only then the store lanes split off)
-            a1[r] = dpp_mov<0x104>(acc[j][r]);                              // row_shl:4  lane i <- lane i + 4
-            a2[r] = dpp_mov<0x108>(acc[j][r]);                              // row_shl:8
-            l[r] = dpp_mov<0x10C>(dpp_mov<0x00>(acc[j][r]));                // quad broadcast of lane 12 to 12..15, then row_shl:12
-        }
-        if (li < 4) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float o = (acc[j][r] + a1[r] * 0.00048828125f + a2[r] * 2.384185791015625e-07f) / l[r];
-                *reinterpret_cast<float*>(ob + (ovo + (unsigned)(16 * j + r) * orow)) = o;
-            }
-        }
+        // row_shl:n = 0x100 + n (lane i <- lane i + n), row_shr:n = 0x110 + n (lane i <- lane i - n), row_newbcast:12 = 0x15C
+        float a = acc[j][0];                                                // column d of register r: lanes 4 r + d <- lanes d
+        a = dpp_merge<0x114, 0x2>(a, acc[j][1]);
+        a = dpp_merge<0x118, 0x4>(a, acc[j][2]);
+        a = dpp_merge<0x11C, 0x8>(a, acc[j][3]);
+        float a1 = acc[j][1];                                               // column d + 4
+        a1 = dpp_merge<0x104, 0x1>(a1, acc[j][0]);
+        a1 = dpp_merge<0x114, 0x4>(a1, acc[j][2]);
+        a1 = dpp_merge<0x118, 0x8>(a1, acc[j][3]);
+        float a2 = acc[j][2];                                               // column d + 8
+        a2 = dpp_merge<0x108, 0x1>(a2, acc[j][0]);
+        a2 = dpp_merge<0x104, 0x2>(a2, acc[j][1]);
+        a2 = dpp_merge<0x114, 0x8>(a2, acc[j][3]);
+        float l = dpp_merge<0x15C, 0xf>(0.f, acc[j][0]);                    // column 12: the row sum
+        l = dpp_merge<0x15C, 0x2>(l, acc[j][1]);
+        l = dpp_merge<0x15C, 0x4>(l, acc[j][2]);
+        l = dpp_merge<0x15C, 0x8>(l, acc[j][3]);
+        const float o = (a + a1 * 0.00048828125f + a2 * 2.384185791015625e-07f) / l;
+        *reinterpret_cast<float*>(ob + (ovo + (unsigned)(16 * j) * orow)) = o;
     }
     if (lse != nullptr) {                                                 // training forward only: a pass of its own keeps the sampler's straight
         char* const lb = reinterpret_cast<char*>(lse + (int64_t)h * M + (int64_t)b * L + q0);
