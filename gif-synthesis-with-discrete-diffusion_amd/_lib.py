@@ -48,8 +48,8 @@ class StepDesc(C.Structure):
         ("B", _i), ("L", _i), ("K", _i), ("T", _i), ("guidance", C.c_float),
         ("sched", _p * 8), ("t_dev", _p), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
         ("post_dbg", _p), ("x0_dbg", _p), ("occupancy", _i),
-        # (post_skip sits in the struct's tail padding: gsdd_abi_sizeof cannot see it missing -- keep it in step with gsdd.h by hand)
-        ("post_skip", _i), ("trunc_rate", C.c_float),
+        # (known / x_known / known_mode sit before trunc_rate, as in gsdd.h: trunc_rate stays the last field)
+        ("post_skip", _i), ("known", _p), ("x_known", _p), ("known_mode", _i), ("trunc_rate", C.c_float),
     ]
 
 

@@ -180,4 +180,47 @@ __device__ __forceinline__ int wave_argmax(float v, int idx) {
     return idx;
 }
 
+// The draw of a position whose clean token is given (gsdd_step_desc.known): Gumbel arg-max over the K + 1 classes of a forward
+// marginal q(x_s | x_0 = tok), which has three values -- `hit` for class tok, `miss` for every other code, `mval` for [MASK] (q_pred of
+// a log-one-hot row, as in d3pm_q_sample_kernel).  No row lives in registers: the wave walks the register slots of the posterior draw
+// with that draw's Philox counters (quad k0 / 4 of global row `grow`, [MASK] = word 0 of quad K / 4 on lane (K / 4) % 64), so a
+// position consumes the same uniforms whichever path it takes.  tok is wave-uniform: the hit is a scalar branch on j plus one lane
+// compare.  Classes are visited in increasing k per lane and wave_argmax keeps the first index: torch.argmax's choice.
+template <int J, bool FULL>
+__device__ __forceinline__ int known_row_draw(int tok, float hit, float miss, float mval, int lane, int K, uint64_t seed,
+                                              uint32_t stream_id, uint64_t grow) {
+    const uint32_t kp4 = (uint32_t)((K + 1 + 3) / 4);
+    const int xj = tok >> 8, xl = (tok >> 2) & 63, xe = tok & 3;
+    const bool mine = (lane == xl);
+    float best = -INFINITY;
+    int best_k = 0;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int k0 = 4 * lane + 256 * j;
+        if (FULL || k0 < K) {
+            const float4 u4 = philox_uniform4(seed, stream_id, grow, kp4, (uint32_t)(k0 >> 2));
+            const float u[4] = {u4.x, u4.y, u4.z, u4.w};
+            if (j == xj) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = gumbel(u[e]) + ((mine && e == xe) ? hit : miss);
+                    if (v > best) { best = v; best_k = k0 + e; }
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = gumbel(u[e]) + miss;
+                    if (v > best) { best = v; best_k = k0 + e; }
+                }
+            }
+        }
+    }
+    if (lane == ((K >> 2) & 63)) {
+        const float4 u4 = philox_uniform4(seed, stream_id, grow, kp4, (uint32_t)(K >> 2));
+        const float v = gumbel(u4.x) + mval;
+        if (v > best) { best = v; best_k = K; }
+    }
+    return wave_argmax(best, best_k);
+}
+
 }  // namespace gsdd

@@ -24,7 +24,13 @@ namespace gsdd {
 // TRUNC: top-r truncation of the guided row (truncate_row, d3pm_rows.hpp) between the guidance mix and the posterior.  It is a
 // kernel family of its own (d3pm_step_trunc_kernel): the plain kernels compile the body with TRUNC = false, instruction for
 // instruction what they were before the option existed.
-template <int J, bool FULL, bool DBG, bool TRUNC>
+// KNOWN: positions whose clean token is given (gsdd_step_desc.known / x_known / known_mode).  One wave owns one position, so
+// known[pos] is wave-uniform: it is read through the scalar pos and branched on before the first logits load.  A known position reads
+// neither logit row nor x_t and never touches x0 / xu: it keeps the three values of q(x_{t'-1} | x_0 = x_known) and walks the draw's
+// register slots with the draw's Philox counters (known_row_draw, d3pm_rows.hpp); hold mode is the token store alone.  Every other
+// position falls through to the code below unchanged.  Kernel families of their own again (d3pm_step_known_kernel,
+// d3pm_step_known_trunc_kernel): with KNOWN = false nothing of this is compiled.
+template <int J, bool FULL, bool DBG, bool TRUNC, bool KNOWN = false>
 __device__ __forceinline__ void d3pm_step_body(const gsdd_step_desc& d, const SchedPtrs& sp) {
     const int lane = threadIdx.x & 63;
     const int64_t pos = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -32,6 +38,23 @@ __device__ __forceinline__ void d3pm_step_body(const gsdd_step_desc& d, const Sc
     const int b = (int)(pos / d.L), l = (int)(pos % d.L);
     const int K = d.K;
     const float NEG = -INFINITY;
+
+    if (KNOWN) {
+        if (__builtin_amdgcn_readfirstlane((int)d.known[pos]) != 0) {       // scalar branch: the whole wave takes it or none of it
+            const int xk = __builtin_amdgcn_readfirstlane((int)d.x_known[pos]);
+            int win = xk;
+            if (d.known_mode == 0) {    // renoise: x_{t'-1} ~ q(. | x_0 = x_known), the level t' - 1 wrapped modulo T + 1 (index T: x_known itself)
+                const int64_t t_in = d.t_dev[b];
+                const int64_t t = t_in > d.post_skip ? t_in - d.post_skip : t_in;
+                const int64_t tp = (t - 1 + (d.T + 1)) % (d.T + 1);
+                const float pca = sp.p[4][tp], pcb = sp.p[5][tp], pcc = sp.p[6][tp], p1mcc = sp.p[7][tp];
+                win = known_row_draw<J, FULL>(xk, lae(0.f + pca, pcb), lae(LOG_ZERO + pca, pcb), lae(LOG_ZERO + p1mcc, pcc), lane, K,
+                                              d.seed, (uint32_t)d.stream_dev[0], (uint64_t)(d.row0 + pos));
+            }
+            if (lane == 0) d.tok_out[pos] = win;
+            return;
+        }
+    }
 
     float x0[J][4];
     {   // ---- predict_start on the conditional logits
@@ -131,21 +154,33 @@ __device__ __forceinline__ void d3pm_step_body(const gsdd_step_desc& d, const Sc
         const float v = gumbel(u) + o;
         if (v > best) { best = v; best_k = k; }
     };
+    // one register slot's four classes
+#define GSDD_STEP_DRAW_SLOT(j)                                                                                       \
+    do {                                                                                                             \
+        const int k0 = 4 * lane + 256 * (j);                                                                         \
+        if (FULL || k0 < K) {                                                                                        \
+            const float4 u4 = philox_uniform4(d.seed, stream_id, grow, kp4, (uint32_t)(k0 >> 2));                    \
+            const float u[4] = {u4.x, u4.y, u4.z, u4.w};                                                             \
+            if ((j) == xj) {                                                                                         \
+                _Pragma("unroll")                                                                                    \
+                for (int e = 0; e < 4; ++e) draw((j), e, (mine && e == xe) ? q1_hit : q1_miss, u[e]);                \
+            } else {                                                                                                 \
+                _Pragma("unroll")                                                                                    \
+                for (int e = 0; e < 4; ++e) draw((j), e, q1_miss, u[e]);                                             \
+            }                                                                                                        \
+        }                                                                                                            \
+    } while (0)
+    // KNOWN at J = 32: two loops of 16 slots.  As one loop of 32 the body passes the size up to which the compiler unrolls a loop in
+    // full; it then unrolls by 16 and indexes x0 with the run-time j of the loop that is left, and x0 lives in scratch memory (528
+    // bytes per lane).  The families with known positions have no scratch; every other family keeps its single loop.
+    constexpr int JH = (KNOWN && J > 16) ? J / 2 : J;
 #pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int k0 = 4 * lane + 256 * j;
-        if (FULL || k0 < K) {
-            const float4 u4 = philox_uniform4(d.seed, stream_id, grow, kp4, (uint32_t)(k0 >> 2));
-            const float u[4] = {u4.x, u4.y, u4.z, u4.w};
-            if (j == xj) {
+    for (int j = 0; j < JH; ++j) GSDD_STEP_DRAW_SLOT(j);
+    if constexpr (JH < J) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) draw(j, e, (mine && e == xe) ? q1_hit : q1_miss, u[e]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) draw(j, e, q1_miss, u[e]);
-            }
-        }
+        for (int j = JH; j < J; ++j) GSDD_STEP_DRAW_SLOT(j);
     }
+#undef GSDD_STEP_DRAW_SLOT
     if (lane == ((K >> 2) & 63)) {  // the [MASK] class k = K (K % 4 == 0 -> word 0 of quad K/4)
         const float4 u4 = philox_uniform4(d.seed, stream_id, grow, kp4, (uint32_t)(K >> 2));
         const float qn = LOG_ZERO - S;
@@ -168,6 +203,18 @@ __global__ __launch_bounds__(256, OCC) void d3pm_step_kernel(gsdd_step_desc d, S
 template <int J, bool FULL, bool DBG>
 __global__ __launch_bounds__(256, 2) void d3pm_step_trunc_kernel(gsdd_step_desc d, SchedPtrs sp) {
     d3pm_step_body<J, FULL, DBG, true>(d, sp);
+}
+
+// the families with known positions: no test hooks; the register budget that leaves the unknown positions' rows in registers
+// (two waves per SIMD at J = 16 as in the production plain kernel, one at J = 32: 512 registers, the spill space is AGPRs)
+template <int J, bool FULL>
+__global__ __launch_bounds__(256, J >= 32 ? 1 : (J >= 16 ? 2 : 3)) void d3pm_step_known_kernel(gsdd_step_desc d, SchedPtrs sp) {
+    d3pm_step_body<J, FULL, false, false, true>(d, sp);
+}
+
+template <int J, bool FULL>
+__global__ __launch_bounds__(256, J >= 32 ? 1 : 2) void d3pm_step_known_trunc_kernel(gsdd_step_desc d, SchedPtrs sp) {
+    d3pm_step_body<J, FULL, false, true, true>(d, sp);
 }
 
 // q_sample (:361-366): x_t ~ Gumbel-argmax(q_pred(onehot(x0), t))
@@ -664,6 +711,26 @@ extern "C" int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream) {
     GSDD_CHECK_ARG(d->occupancy == 0 || d->occupancy == 2 || d->occupancy == 3, "occupancy: 0 (auto), 2 or 3 waves per SIMD");
     GSDD_CHECK_ARG(d->post_skip >= 0, "post_skip must be >= 0");
     GSDD_CHECK_ARG(d->trunc_rate == 0.f || (d->trunc_rate > 0.f && d->trunc_rate < 1.f), "trunc_rate must be 0 (off) or in (0, 1)");
+    if (d->known != nullptr) {                     // positions with a given clean token: the d3pm_step_known*_kernel families (FULL at K = 4096 only)
+        GSDD_CHECK_ARG(d->x_known != nullptr, "known needs x_known");
+        GSDD_CHECK_ARG(d->known_mode == 0 || d->known_mode == 1, "known_mode: 0 (renoise) or 1 (hold)");
+        GSDD_CHECK_ARG(!dbg, "known cannot be combined with post_dbg / x0_dbg");
+#define GSDD_STEP_KNOWN_LAUNCH(JJ, FF)                                                                               \
+    do {                                                                                                             \
+        if (d->trunc_rate == 0.f) hipLaunchKernelGGL((d3pm_step_known_kernel<JJ, FF>), grid, block, 0, st, *d, sp);  \
+        else hipLaunchKernelGGL((d3pm_step_known_trunc_kernel<JJ, FF>), grid, block, 0, st, *d, sp);                 \
+    } while (0)
+        if (d->K == 4096) GSDD_STEP_KNOWN_LAUNCH(16, true);
+        else if (J <= 1) GSDD_STEP_KNOWN_LAUNCH(1, false);
+        else if (J <= 2) GSDD_STEP_KNOWN_LAUNCH(2, false);
+        else if (J <= 4) GSDD_STEP_KNOWN_LAUNCH(4, false);
+        else if (J <= 8) GSDD_STEP_KNOWN_LAUNCH(8, false);
+        else if (J <= 16) GSDD_STEP_KNOWN_LAUNCH(16, false);
+        else GSDD_STEP_KNOWN_LAUNCH(32, false);
+#undef GSDD_STEP_KNOWN_LAUNCH
+        GSDD_CHECK_LAUNCH();
+        return GSDD_OK;
+    }
     if (d->trunc_rate != 0.f) {                    // top-r truncated sampling: the d3pm_step_trunc_kernel family (FULL at K = 4096 only)
 #define GSDD_STEP_TRUNC_LAUNCH(JJ, FF)                                                                               \
     do {                                                                                                             \

@@ -504,6 +504,68 @@ def _trunc_kwargs(rate):
     return {} if rate is None else {"trunc_rate": float(rate)}
 
 
+KNOWN_MODES = {"renoise": 0, "hold": 1}      # gsdd_step_desc.known_mode
+
+
+def frame_mask(latent_shape, frames):
+    """-> (L,) bool, true at the positions of the latent frames listed.  latent_shape is (t, h, w), flattened t-major as
+    quant.view(B, -1) flattens the encoder's codes; frames is an int k (the first k frames: clip continuation) or an iterable of frame
+    indices (first + last frame: interpolation).  Negative indices count from the end."""
+    shape = tuple(latent_shape)
+    is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if len(shape) != 3 or not all(is_int(v) and v >= 1 for v in shape):
+        raise GsddError(f"frame_mask: latent_shape must be three positive ints (t, h, w), got {latent_shape!r}")
+    nt = int(shape[0])
+    if is_int(frames):
+        if not 0 <= frames <= nt:
+            raise GsddError(f"frame_mask: the first {frames} frames of a latent with {nt}")
+        idx = list(range(int(frames)))
+    else:
+        try:
+            idx = list(frames)
+        except TypeError:
+            raise GsddError(f"frame_mask: frames must be an int or an iterable of frame indices, got {frames!r}") from None
+        if not all(is_int(i) and -nt <= i < nt for i in idx):
+            raise GsddError(f"frame_mask: frame indices {idx!r} outside a latent with {nt} frames")
+    m = torch.zeros(shape, dtype=torch.bool)
+    m[[int(i) for i in idx]] = True
+    return m.reshape(-1)
+
+
+def check_known(known_mask, content_token, known_mode, *, B, L, K, start_step=0, prior_rule=0):
+    """Validates the arguments of known-token conditioned sampling.  -> None (no mask: the plain call) or (mask (B, L) bool,
+    tokens (B, L) int64, gsdd_step_desc.known_mode), on the devices the arguments came on.  known_mask is (B, L) or (L,) (the same
+    positions in every clip, what frame_mask returns); the tokens at its positions are content_token's and must be codes in [0, K)
+    -- [MASK] is no clean token.  One host check per call, as content_token is checked for filter_ratio > 0."""
+    if known_mask is None:
+        return None
+    if not isinstance(known_mode, str) or known_mode not in KNOWN_MODES:
+        raise GsddError(f"known_mode must be one of {sorted(KNOWN_MODES)}, got {known_mode!r}")
+    if content_token is None:
+        raise GsddError("known_mask needs content_token (the tokens at the known positions)")
+    if start_step != 0:
+        raise GsddError(f"known_mask samples from all-[MASK] only: int(num_timesteps * filter_ratio) = {start_step}, must be 0 "
+                        "(a partially noised start re-noises every position, the known ones included)")
+    if prior_rule != 0:
+        raise GsddError("known_mask cannot be combined with prior_rule > 0: the purity prior's reveal schedule counts [MASK] positions")
+    mask, tok = torch.as_tensor(known_mask), torch.as_tensor(content_token)
+    if mask.dtype != torch.bool:
+        raise GsddError(f"known_mask must be a bool tensor, got {mask.dtype}")
+    if mask.dim() == 1 and mask.shape[0] == L:
+        mask = mask.unsqueeze(0).expand(B, L)
+    if tuple(mask.shape) != (B, L):
+        raise GsddError(f"known_mask must have shape {(B, L)} or {(L,)}, got {tuple(mask.shape)}")
+    if tok.numel() != B * L or tok.is_floating_point() or tok.dtype == torch.bool:
+        raise GsddError(f"content_token must hold {B} x {L} integer tokens, got {tuple(tok.shape)} {tok.dtype}")
+    tok = tok.long().reshape(B, L)
+    mask = mask.to(tok.device)
+    at = tok[mask]
+    if at.numel() and (int(at.min()) < 0 or int(at.max()) >= K):
+        raise GsddError(f"content_token at known positions must lie in [0, {K}): found {int(at.min())} .. {int(at.max())} "
+                        f"([MASK] = {K} is not a clean token)")
+    return mask.contiguous(), tok.contiguous(), KNOWN_MODES[known_mode]
+
+
 SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct",
                "log_1_min_cumprod_ct")
 
@@ -603,11 +665,15 @@ class DiffusionTransformer(nn.Module):
         final = bool(calls) and calls[-1][0] == 0
         return PurityPlan(tuple(calls[:-1] if final else calls), final, int(self.prior_rule), float(self.prior_weight))
 
+    @staticmethod
+    def _batch_of(condition_token, kwargs):
+        return len(condition_token) if condition_token is not None else kwargs["batch_size"]
+
     # ------------------------------------------------------------------ sampling (diffusion_transformer.py:568-713)
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
-               print_log=True, use_graph=True, trace=None, **kwargs):
+               print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", **kwargs):
         """diffusion_transformer.py:568-644.  The loop itself is `_sample_once`, driven by `sample_plan`; `_sample_checked` repeats it
         on the bf16x3 layer kernel if an activation left the f16 operand range.
         filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
@@ -615,11 +681,23 @@ class DiffusionTransformer(nn.Module):
         parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step).
         prior_rule 1 / 2 (attributes, as in the reference): the purity-prior chain of `purity_plan` -- every call at t > 0 runs the
         denoiser, draws a candidate per position and reveals the n most trusted [MASK] positions (two noise streams per call);
-        the step at t = 0 is the ordinary one."""
+        the step at t = 0 is the ordinary one.
+        known_mask (bool, (B, L) or (L,)): the positions whose clean tokens are given, in content_token (frame prediction,
+        interpolation, inpainting; `frame_mask`).  From all-[MASK], prior_rule 0.  Those positions skip the learned reverse step:
+        known_mode "renoise" draws them from the forward marginal q(x_{t-1} | x_0) at every step (RePaint's construction for the
+        absorbing chain; x_0 itself at t = 0), "hold" writes x_0 at every step.  Every other position is sampled as without the mask
+        and sees the known ones through self-attention.  None launches exactly the plain chain."""
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
         if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
             raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
+        known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
+                                                            L=self.shape, K=self.num_classes - 1, start_step=start_step,
+                                                            prior_rule=self.prior_rule)
+        if known is not None:
+            return self._sample_checked(sample_plan(self.num_timesteps), condition_token, condition_embed, cf_condition_embed,
+                                        return_logits=return_logits, use_graph=use_graph, trace=trace, truncation_rate=trunc,
+                                        known=known, **kwargs)
         if self.prior_rule != 0:        # purity-prior inference (:304-346): reveal n_sample[t] trusted positions per timestep
             return self._sample_checked(self._purity_plan(start_step), condition_token, condition_embed, cf_condition_embed,
                                         return_logits=return_logits, use_graph=use_graph, trace=trace, truncation_rate=trunc, **kwargs)
@@ -632,13 +710,18 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None, print_log=True,
-                    skip_step=1, *, cf_condition_embed=None, use_graph=True, trace=None, **kwargs):
+                    skip_step=1, *, cf_condition_embed=None, use_graph=True, trace=None, known_mask=None, known_mode="renoise",
+                    **kwargs):
         """VQ-Diffusion's skip-step sampler (diffusion_transformer.py:648-713): the denoiser runs at t = T-1, T-1-(1+s), ..., then 0
         (`sample_plan`), and each step's posterior jumps to t - s (for t > s) across the skipped levels.  From all-[MASK] only, as the
         reference asserts.  The reference passes cf_predict_start three of its four arguments; the
-        unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit."""
+        unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit.
+        known_mask / known_mode: as in sample(); a known position is re-noised to the level the step's posterior jumps to."""
         T = self.num_timesteps
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
+        known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
+                                                            L=self.shape, K=self.num_classes - 1, start_step=int(T * filter_ratio))
+        known_kw = {} if known is None else {"known": known}
         if int(T * filter_ratio) != 0:
             raise GsddError(f"sample_fast starts from all-[MASK] only: int(num_timesteps * filter_ratio) = {int(T * filter_ratio)}, "
                             "must be 0 (diffusion_transformer.py:686)")
@@ -649,7 +732,7 @@ class DiffusionTransformer(nn.Module):
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
         return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
-                                    use_graph=use_graph, trace=trace, truncation_rate=trunc, **kwargs)
+                                    use_graph=use_graph, trace=trace, truncation_rate=trunc, **known_kw, **kwargs)
 
     def _sample_checked(self, plan, *args, trace=None, **kw):
         """`_sample_once`, then one read of the layer kernel's range flags after the loop (outside graph capture): if an activation left
@@ -667,7 +750,7 @@ class DiffusionTransformer(nn.Module):
         return out
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
-                     use_graph=True, trace=None, truncation_rate=None, **kwargs):
+                     use_graph=True, trace=None, truncation_rate=None, known=None, **kwargs):
         dev = self.device
         trunc_kw = _trunc_kwargs(truncation_rate)   # a launch constant of both step kernels: the captured graph records it
         if dev.type != "cuda":
@@ -735,10 +818,16 @@ class DiffusionTransformer(nn.Module):
                                       torch.tensor([self.noise_stream], dtype=torch.int64, device=dev), K=K, T=T,
                                       seed=self.noise_seed, row0=row0, stream=st)
 
-                def plain_step(post_skip, tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st):
+                # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they
+                # are constants of the chain, so the captured graph is still one step; nothing at all without a mask
+                known_kw = {} if known is None else {"known": known[0][sl].to(dev).to(torch.uint8).contiguous(),
+                                                     "x_known": known[1][sl].to(dev).contiguous(), "known_mode": known[2]}
+
+                def plain_step(post_skip, tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st, known_kw=known_kw):
                     logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
                     ops.d3pm_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, tok, tok, sched, t2, sid, K=K, T=T,
-                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st, **trunc_kw)
+                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st,
+                                  **trunc_kw, **known_kw)
 
                 if purity:
                     # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
@@ -816,10 +905,14 @@ class DiffusionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ single-step pieces (parity tests, training glue)
     @torch.no_grad()
-    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0, truncation_rate=None):
+    def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0, truncation_rate=None,
+                        known=None):
         """One reverse step on tokens (p_sample, diffusion_transformer.py:304-352, prior_rule 0); post_skip > 0: the posterior at
-        t - post_skip for t > post_skip (a sample_fast step, :700-704); truncation_rate: top-r truncation of the guided row."""
+        t - post_skip for t > post_skip (a sample_fast step, :700-704); truncation_rate: top-r truncation of the guided row;
+        known: what `check_known` returns (mask, clean tokens, mode) -- those positions skip the learned step as in sample()."""
         trunc_kw = _trunc_kwargs(check_truncation_rate(truncation_rate))
+        known_kw = {} if known is None else {"known": known[0].to(tok.device).to(torch.uint8).contiguous(),
+                                             "x_known": known[1].to(tok.device).contiguous(), "known_mode": known[2]}
         dev = tok.device
         B, L = tok.shape
         K, T = self.num_classes - 1, self.num_timesteps
@@ -836,7 +929,7 @@ class DiffusionTransformer(nn.Module):
         M = B * L
         ops.d3pm_step(logits[:M], logits[M:] if guided else None, tok, out, self._sched(), t2, sid, K=K, T=T,
                       guidance=float(self.guidance_scale), seed=self.noise_seed, row0=self.row_offset * L,
-                      post_dbg=post_dbg, x0_dbg=x0_dbg, post_skip=post_skip, **trunc_kw)
+                      post_dbg=post_dbg, x0_dbg=x0_dbg, post_skip=post_skip, **trunc_kw, **known_kw)
         return out
 
     # ------------------------------------------------------------------ training objective (forward value)
@@ -978,11 +1071,14 @@ class DiscreteDiffusion(nn.Module):
     prior_ps before sampling (purity-prior inference; prior_ps also reloads the reference's n_sample list);
     sample_prior_scale_schedule=True rescales that list from 1024 tokens to the model's content_seq_len (scaled_n_sample).
     sample_truncation_rate: when not None, sets the diffusion model's truncation_rate before sampling (top-r truncated sampling,
-    0 < r < 1; VQ-Diffusion's inference uses 0.86)."""
+    0 < r < 1; VQ-Diffusion's inference uses 0.86).
+    sample_condition_frames: null, an int k in [1, t_latent) or a list of latent frame indices: forward(do_inference=True) then keeps
+    those latent frames of the input clip (its own codes) and samples the rest (frame prediction / interpolation; `frame_mask`);
+    sample_known_mode "renoise" / "hold" is the sampler's known_mode.  Not with sample_prior_rule > 0."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
-                 **kwargs):
+                 sample_condition_frames=None, sample_known_mode="renoise", **kwargs):
         super().__init__()
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -1013,6 +1109,39 @@ class DiscreteDiffusion(nn.Module):
         self.sample_prior_ps = None if sample_prior_ps is None else int(sample_prior_ps)
         self.sample_prior_scale_schedule = sample_prior_scale_schedule
         self.sample_truncation_rate = check_truncation_rate(sample_truncation_rate, "sample_truncation_rate")
+        if sample_condition_frames is not None:
+            frames = sample_condition_frames
+            if is_int(frames):
+                if frames < 1:
+                    raise GsddError(f"sample_condition_frames must be null, an int >= 1 or a list of frame indices, got {frames!r}")
+                frames = int(frames)
+            else:
+                try:
+                    frames = [v for v in frames] if not isinstance(frames, (str, bytes)) else None
+                except TypeError:
+                    frames = None
+                if not frames or not all(is_int(v) for v in frames):
+                    raise GsddError("sample_condition_frames must be null, an int >= 1 or a non-empty list of frame indices, "
+                                    f"got {sample_condition_frames!r}")
+                frames = [int(v) for v in frames]
+            if sample_prior_rule:
+                raise GsddError("sample_condition_frames and sample_prior_rule > 0 cannot be combined: the purity prior's reveal "
+                                "schedule counts [MASK] positions")
+            sample_condition_frames = frames
+        if not isinstance(sample_known_mode, str) or sample_known_mode not in KNOWN_MODES:
+            raise GsddError(f"sample_known_mode must be one of {sorted(KNOWN_MODES)}, got {sample_known_mode!r}")
+        self.sample_condition_frames = sample_condition_frames
+        self.sample_known_mode = sample_known_mode
+
+    def condition_frame_mask(self, latent_shape):
+        """-> None or the (L,) bool mask of sample_condition_frames on this latent grid (validated here, at sampling time)."""
+        frames = self.sample_condition_frames
+        if frames is None:
+            return None
+        if isinstance(frames, int) and not 1 <= frames < latent_shape[0]:
+            raise GsddError(f"sample_condition_frames = {frames} must lie in [1, {latent_shape[0]}): the latent has {latent_shape[0]} "
+                            "frames and at least one must be left to sample")
+        return frame_mask(latent_shape, frames)
 
     def _text(self, texts, dev):
         emb = self.textencoder(texts)
@@ -1061,8 +1190,10 @@ class DiscreteDiffusion(nn.Module):
         test = deferred_decode(quant)
         with torch.no_grad():
             if do_inference:                # (the sampler draws from the noise stream: always at this point of the call)
-                inference_out = self.sample_videos(batch["text"], autoencoder, latent_shape=tuple(quant.shape[1:]),
-                                                   text_emb=text_emb)
+                shape = tuple(quant.shape[1:])
+                mask = self.condition_frame_mask(shape)     # the conditioned latent frames keep the input clip's own codes
+                known_kw = {} if mask is None else {"known_tokens": quant_flat, "known_mask": mask}
+                inference_out = self.sample_videos(batch["text"], autoencoder, latent_shape=shape, text_emb=text_emb, **known_kw)
         if do_inference:
             out = LazyOutputs(pred_data=inference_out, pred_single_step=single_step_out, gt_data=x, losses=diffusion_out["loss"], test=test)
         else:
@@ -1073,8 +1204,10 @@ class DiscreteDiffusion(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None):
-        """The inference branch of forward (discrete_diffusion.py:44-62): text -> tokens -> decoded clips."""
+    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None):
+        """The inference branch of forward (discrete_diffusion.py:44-62): text -> tokens -> decoded clips.
+        known_tokens (B, L) / known_mask ((B, L) or (L,) bool): clean tokens to keep at the mask's positions (the sampler's
+        content_token / known_mask, with sample_known_mode); without a mask the call is the plain one."""
         dev = autoencoder.device
         B = len(texts)
         if text_emb is None:
@@ -1095,11 +1228,15 @@ class DiscreteDiffusion(nn.Module):
             if ref is None:
                 raise GsddError(f"sample_prior_scale_schedule: the reference has no n_sample list for num_timesteps = {dm.num_timesteps}")
             dm.n_sample = scaled_n_sample(ref, dm.shape)
-        if self.sample_skip_step is None:
-            out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=None, filter_ratio=0)
+        if known_mask is None:
+            content, known_kw = None, {}
         else:
-            out = self.diffusion_model.sample_fast(texts, None, text_emb, content_token=None, filter_ratio=0,
-                                                   skip_step=self.sample_skip_step, cf_condition_embed=cf_emb)
+            content, known_kw = known_tokens, {"known_mask": known_mask, "known_mode": self.sample_known_mode}
+        if self.sample_skip_step is None:
+            out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=content, filter_ratio=0, **known_kw)
+        else:
+            out = self.diffusion_model.sample_fast(texts, None, text_emb, content_token=content, filter_ratio=0,
+                                                   skip_step=self.sample_skip_step, cf_condition_embed=cf_emb, **known_kw)
         self.last_content_token = out["content_token"]
         shape = latent_shape if latent_shape is not None else autoencoder.latent_shape
         return autoencoder.decode(out["content_token"].view(B, *shape))

@@ -339,10 +339,20 @@ def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None):
 
 
 def d3pm_step(logits_c, logits_u, tok_in, tok_out, sched, t_dev, stream_dev, *, K, T, guidance, seed, row0=0,
-              post_dbg=None, x0_dbg=None, post_skip=0, trunc_rate=None, stream=None):
-    """trunc_rate: None (off) or 0 < r < 1, top-r truncation of the guided row before the posterior (gsdd_step_desc.trunc_rate)."""
+              post_dbg=None, x0_dbg=None, post_skip=0, trunc_rate=None, known=None, x_known=None, known_mode=0, stream=None):
+    """trunc_rate: None (off) or 0 < r < 1, top-r truncation of the guided row before the posterior (gsdd_step_desc.trunc_rate).
+    known: None (off) or a (B, L) uint8 / bool tensor, non-zero where the clean token x_known (B, L) int64 is given; known_mode 0
+    re-noises x_known to the step's level, 1 holds it (gsdd_step_desc.known / x_known / known_mode)."""
     B, L = tok_in.shape
     d = StepDesc()
+    if known is not None:
+        if x_known is None:
+            raise GsddError("d3pm_step: known needs x_known")
+        if known.dtype not in (torch.uint8, torch.bool) or x_known.dtype != torch.int64:
+            raise GsddError(f"d3pm_step: known must be uint8 / bool and x_known int64, got {known.dtype} / {x_known.dtype}")
+        if tuple(known.shape) != (B, L) or tuple(x_known.shape) != (B, L) or not known.is_contiguous() or not x_known.is_contiguous():
+            raise GsddError(f"d3pm_step: known and x_known must be contiguous {(B, L)} tensors, got {tuple(known.shape)} / {tuple(x_known.shape)}")
+        d.known, d.x_known, d.known_mode = ptr(known), ptr(x_known), int(known_mode)
     d.post_skip = int(post_skip)
     d.trunc_rate = 0.0 if trunc_rate is None else float(trunc_rate)
     d.occupancy = int(os.environ.get("GSDD_STEP_OCC", "0"))

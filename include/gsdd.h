@@ -327,6 +327,16 @@ typedef struct {
     int post_skip;              /* >= 0; the posterior runs at t' = t - post_skip when t > post_skip, else at t' = t (skip-step */
                                 /* sampling, diffusion_transformer.py:700-704); the denoiser's logits are those of step t.     */
                                 /* 0 = the plain reverse step                                                                  */
+    const uint8_t* known;       /* [B*L], NULL = off (exactly the launch without these fields).  A position with known[pos] != 0   */
+                                /* has a given clean token x_known[pos] in [0, K): it reads neither logit row nor tok_in and skips */
+                                /* the learned reverse step (frame prediction / interpolation / inpainting); every other position  */
+                                /* is sampled as without the mask, bit for bit, from the same uniforms.                            */
+    const int64_t* x_known;     /* [B*L]; required when known != NULL, read at known positions only                               */
+    int known_mode;             /* 0 renoise: tok_out = Gumbel arg-max of q(x_{t'-1} | x_0 = x_known) (q_pred at level t' - 1,     */
+                                /*   wrapped modulo T + 1, t' the posterior's timestep) on the position's own uniforms of the step */
+                                /*   -- x_known itself at t' = 0;  1 hold: tok_out = x_known, no uniforms read.                    */
+                                /* post_dbg / x0_dbg cannot be combined with known (the masked kernels carry no hooks).            */
+                                /* (these three sit before trunc_rate, which stays the struct's last field)                       */
     float trunc_rate;           /* 0 = off, or 0 < r < 1: top-r truncated sampling (VQ-Diffusion's predict_start_with_truncation, */
                                 /* "top0.86r").  Of the guided row, class k is kept iff sum_{x_j > x_k} exp(x_j) < r; every other  */
                                 /* class drops to -70, without renormalising, before the posterior.  x0_dbg shows the cut row.    */

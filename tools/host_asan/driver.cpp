@@ -152,6 +152,20 @@ int main() {
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true);
         for (float bad : {1.f, -0.5f, 1.5f}) { d.trunc_rate = bad; EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false); }
         d.trunc_rate = 0.f;
+        d.known = devp<uint8_t>(); d.x_known = devp<int64_t>();                 // known positions: the masked kernel families
+        for (int mode : {0, 1}) { d.known_mode = mode; EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true); }
+        d.trunc_rate = 0.86f;
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true);
+        d.trunc_rate = 0.f;
+        for (int bad : {-1, 2}) { d.known_mode = bad; EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false); }
+        d.known_mode = 0;
+        d.x_known = nullptr;
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
+        d.x_known = devp<int64_t>(); d.post_dbg = devp();                         // the masked families carry no hooks
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
+        d.post_dbg = nullptr; d.known = nullptr; d.known_mode = 5;               // without a mask the other two fields are not looked at
+        EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true);
+        d.x_known = nullptr; d.known_mode = 0;
         EXPECT(gsdd_advance_floor(devp<int64_t>(), B, -4, 0, devp<int64_t>(), 1, st), GSDD_OK, true);
         EXPECT(gsdd_advance_floor(devp<int64_t>(), -1, -4, 0, devp<int64_t>(), 1, st), GSDD_E_ARG, false);
         for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { d.K = k; EXPECT(gsdd_d3pm_step(&d, st), GSDD_OK, true); }
