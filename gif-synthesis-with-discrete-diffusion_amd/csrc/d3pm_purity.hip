@@ -267,49 +267,36 @@ extern "C" int gsdd_d3pm_purity_step(const gsdd_purity_desc* d, void* stream) {
     const int64_t npos = (int64_t)d->B * d->L;
     const dim3 grid((unsigned)((npos + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    const int J = (d->K + 255) / 256;
     const bool dbg = d->recon_dbg != nullptr || d->prob_dbg != nullptr || d->score_dbg != nullptr;
     const bool two_pass = dbg || (d->prior_rule == 2 && d->prior_weight > 0.f);
-    // pass: 0 = the fused score + draw, 1 = scores, 2 = draw
     const bool trunc = d->trunc_rate != 0.f;
+    // pass: 0 = the fused score + draw, 1 = scores, 2 = draw
     auto launch = [&](int mode) {
-        if (trunc && mode != 1) {                    // top-r truncation: the d3pm_purity_trunc_kernel family (the score pass has no use for it)
-#define GSDD_PURITY_TRUNC_LAUNCH(JJ, FF)                                                                                     \
-    do {                                                                                                                     \
-        if (mode == 0) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 0, false>), grid, block, 0, st, *d);            \
-        else if (!dbg) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 2, false>), grid, block, 0, st, *d);            \
-        else hipLaunchKernelGGL((d3pm_purity_trunc_kernel<JJ, FF, 2, true>), grid, block, 0, st, *d);                       \
-    } while (0)
-            if (d->K == 4096) GSDD_PURITY_TRUNC_LAUNCH(16, true);
-            else if (J <= 1) GSDD_PURITY_TRUNC_LAUNCH(1, false);
-            else if (J <= 2) GSDD_PURITY_TRUNC_LAUNCH(2, false);
-            else if (J <= 4) GSDD_PURITY_TRUNC_LAUNCH(4, false);
-            else if (J <= 8) GSDD_PURITY_TRUNC_LAUNCH(8, false);
-            else if (J <= 16) GSDD_PURITY_TRUNC_LAUNCH(16, false);
-            else GSDD_PURITY_TRUNC_LAUNCH(32, false);
-#undef GSDD_PURITY_TRUNC_LAUNCH
-            return;
-        }
-        if (d->K == 4096 && !dbg) {                  // the production shape: every slot holds a class, no hooks, no scratch
+        // top-r truncation: the d3pm_purity_trunc_kernel family (the score pass has no use for it), FULL at K = 4096 only
+        if (trunc && mode != 1 && d->K == 4096) {
+            if (mode == 0) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<16, true, 0, false>), grid, block, 0, st, *d);
+            else if (!dbg) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<16, true, 2, false>), grid, block, 0, st, *d);
+            else hipLaunchKernelGGL((d3pm_purity_trunc_kernel<16, true, 2, true>), grid, block, 0, st, *d);
+        } else if (trunc && mode != 1) {
+            for_class_width(d->K, [&](auto jc) {
+                constexpr int J = decltype(jc)::value;
+                if (mode == 0) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<J, false, 0, false>), grid, block, 0, st, *d);
+                else if (!dbg) hipLaunchKernelGGL((d3pm_purity_trunc_kernel<J, false, 2, false>), grid, block, 0, st, *d);
+                else hipLaunchKernelGGL((d3pm_purity_trunc_kernel<J, false, 2, true>), grid, block, 0, st, *d);
+            });
+        } else if (d->K == 4096 && !dbg) {           // the production shape: every slot holds a class, no hooks, OCC = 2 (no scratch)
             if (mode == 0) hipLaunchKernelGGL((d3pm_purity_kernel<16, true, 0, false, 2>), grid, block, 0, st, *d);
             else if (mode == 1) hipLaunchKernelGGL((d3pm_purity_kernel<16, true, 1, false, 2>), grid, block, 0, st, *d);
             else hipLaunchKernelGGL((d3pm_purity_kernel<16, true, 2, false, 2>), grid, block, 0, st, *d);
-            return;
+        } else {                                     // never FULL, OCC = 3; test hooks in the draw pass only
+            for_class_width(d->K, [&](auto jc) {
+                constexpr int J = decltype(jc)::value;
+                if (mode == 0) hipLaunchKernelGGL((d3pm_purity_kernel<J, false, 0, false>), grid, block, 0, st, *d);
+                else if (mode == 1) hipLaunchKernelGGL((d3pm_purity_kernel<J, false, 1, false>), grid, block, 0, st, *d);
+                else if (!dbg) hipLaunchKernelGGL((d3pm_purity_kernel<J, false, 2, false>), grid, block, 0, st, *d);
+                else hipLaunchKernelGGL((d3pm_purity_kernel<J, false, 2, true>), grid, block, 0, st, *d);
+            });
         }
-#define GSDD_PURITY_LAUNCH(JJ)                                                                                          \
-    do {                                                                                                                \
-        if (mode == 0) hipLaunchKernelGGL((d3pm_purity_kernel<JJ, false, 0, false>), grid, block, 0, st, *d);          \
-        else if (mode == 1) hipLaunchKernelGGL((d3pm_purity_kernel<JJ, false, 1, false>), grid, block, 0, st, *d);     \
-        else if (!dbg) hipLaunchKernelGGL((d3pm_purity_kernel<JJ, false, 2, false>), grid, block, 0, st, *d);          \
-        else hipLaunchKernelGGL((d3pm_purity_kernel<JJ, false, 2, true>), grid, block, 0, st, *d);                     \
-    } while (0)
-        if (J <= 1) GSDD_PURITY_LAUNCH(1);
-        else if (J <= 2) GSDD_PURITY_LAUNCH(2);
-        else if (J <= 4) GSDD_PURITY_LAUNCH(4);
-        else if (J <= 8) GSDD_PURITY_LAUNCH(8);
-        else if (J <= 16) GSDD_PURITY_LAUNCH(16);
-        else GSDD_PURITY_LAUNCH(32);
-#undef GSDD_PURITY_LAUNCH
     };
     launch(two_pass ? 1 : 0);
     GSDD_CHECK_LAUNCH();

@@ -2,6 +2,8 @@
 // quads k = 4*lane + 256*j; the restricted-range expf / logf, the reference's log_add_exp, the fp64-sum log_softmax, the wave
 // log-sum-exp, the top-r truncation, the Gumbel transform and the first-index arg-max they share.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace gsdd {
@@ -221,6 +223,19 @@ __device__ __forceinline__ int known_row_draw(int tok, float hit, float miss, fl
         if (v > best) { best = v; best_k = K; }
     }
     return wave_argmax(best, best_k);
+}
+
+// Host side: the one map from a class count K <= 8192 to the register quads per lane of the kernel that covers it.  Calls
+// f(std::integral_constant<int, J>{}) with the smallest J in {1, 2, 4, 8, 16, 32} such that K <= 256 J; the caller's generic lambda
+// picks the other template arguments of its kernel family (FULL, DBG, OCC, MODE) and launches.
+template <class F>
+void for_class_width(int K, F&& f) {
+    if (K <= 256) f(std::integral_constant<int, 1>{});
+    else if (K <= 512) f(std::integral_constant<int, 2>{});
+    else if (K <= 1024) f(std::integral_constant<int, 4>{});
+    else if (K <= 2048) f(std::integral_constant<int, 8>{});
+    else if (K <= 4096) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 32>{});
 }
 
 }  // namespace gsdd

@@ -695,79 +695,72 @@ __global__ __launch_bounds__(256, 2) void d3pm_train_bwd_kernel(TrainBwdArgs d, 
 
 using namespace gsdd;
 
+// false if one of the eight schedule buffers is null
+static bool fill_sched(SchedPtrs& sp, const float* const* sched) {
+    for (int i = 0; i < 8; ++i) {
+        if (sched[i] == nullptr) return false;
+        sp.p[i] = sched[i];
+    }
+    return true;
+}
+
+// the per-sample reductions and the scalar loss from what the loss (or the fused loss + gradient) kernel left in d's outputs
+static void launch_train_finalize(const gsdd_train_desc* d, hipStream_t st) {
+    TrainFinArgs f;
+    f.kl = d->kl; f.nll = d->nll; f.aux = d->aux; f.x0 = d->x0; f.xt = d->xt; f.x0_recon = d->x0_recon;
+    f.xt1_recon = d->xt1_recon; f.t_dev = d->t_dev; f.pt = d->pt; f.B = d->B; f.L = d->L; f.T = d->T;
+    f.aux_weight = d->aux_weight; f.adaptive = d->adaptive_aux; f.Lt_history = d->Lt_history; f.Lt_count = d->Lt_count;
+    f.loss = d->loss; f.per_sample = d->per_sample;
+    hipLaunchKernelGGL(d3pm_train_finalize_kernel, dim3(1), dim3(256), 0, st, f);
+}
+
 extern "C" int gsdd_d3pm_step(const gsdd_step_desc* d, void* stream) {
     GSDD_CHECK_ARG(d != nullptr, "null descriptor");
     GSDD_CHECK_ARG(d->logits_c && d->tok_in && d->tok_out && d->t_dev && d->stream_dev, "null pointer");
     GSDD_CHECK_ARG(d->B > 0 && d->L > 0 && d->T > 0, "bad sizes");
     GSDD_CHECK_ARG(d->K >= 4 && d->K % 4 == 0 && d->K <= 8192, "K must be a multiple of 4 in [4, 8192]");
-    for (int i = 0; i < 8; ++i) GSDD_CHECK_ARG(d->sched[i] != nullptr, "null schedule buffer");
     SchedPtrs sp;
-    for (int i = 0; i < 8; ++i) sp.p[i] = d->sched[i];
+    GSDD_CHECK_ARG(fill_sched(sp, d->sched), "null schedule buffer");
     const int64_t npos = (int64_t)d->B * d->L;
     const dim3 grid((unsigned)((npos + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    const int J = (d->K + 255) / 256;
     const bool dbg = d->post_dbg != nullptr || d->x0_dbg != nullptr;
+    const bool trunc = d->trunc_rate != 0.f;
     GSDD_CHECK_ARG(d->occupancy == 0 || d->occupancy == 2 || d->occupancy == 3, "occupancy: 0 (auto), 2 or 3 waves per SIMD");
     GSDD_CHECK_ARG(d->post_skip >= 0, "post_skip must be >= 0");
     GSDD_CHECK_ARG(d->trunc_rate == 0.f || (d->trunc_rate > 0.f && d->trunc_rate < 1.f), "trunc_rate must be 0 (off) or in (0, 1)");
-    if (d->known != nullptr) {                     // positions with a given clean token: the d3pm_step_known*_kernel families (FULL at K = 4096 only)
+    if (d->known != nullptr) {                     // positions with a given clean token: the d3pm_step_known*_kernel families
         GSDD_CHECK_ARG(d->x_known != nullptr, "known needs x_known");
         GSDD_CHECK_ARG(d->known_mode == 0 || d->known_mode == 1, "known_mode: 0 (renoise) or 1 (hold)");
         GSDD_CHECK_ARG(!dbg, "known cannot be combined with post_dbg / x0_dbg");
-#define GSDD_STEP_KNOWN_LAUNCH(JJ, FF)                                                                               \
-    do {                                                                                                             \
-        if (d->trunc_rate == 0.f) hipLaunchKernelGGL((d3pm_step_known_kernel<JJ, FF>), grid, block, 0, st, *d, sp);  \
-        else hipLaunchKernelGGL((d3pm_step_known_trunc_kernel<JJ, FF>), grid, block, 0, st, *d, sp);                 \
-    } while (0)
-        if (d->K == 4096) GSDD_STEP_KNOWN_LAUNCH(16, true);
-        else if (J <= 1) GSDD_STEP_KNOWN_LAUNCH(1, false);
-        else if (J <= 2) GSDD_STEP_KNOWN_LAUNCH(2, false);
-        else if (J <= 4) GSDD_STEP_KNOWN_LAUNCH(4, false);
-        else if (J <= 8) GSDD_STEP_KNOWN_LAUNCH(8, false);
-        else if (J <= 16) GSDD_STEP_KNOWN_LAUNCH(16, false);
-        else GSDD_STEP_KNOWN_LAUNCH(32, false);
-#undef GSDD_STEP_KNOWN_LAUNCH
-        GSDD_CHECK_LAUNCH();
-        return GSDD_OK;
-    }
-    if (d->trunc_rate != 0.f) {                    // top-r truncated sampling: the d3pm_step_trunc_kernel family (FULL at K = 4096 only)
-#define GSDD_STEP_TRUNC_LAUNCH(JJ, FF)                                                                               \
-    do {                                                                                                             \
-        if (!dbg) hipLaunchKernelGGL((d3pm_step_trunc_kernel<JJ, FF, false>), grid, block, 0, st, *d, sp);           \
-        else hipLaunchKernelGGL((d3pm_step_trunc_kernel<JJ, FF, true>), grid, block, 0, st, *d, sp);                 \
-    } while (0)
-        if (d->K == 4096) GSDD_STEP_TRUNC_LAUNCH(16, true);
-        else if (J <= 1) GSDD_STEP_TRUNC_LAUNCH(1, false);
-        else if (J <= 2) GSDD_STEP_TRUNC_LAUNCH(2, false);
-        else if (J <= 4) GSDD_STEP_TRUNC_LAUNCH(4, false);
-        else if (J <= 8) GSDD_STEP_TRUNC_LAUNCH(8, false);
-        else if (J <= 16) GSDD_STEP_TRUNC_LAUNCH(16, false);
-        else GSDD_STEP_TRUNC_LAUNCH(32, false);
-#undef GSDD_STEP_TRUNC_LAUNCH
-        GSDD_CHECK_LAUNCH();
-        return GSDD_OK;
-    }
-    if (J > 8 && J <= 16 && d->K == 4096 && !dbg && d->occupancy != 3) {       // the production shape: no scratch (see the kernel's note)
+        // FULL at K = 4096 only
+        if (d->K == 4096 && !trunc) hipLaunchKernelGGL((d3pm_step_known_kernel<16, true>), grid, block, 0, st, *d, sp);
+        else if (d->K == 4096) hipLaunchKernelGGL((d3pm_step_known_trunc_kernel<16, true>), grid, block, 0, st, *d, sp);
+        else for_class_width(d->K, [&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (!trunc) hipLaunchKernelGGL((d3pm_step_known_kernel<J, false>), grid, block, 0, st, *d, sp);
+            else hipLaunchKernelGGL((d3pm_step_known_trunc_kernel<J, false>), grid, block, 0, st, *d, sp);
+        });
+    } else if (trunc) {                            // top-r truncated sampling: the d3pm_step_trunc_kernel family, FULL at K = 4096 only
+        if (d->K == 4096 && !dbg) hipLaunchKernelGGL((d3pm_step_trunc_kernel<16, true, false>), grid, block, 0, st, *d, sp);
+        else if (d->K == 4096) hipLaunchKernelGGL((d3pm_step_trunc_kernel<16, true, true>), grid, block, 0, st, *d, sp);
+        else for_class_width(d->K, [&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (!dbg) hipLaunchKernelGGL((d3pm_step_trunc_kernel<J, false, false>), grid, block, 0, st, *d, sp);
+            else hipLaunchKernelGGL((d3pm_step_trunc_kernel<J, false, true>), grid, block, 0, st, *d, sp);
+        });
+    } else if (d->K == 4096 && !dbg && d->occupancy != 3) {    // the production shape: OCC = 2, no scratch (see the kernel's note)
         hipLaunchKernelGGL((d3pm_step_kernel<16, true, false, 2>), grid, block, 0, st, *d, sp);
-        GSDD_CHECK_LAUNCH();
-        return GSDD_OK;
+    } else {                                       // the plain family: FULL at every K == 256 J, OCC = 3
+        for_class_width(d->K, [&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            const bool full = d->K == 256 * J;
+            if (full && !dbg) hipLaunchKernelGGL((d3pm_step_kernel<J, true, false>), grid, block, 0, st, *d, sp);
+            else if (full) hipLaunchKernelGGL((d3pm_step_kernel<J, true, true>), grid, block, 0, st, *d, sp);
+            else if (!dbg) hipLaunchKernelGGL((d3pm_step_kernel<J, false, false>), grid, block, 0, st, *d, sp);
+            else hipLaunchKernelGGL((d3pm_step_kernel<J, false, true>), grid, block, 0, st, *d, sp);
+        });
     }
-#define GSDD_STEP_LAUNCH(JJ)                                                                                         \
-    do {                                                                                                             \
-        const bool full = d->K == 256 * (JJ);                                                                        \
-        if (full && !dbg) hipLaunchKernelGGL((d3pm_step_kernel<JJ, true, false>), grid, block, 0, st, *d, sp);      \
-        else if (full) hipLaunchKernelGGL((d3pm_step_kernel<JJ, true, true>), grid, block, 0, st, *d, sp);          \
-        else if (!dbg) hipLaunchKernelGGL((d3pm_step_kernel<JJ, false, false>), grid, block, 0, st, *d, sp);        \
-        else hipLaunchKernelGGL((d3pm_step_kernel<JJ, false, true>), grid, block, 0, st, *d, sp);                   \
-    } while (0)
-    if (J <= 1) GSDD_STEP_LAUNCH(1);
-    else if (J <= 2) GSDD_STEP_LAUNCH(2);
-    else if (J <= 4) GSDD_STEP_LAUNCH(4);
-    else if (J <= 8) GSDD_STEP_LAUNCH(8);
-    else if (J <= 16) GSDD_STEP_LAUNCH(16);
-    else GSDD_STEP_LAUNCH(32);
-#undef GSDD_STEP_LAUNCH
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }
@@ -778,10 +771,7 @@ extern "C" int gsdd_d3pm_q_sample(const int64_t* x0, int64_t* xt, int B, int L, 
     GSDD_CHECK_ARG(x0 && xt && sched && t_dev && stream_dev, "null pointer");
     GSDD_CHECK_ARG(B > 0 && L > 0 && T > 0 && K >= 4 && K % 4 == 0, "bad sizes");
     SchedPtrs sp;
-    for (int i = 0; i < 8; ++i) {
-        GSDD_CHECK_ARG(sched[i] != nullptr, "null schedule buffer");
-        sp.p[i] = sched[i];
-    }
+    GSDD_CHECK_ARG(fill_sched(sp, sched), "null schedule buffer");
     const int64_t npos = (int64_t)B * L;
     hipLaunchKernelGGL(d3pm_q_sample_kernel, dim3((unsigned)((npos + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x0,
                        xt, B, L, K, T, sp, t_dev, seed, stream_dev, row0);
@@ -825,10 +815,7 @@ extern "C" int gsdd_d3pm_train_loss(const gsdd_train_desc* d, void* stream) {
     GSDD_CHECK_ARG(d->B > 0 && d->B <= 1024 && d->L > 0 && d->T > 0, "bad sizes (B <= 1024)");
     GSDD_CHECK_ARG(d->K >= 4 && d->K % 4 == 0 && d->K <= 8192, "K must be a multiple of 4 in [4, 8192]");
     SchedPtrs sp;
-    for (int i = 0; i < 8; ++i) {
-        GSDD_CHECK_ARG(d->sched[i] != nullptr, "null schedule buffer");
-        sp.p[i] = d->sched[i];
-    }
+    GSDD_CHECK_ARG(fill_sched(sp, d->sched), "null schedule buffer");
     TrainArgs a;
     a.logits = d->logits; a.x0 = d->x0; a.xt = d->xt; a.t_dev = d->t_dev; a.B = d->B; a.L = d->L; a.K = d->K; a.T = d->T;
     a.mw_mask = d->mask_weight[0]; a.mw_other = d->mask_weight[1];
@@ -836,21 +823,12 @@ extern "C" int gsdd_d3pm_train_loss(const gsdd_train_desc* d, void* stream) {
     const int64_t npos = (int64_t)d->B * d->L;
     const dim3 grid((unsigned)((npos + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    const int J = (d->K + 255) / 256;
-    if (d->K == 4096) hipLaunchKernelGGL((d3pm_train_loss_kernel<16, true>), grid, block, 0, st, a, sp);
-    else if (J <= 1) hipLaunchKernelGGL(d3pm_train_loss_kernel<1>, grid, block, 0, st, a, sp);
-    else if (J <= 2) hipLaunchKernelGGL(d3pm_train_loss_kernel<2>, grid, block, 0, st, a, sp);
-    else if (J <= 4) hipLaunchKernelGGL(d3pm_train_loss_kernel<4>, grid, block, 0, st, a, sp);
-    else if (J <= 8) hipLaunchKernelGGL(d3pm_train_loss_kernel<8>, grid, block, 0, st, a, sp);
-    else if (J <= 16) hipLaunchKernelGGL(d3pm_train_loss_kernel<16>, grid, block, 0, st, a, sp);
-    else hipLaunchKernelGGL(d3pm_train_loss_kernel<32>, grid, block, 0, st, a, sp);
+    if (d->K == 4096) hipLaunchKernelGGL((d3pm_train_loss_kernel<16, true>), grid, block, 0, st, a, sp);      // FULL at K = 4096 only
+    else for_class_width(d->K, [&](auto jc) {
+        hipLaunchKernelGGL(d3pm_train_loss_kernel<decltype(jc)::value>, grid, block, 0, st, a, sp);
+    });
     GSDD_CHECK_LAUNCH();
-    TrainFinArgs f;
-    f.kl = d->kl; f.nll = d->nll; f.aux = d->aux; f.x0 = d->x0; f.xt = d->xt; f.x0_recon = d->x0_recon;
-    f.xt1_recon = d->xt1_recon; f.t_dev = d->t_dev; f.pt = d->pt; f.B = d->B; f.L = d->L; f.T = d->T;
-    f.aux_weight = d->aux_weight; f.adaptive = d->adaptive_aux; f.Lt_history = d->Lt_history; f.Lt_count = d->Lt_count;
-    f.loss = d->loss; f.per_sample = d->per_sample;
-    hipLaunchKernelGGL(d3pm_train_finalize_kernel, dim3(1), dim3(256), 0, st, f);
+    launch_train_finalize(d, st);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }
@@ -869,12 +847,7 @@ extern "C" int gsdd_d3pm_train_loss_grad(const gsdd_train_desc* d, float* dlogit
     GSDD_CHECK_ARG(d->B <= 1024, "bad sizes (B <= 1024)");
     const int rc = train_bwd_launch(d, dlogits, true, stream);
     if (rc != GSDD_OK) return rc;
-    TrainFinArgs f;
-    f.kl = d->kl; f.nll = d->nll; f.aux = d->aux; f.x0 = d->x0; f.xt = d->xt; f.x0_recon = d->x0_recon;
-    f.xt1_recon = d->xt1_recon; f.t_dev = d->t_dev; f.pt = d->pt; f.B = d->B; f.L = d->L; f.T = d->T;
-    f.aux_weight = d->aux_weight; f.adaptive = d->adaptive_aux; f.Lt_history = d->Lt_history; f.Lt_count = d->Lt_count;
-    f.loss = d->loss; f.per_sample = d->per_sample;
-    hipLaunchKernelGGL(d3pm_train_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f);
+    launch_train_finalize(d, (hipStream_t)stream);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }
@@ -884,10 +857,7 @@ static int train_bwd_launch(const gsdd_train_desc* d, float* dlogits, bool with_
     GSDD_CHECK_ARG(d->logits && d->x0 && d->xt && d->t_dev && d->pt, "null pointer");
     GSDD_CHECK_ARG(d->B > 0 && d->L > 0 && d->T > 0 && d->K >= 4 && d->K % 4 == 0 && d->K <= 8192, "bad sizes");
     SchedPtrs sp;
-    for (int i = 0; i < 8; ++i) {
-        GSDD_CHECK_ARG(d->sched[i] != nullptr, "null schedule buffer");
-        sp.p[i] = d->sched[i];
-    }
+    GSDD_CHECK_ARG(fill_sched(sp, d->sched), "null schedule buffer");
     TrainBwdArgs a;
     a.logits = d->logits; a.x0 = d->x0; a.xt = d->xt; a.t_dev = d->t_dev; a.pt = d->pt;
     a.B = d->B; a.L = d->L; a.K = d->K; a.T = d->T;
@@ -897,14 +867,8 @@ static int train_bwd_launch(const gsdd_train_desc* d, float* dlogits, bool with_
     const int64_t npos = (int64_t)d->B * d->L;
     const dim3 grid((unsigned)((npos + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    const int J = (d->K + 255) / 256;
     // dynamic LDS: one float4 per (wave, register quad, lane) = 4 KB * J per workgroup (64 KB at K = 4096: two workgroups per CU)
-#define GSDD_BWD_LAUNCH(JJ)                                                                                                   \
-    do {                                                                                                                      \
-        if (with_loss) hipLaunchKernelGGL((d3pm_train_bwd_kernel<JJ, true>), grid, block, (size_t)4096 * JJ, st, a, sp);      \
-        else hipLaunchKernelGGL((d3pm_train_bwd_kernel<JJ, false>), grid, block, (size_t)4096 * JJ, st, a, sp);               \
-    } while (0)
-    if (J > 16) {                                  // J = 32 (4096 < K <= 8192) needs 128 KB of dynamic LDS: above the 64 KB default
+    if (d->K > 4096) {                             // J = 32 (4096 < K <= 8192) needs 128 KB of dynamic LDS: above the 64 KB default
         int dev = 0, lds_max = 0;
         GSDD_CHECK_HIP(hipGetDevice(&dev));
         GSDD_CHECK_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
@@ -914,16 +878,14 @@ static int train_bwd_launch(const gsdd_train_desc* d, float* dlogits, bool with_
             GSDD_CHECK_HIP(hipFuncSetAttribute((const void*)d3pm_train_bwd_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 32));
         );
     }
-    if (d->K == 4096) {                            // the workload's class count: every register slot holds a class
-        if (with_loss) hipLaunchKernelGGL((d3pm_train_bwd_kernel<16, true, true>), grid, block, (size_t)4096 * 16, st, a, sp);
-        else hipLaunchKernelGGL((d3pm_train_bwd_kernel<16, false, true>), grid, block, (size_t)4096 * 16, st, a, sp);
-    } else if (J <= 1) GSDD_BWD_LAUNCH(1);
-    else if (J <= 2) GSDD_BWD_LAUNCH(2);
-    else if (J <= 4) GSDD_BWD_LAUNCH(4);
-    else if (J <= 8) GSDD_BWD_LAUNCH(8);
-    else if (J <= 16) GSDD_BWD_LAUNCH(16);
-    else GSDD_BWD_LAUNCH(32);
-#undef GSDD_BWD_LAUNCH
+    // FULL at K = 4096, the workload's class count, only: every register slot holds a class
+    if (d->K == 4096 && with_loss) hipLaunchKernelGGL((d3pm_train_bwd_kernel<16, true, true>), grid, block, (size_t)4096 * 16, st, a, sp);
+    else if (d->K == 4096) hipLaunchKernelGGL((d3pm_train_bwd_kernel<16, false, true>), grid, block, (size_t)4096 * 16, st, a, sp);
+    else for_class_width(d->K, [&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        if (with_loss) hipLaunchKernelGGL((d3pm_train_bwd_kernel<J, true>), grid, block, (size_t)4096 * J, st, a, sp);
+        else hipLaunchKernelGGL((d3pm_train_bwd_kernel<J, false>), grid, block, (size_t)4096 * J, st, a, sp);
+    });
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }

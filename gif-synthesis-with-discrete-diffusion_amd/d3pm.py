@@ -12,6 +12,7 @@ import contextlib
 import ctypes
 import numbers
 import os
+import types
 
 import torch
 import torch.nn as nn
@@ -405,9 +406,15 @@ def alpha_schedule(time_step, N=100, att_1=0.99999, att_T=0.000009, ctt_1=0.0000
     return at, bt, ct, att, btt, ctt
 
 
-SamplePlan = collections.namedtuple("SamplePlan", "t0 n_steps dt post_skip q_sample")
-SamplePlan.__doc__ = """A reverse chain: the denoiser's first timestep t0, the number of steps, how far t moves per step (t <- max(t - dt, 0)),
-the posterior's skip s (it runs at t - s for t > s, else at t) and whether the start is a q_sample draw of given tokens."""
+class SamplePlan(collections.namedtuple("SamplePlan", "t0 n_steps dt post_skip q_sample")):
+    """A reverse chain: the denoiser's first timestep t0, the number of steps, how far t moves per step (t <- max(t - dt, 0)),
+    the posterior's skip s (it runs at t - s for t > s, else at t) and whether the start is a q_sample draw of given tokens."""
+    __slots__ = ()
+
+    @property
+    def draws(self):
+        """Noise streams a run spends: one per step, one more for the q_sample start."""
+        return self.n_steps + (1 if self.q_sample else 0)
 
 
 def sample_plan(T, skip_step=0, start_step=0):
@@ -430,9 +437,25 @@ def plan_timesteps(plan):
     return out
 
 
-PurityPlan = collections.namedtuple("PurityPlan", "calls final rule weight")
-PurityPlan.__doc__ = """A purity-prior chain (sample() with prior_rule 1 / 2): the (t, n) of every p_sample call at t > 0 -- denoiser at t, reveal n
-[MASK] positions per sample -- whether a plain reverse step at t = 0 closes it, the rule and the prior weight r."""
+class PurityPlan(collections.namedtuple("PurityPlan", "calls final rule weight")):
+    """A purity-prior chain (sample() with prior_rule 1 / 2): the (t, n) of every p_sample call at t > 0 -- denoiser at t, reveal n
+    [MASK] positions per sample -- whether a plain reverse step at t = 0 closes it, the rule and the prior weight r.
+    n_steps, t0, q_sample and draws read like SamplePlan's: what the sampling loop asks of either plan."""
+    __slots__ = ()
+    q_sample = False                                # from all-[MASK] only
+
+    @property
+    def n_steps(self):
+        return len(self.calls)
+
+    @property
+    def t0(self):
+        return self.calls[0][0] if self.calls else 0
+
+    @property
+    def draws(self):
+        """Two noise streams per call (candidates, selection), one more for the closing plain step."""
+        return 2 * len(self.calls) + (1 if self.final else 0)
 
 
 def reference_n_sample(T, prior_ps=1024):
@@ -564,6 +587,15 @@ def check_known(known_mask, content_token, known_mode, *, B, L, K, start_step=0,
         raise GsddError(f"content_token at known positions must lie in [0, {K}): found {int(at.min())} .. {int(at.max())} "
                         f"([MASK] = {K} is not a clean token)")
     return mask.contiguous(), tok.contiguous(), KNOWN_MODES[known_mode]
+
+
+def _known_kwargs(known, dev, sl=slice(None)):
+    """check_known's result -> the known / x_known / known_mode keywords of ops.d3pm_step for the clips `sl` of the batch, on `dev`;
+    nothing at all without a mask."""
+    if known is None:
+        return {}
+    mask, tok, mode = known
+    return {"known": mask[sl].to(dev).to(torch.uint8).contiguous(), "x_known": tok[sl].to(dev).contiguous(), "known_mode": mode}
 
 
 SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct",
@@ -767,11 +799,9 @@ class DiffusionTransformer(nn.Module):
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
         same_cond = (guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape and bool(torch.equal(cond, cf)))
         purity = isinstance(plan, PurityPlan)       # prior_rule 1 / 2: the calls at t > 0 come from device plan arrays; the rest is shared
-        q_sample = not purity and plan.q_sample
-        n_steps = len(plan.calls) if purity else plan.n_steps
-        t0 = (plan.calls[0][0] if plan.calls else 0) if purity else plan.t0
-        stream0 = self.noise_stream + (1 if q_sample else 0)           # the partially noised start spends one draw on q_sample
-        if q_sample:
+        n_steps = plan.n_steps
+        stream0 = self.noise_stream + (1 if plan.q_sample else 0)      # the partially noised start spends one draw on q_sample
+        if plan.q_sample:
             x0_start = content_token.to(dev).long().reshape(B, L).contiguous()
             if int(x0_start.min()) < 0 or int(x0_start.max()) > K:
                 raise GsddError("content_token outside [0, num_embed]")
@@ -791,6 +821,35 @@ class DiffusionTransformer(nn.Module):
         self._stream = self._streams[0]
         Bs = B // lanes
         toks, graphs, finals, redo_counters, range_flags = [], [], [], [], []
+        sched = self._sched()
+
+        # The steps of a lane's chain.  `lane` holds what belongs to one sub-batch: its stream st, tokens tok, condition vectors condv
+        # (Te condition tokens), timesteps t2, workspace ws, noise-stream counter sid, M = Bs L positions from global row row0, its
+        # known-position keywords and, for a purity chain, the plan arrays, counters and candidate buffers.
+        def denoise(lane):                      # -> the conditional and the unconditional logits of the lane's tokens at t2
+            logits = tr.run(lane.tok, lane.condv, lane.Te, lane.t2, lane.ws, rep=rep, stream=lane.st)
+            return logits[:lane.M], (logits[lane.M:] if rep == 2 else logits[:lane.M]) if guided else None
+
+        def plain_step(lane, post_skip):
+            ops.d3pm_step(*denoise(lane), lane.tok, lane.tok, sched, lane.t2, lane.sid, K=K, T=T, guidance=float(self.guidance_scale),
+                          seed=self.noise_seed, row0=lane.row0, post_skip=post_skip, stream=lane.st, **trunc_kw, **lane.known_kw)
+
+        def chain_step(lane):
+            plain_step(lane, plan.post_skip)
+            if plan.dt == 1:
+                ops.advance(lane.t2, -1, lane.sid, 1, stream=lane.st)
+            else:                               # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
+                ops.advance_floor(lane.t2, -plan.dt, 0, lane.sid, 1, stream=lane.st)
+
+        def purity_step(lane):
+            ops.d3pm_purity_step(*denoise(lane), lane.score, lane.smax, lane.cand, lane.sid, K=K, guidance=float(self.guidance_scale),
+                                 prior_rule=plan.rule, prior_weight=plan.weight, seed=self.noise_seed, row0=lane.row0, stream=lane.st,
+                                 **trunc_kw)
+            ops.d3pm_purity_select(lane.tok, lane.tok, lane.cand, lane.score, lane.smax, lane.n_dev, lane.sid, K=K, prior_rule=plan.rule,
+                                   seed=self.noise_seed, stream_add=1, row0=lane.row0, stream=lane.st)
+            ops.advance_plan(lane.step_dev, lane.plan_t, lane.plan_n, lane.t2, lane.n_dev, lane.sid, 2, stream=lane.st)
+
+        one_step = purity_step if purity else chain_step
         cur = torch.cuda.current_stream()
         tr.packed()                                 # packed weights, AdaLN tables and the fragment images are (re)built HERE, on the
         tr.fragment_images()                        # caller's stream: each lane's wait_stream(cur) below then orders its reads after them
@@ -800,88 +859,58 @@ class DiffusionTransformer(nn.Module):
             with torch.cuda.stream(st):
                 sl = slice(ln * Bs, (ln + 1) * Bs)
                 conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
-                Te = conds.shape[1]
-                condv = tr.cond_vectors(conds.contiguous())
-                ws = tr.workspace(rep * Bs, L, dev, rep=rep)
-                redo_counters.append(ws["redo"])
-                range_flags.append(ws["range"])
-                t2 = torch.full((rep * Bs,), t0, dtype=torch.int64, device=dev)
-                sid = torch.tensor([stream0], dtype=torch.int64, device=dev)
-                sched = self._sched()
-                M = Bs * L
-                row0 = (self.row_offset + ln * Bs) * L
-                if not q_sample:
-                    tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)           # all [MASK] (:613-618)
+                lane = types.SimpleNamespace(st=st, Te=conds.shape[1], M=Bs * L, row0=(self.row_offset + ln * Bs) * L)
+                lane.condv = tr.cond_vectors(conds.contiguous())
+                lane.ws = tr.workspace(rep * Bs, L, dev, rep=rep)
+                redo_counters.append(lane.ws["redo"])
+                range_flags.append(lane.ws["range"])
+                lane.t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
+                lane.sid = torch.tensor([stream0], dtype=torch.int64, device=dev)
+                if not plan.q_sample:
+                    lane.tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)      # all [MASK] (:613-618)
                 else:                                                                    # q_sample at t = start_step - 1 (:628-630)
-                    tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
-                    ops.d3pm_q_sample(x0_start[sl].contiguous(), tok, sched, t2[:Bs].contiguous(),
+                    lane.tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
+                    ops.d3pm_q_sample(x0_start[sl].contiguous(), lane.tok, sched, lane.t2[:Bs].contiguous(),
                                       torch.tensor([self.noise_stream], dtype=torch.int64, device=dev), K=K, T=T,
-                                      seed=self.noise_seed, row0=row0, stream=st)
-
+                                      seed=self.noise_seed, row0=lane.row0, stream=st)
                 # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they
                 # are constants of the chain, so the captured graph is still one step; nothing at all without a mask
-                known_kw = {} if known is None else {"known": known[0][sl].to(dev).to(torch.uint8).contiguous(),
-                                                     "x_known": known[1][sl].to(dev).contiguous(), "known_mode": known[2]}
-
-                def plain_step(post_skip, tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st, known_kw=known_kw):
-                    logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
-                    ops.d3pm_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, tok, tok, sched, t2, sid, K=K, T=T,
-                                  guidance=float(self.guidance_scale), seed=self.noise_seed, row0=row0, post_skip=post_skip, stream=st,
-                                  **trunc_kw, **known_kw)
-
+                lane.known_kw = _known_kwargs(known, dev, sl)
                 if purity:
                     # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
                     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
-                    plan_t, plan_n = i64([t for t, _ in plan.calls] + [0]), i64([n for _, n in plan.calls] + [0])
-                    step_dev, n_dev = i64([0]), i64([plan.calls[0][1] if plan.calls else 0])
-                    score = torch.empty((Bs, L), dtype=torch.float32, device=dev)
-                    smax = torch.empty((Bs,), dtype=torch.float32, device=dev)
-                    cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
-
-                    def one_step(tok=tok, condv=condv, Te=Te, t2=t2, ws=ws, sid=sid, M=M, row0=row0, st=st, plan_t=plan_t, plan_n=plan_n,
-                                 step_dev=step_dev, n_dev=n_dev, score=score, smax=smax, cand=cand):
-                        logits = tr.run(tok, condv, Te, t2, ws, rep=rep, stream=st)
-                        ops.d3pm_purity_step(logits[:M], (logits[M:] if rep == 2 else logits[:M]) if guided else None, score, smax, cand, sid,
-                                             K=K, guidance=float(self.guidance_scale), prior_rule=plan.rule, prior_weight=plan.weight,
-                                             seed=self.noise_seed, row0=row0, stream=st, **trunc_kw)
-                        ops.d3pm_purity_select(tok, tok, cand, score, smax, n_dev, sid, K=K, prior_rule=plan.rule, seed=self.noise_seed,
-                                               stream_add=1, row0=row0, stream=st)
-                        ops.advance_plan(step_dev, plan_t, plan_n, t2, n_dev, sid, 2, stream=st)
-
+                    lane.plan_t, lane.plan_n = i64([t for t, _ in plan.calls] + [0]), i64([n for _, n in plan.calls] + [0])
+                    lane.step_dev, lane.n_dev = i64([0]), i64([plan.calls[0][1] if plan.calls else 0])
+                    lane.score = torch.empty((Bs, L), dtype=torch.float32, device=dev)
+                    lane.smax = torch.empty((Bs,), dtype=torch.float32, device=dev)
+                    lane.cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
                     if plan.final:
-                        finals.append((st, lambda plain_step=plain_step: plain_step(0)))
-                else:
-                    def one_step(plain_step=plain_step, t2=t2, sid=sid, st=st):
-                        plain_step(plan.post_skip)
-                        if plan.dt == 1:
-                            ops.advance(t2, -1, sid, 1, stream=st)
-                        else:                   # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
-                            ops.advance_floor(t2, -plan.dt, 0, sid, 1, stream=st)
+                        finals.append(lane)
 
                 if n_steps == 0:                # (a purity schedule that reveals nothing at t >= 1)
                     pass
                 elif use_graph and trace is None:
-                    one_step()                  # eager first step (validates arguments outside capture)
+                    one_step(lane)              # eager first step (validates arguments outside capture)
                     g = ops.Graph()
                     g.begin(st)
-                    one_step()                  # recorded, not executed
+                    one_step(lane)              # recorded, not executed
                     g.end(st)
                     graphs.append(g)
                 else:
                     for _ in range(n_steps):
-                        one_step()
+                        one_step(lane)
                         if trace is not None:
-                            trace.append(tok.clone())
-                toks.append(tok)
+                            trace.append(lane.tok.clone())
+                toks.append(lane.tok)
         if graphs:
             for _ in range(n_steps - 1):        # the lanes' replays are issued alternately so that both queues stay fed
                 for ln, g in enumerate(graphs):
                     g.launch(self._streams[ln])
             self._last_graph = graphs[0]
             self._last_graphs = graphs
-        for st, final_step in finals:           # the purity chain's ordinary reverse step at t = 0, after the lane's replays
-            with torch.cuda.stream(st):
-                final_step()
+        for lane in finals:                     # the purity chain's ordinary reverse step at t = 0, after the lane's replays
+            with torch.cuda.stream(lane.st):
+                plain_step(lane, 0)
                 if trace is not None:           # (a trace runs in one lane)
                     trace.append(toks[0].clone())
         for ln in range(lanes):
@@ -892,7 +921,7 @@ class DiffusionTransformer(nn.Module):
         self._range_flags = range_flags
         self._last_lanes = lanes
         self._last_plan = plan
-        self._last_draws = (2 * n_steps + (1 if plan.final else 0)) if purity else n_steps + (1 if q_sample else 0)
+        self._last_draws = plan.draws
         self.noise_stream += self._last_draws
         out = {"content_token": tok}
         if return_logits:
@@ -911,9 +940,8 @@ class DiffusionTransformer(nn.Module):
         t - post_skip for t > post_skip (a sample_fast step, :700-704); truncation_rate: top-r truncation of the guided row;
         known: what `check_known` returns (mask, clean tokens, mode) -- those positions skip the learned step as in sample()."""
         trunc_kw = _trunc_kwargs(check_truncation_rate(truncation_rate))
-        known_kw = {} if known is None else {"known": known[0].to(tok.device).to(torch.uint8).contiguous(),
-                                             "x_known": known[1].to(tok.device).contiguous(), "known_mode": known[2]}
         dev = tok.device
+        known_kw = _known_kwargs(known, dev)
         B, L = tok.shape
         K, T = self.num_classes - 1, self.num_timesteps
         guided = abs(self.guidance_scale - 1) >= 1e-3

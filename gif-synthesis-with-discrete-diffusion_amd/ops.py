@@ -376,28 +376,41 @@ def d3pm_q_sample(x0, xt, sched, t_dev, stream_dev, *, K, T, seed, row0=0, strea
     return xt
 
 
-def d3pm_train_loss(logits, x0, xt, t_dev, pt, sched, Lt_history, Lt_count, *, K, T, mask_weight, aux_weight, adaptive_aux,
-                    want_probs=True, stream=None):
-    """-> dict(loss [1], per_sample [B][4], x0_recon (B,L), xt1_recon (B,L), probs (B,K+1,L) or None)"""
+def _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux):
+    """gsdd_train_desc with its inputs filled; the output pointers stay null (what gsdd_d3pm_train_loss_bwd takes)."""
+    d = TrainDesc()
+    d.logits, d.x0, d.xt, d.t_dev, d.pt = ptr(logits), ptr(x0), ptr(xt), ptr(t_dev), ptr(pt)
+    (d.B, d.L), d.K, d.T = x0.shape, K, T
+    for i in range(8):
+        d.sched[i] = ptr(sched[i])
+    d.mask_weight[0], d.mask_weight[1] = float(mask_weight[0]), float(mask_weight[1])
+    d.aux_weight, d.adaptive_aux = float(aux_weight), int(bool(adaptive_aux))
+    return d
+
+
+def _train_outputs(d, x0, Lt_history, Lt_count, probs_classes=None):
+    """Allocates the forward results and points d at them -> (the result dict, the per-position scratch: the caller holds it until its
+    launch is enqueued)."""
     B, L = x0.shape
     dev = x0.device
     f = dict(dtype=torch.float32, device=dev)
     out = {"loss": torch.empty((1,), **f), "per_sample": torch.empty((B, 4), **f),
            "x0_recon": torch.empty((B, L), dtype=torch.int64, device=dev),
            "xt1_recon": torch.empty((B, L), dtype=torch.int64, device=dev),
-           "probs": torch.empty((B, K + 1, L), **f) if want_probs else None}
+           "probs": torch.empty((B, probs_classes, L), **f) if probs_classes else None}
     scratch = torch.empty((3, B * L), **f)
-    d = TrainDesc()
-    d.logits, d.x0, d.xt, d.t_dev, d.pt = ptr(logits), ptr(x0), ptr(xt), ptr(t_dev), ptr(pt)
-    d.B, d.L, d.K, d.T = B, L, K, T
-    for i in range(8):
-        d.sched[i] = ptr(sched[i])
-    d.mask_weight[0], d.mask_weight[1] = float(mask_weight[0]), float(mask_weight[1])
-    d.aux_weight, d.adaptive_aux = float(aux_weight), int(bool(adaptive_aux))
     d.kl, d.nll, d.aux = ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2])
     d.x0_recon, d.xt1_recon = ptr(out["x0_recon"]), ptr(out["xt1_recon"])
     d.Lt_history, d.Lt_count = ptr(Lt_history), ptr(Lt_count)
     d.loss, d.per_sample, d.probs = ptr(out["loss"]), ptr(out["per_sample"]), ptr(out["probs"])
+    return out, scratch
+
+
+def d3pm_train_loss(logits, x0, xt, t_dev, pt, sched, Lt_history, Lt_count, *, K, T, mask_weight, aux_weight, adaptive_aux,
+                    want_probs=True, stream=None):
+    """-> dict(loss [1], per_sample [B][4], x0_recon (B,L), xt1_recon (B,L), probs (B,K+1,L) or None)"""
+    d = _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux)
+    out, scratch = _train_outputs(d, x0, Lt_history, Lt_count, probs_classes=K + 1 if want_probs else None)
     check(lib().gsdd_d3pm_train_loss(C.byref(d), stream_ptr(stream)))
     return out
 
@@ -405,24 +418,8 @@ def d3pm_train_loss(logits, x0, xt, t_dev, pt, sched, Lt_history, Lt_count, *, K
 def d3pm_train_loss_grad(logits, x0, xt, t_dev, pt, sched, Lt_history, Lt_count, *, K, T, mask_weight, aux_weight, adaptive_aux,
                          stream=None):
     """d3pm_train_loss (without probs) and d3pm_train_loss_bwd in one pass over the logits -> (forward dict, dlogits)."""
-    B, L = x0.shape
-    dev = x0.device
-    f = dict(dtype=torch.float32, device=dev)
-    out = {"loss": torch.empty((1,), **f), "per_sample": torch.empty((B, 4), **f),
-           "x0_recon": torch.empty((B, L), dtype=torch.int64, device=dev),
-           "xt1_recon": torch.empty((B, L), dtype=torch.int64, device=dev), "probs": None}
-    scratch = torch.empty((3, B * L), **f)
-    d = TrainDesc()
-    d.logits, d.x0, d.xt, d.t_dev, d.pt = ptr(logits), ptr(x0), ptr(xt), ptr(t_dev), ptr(pt)
-    d.B, d.L, d.K, d.T = B, L, K, T
-    for i in range(8):
-        d.sched[i] = ptr(sched[i])
-    d.mask_weight[0], d.mask_weight[1] = float(mask_weight[0]), float(mask_weight[1])
-    d.aux_weight, d.adaptive_aux = float(aux_weight), int(bool(adaptive_aux))
-    d.kl, d.nll, d.aux = ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2])
-    d.x0_recon, d.xt1_recon = ptr(out["x0_recon"]), ptr(out["xt1_recon"])
-    d.Lt_history, d.Lt_count = ptr(Lt_history), ptr(Lt_count)
-    d.loss, d.per_sample, d.probs = ptr(out["loss"]), ptr(out["per_sample"]), None
+    d = _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux)
+    out, scratch = _train_outputs(d, x0, Lt_history, Lt_count)
     dlogits = torch.empty_like(logits)
     check(lib().gsdd_d3pm_train_loss_grad(C.byref(d), ptr(dlogits), stream_ptr(stream)))
     return out, dlogits
@@ -529,14 +526,7 @@ class Event:
 
 # ----------------------------------------------------------------------------- training-step building blocks
 def d3pm_train_loss_bwd(logits, x0, xt, t_dev, pt, sched, *, K, T, mask_weight, aux_weight, adaptive_aux, stream=None):
-    B, L = x0.shape
-    d = TrainDesc()
-    d.logits, d.x0, d.xt, d.t_dev, d.pt = ptr(logits), ptr(x0), ptr(xt), ptr(t_dev), ptr(pt)
-    d.B, d.L, d.K, d.T = B, L, K, T
-    for i in range(8):
-        d.sched[i] = ptr(sched[i])
-    d.mask_weight[0], d.mask_weight[1] = float(mask_weight[0]), float(mask_weight[1])
-    d.aux_weight, d.adaptive_aux = float(aux_weight), int(bool(adaptive_aux))
+    d = _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux)
     dlogits = torch.empty_like(logits)
     check(lib().gsdd_d3pm_train_loss_bwd(C.byref(d), ptr(dlogits), stream_ptr(stream)))
     return dlogits

@@ -613,3 +613,59 @@ def test_bench_dump_outputs_stays_within_its_budget_and_samples_the_same_element
     assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= limit
     for f in files:
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+def test_train_loss_wrappers_fill_every_descriptor_field(monkeypatch):
+    """ops.d3pm_train_loss / d3pm_train_loss_grad / d3pm_train_loss_bwd (no GPU: a fake library records the gsdd_train_desc each
+    passes): the input pointers, sizes, weights and all eight schedule pointers as given; the outputs point at the tensors of the
+    returned dict, kl / nll / aux at three consecutive B L rows; probs only for want_probs; the backward-only call leaves every
+    output pointer null."""
+    from gsdd_amd import ops
+    from gsdd_amd._lib import TrainDesc
+    names = [n for n, _ in TrainDesc._fields_]
+    calls = []
+
+    class FakeLib:
+        def _take(self, ref, *rest):
+            d = ref._obj
+            assert type(d) is TrainDesc
+            calls.append(({n: list(getattr(d, n)) if n in ("sched", "mask_weight") else getattr(d, n) for n in names}, rest))
+            return 0
+        gsdd_d3pm_train_loss = gsdd_d3pm_train_loss_grad = gsdd_d3pm_train_loss_bwd = _take
+
+    monkeypatch.setattr(ops, "lib", lambda: FakeLib())
+    monkeypatch.setattr(ops, "ptr", lambda t: None if t is None else ctypes.c_void_p(t.data_ptr()))
+    monkeypatch.setattr(ops, "stream_ptr", lambda s=None: None)
+    B, L, K, T = 2, 3, 8, 5
+    logits = torch.zeros(B * L, K)
+    x0, xt = torch.zeros(B, L, dtype=torch.long), torch.ones(B, L, dtype=torch.long)
+    t, pt = torch.zeros(B, dtype=torch.long), torch.ones(B)
+    sched = [torch.zeros(T + 1) for _ in range(8)]
+    hist, cnt = torch.zeros(T), torch.zeros(T)
+    kw = dict(K=K, T=T, mask_weight=(1.5, 0.25), aux_weight=0.125, adaptive_aux=True)
+    with_probs = ops.d3pm_train_loss(logits, x0, xt, t, pt, sched, hist, cnt, want_probs=True, **kw)
+    no_probs = ops.d3pm_train_loss(logits, x0, xt, t, pt, sched, hist, cnt, want_probs=False, **dict(kw, adaptive_aux=0))
+    fused, dl_fused = ops.d3pm_train_loss_grad(logits, x0, xt, t, pt, sched, hist, cnt, **kw)
+    dl_bwd = ops.d3pm_train_loss_bwd(logits, x0, xt, t, pt, sched, **kw)
+    assert len(calls) == 4
+    outputs = ("kl", "nll", "aux", "x0_recon", "xt1_recon", "Lt_history", "Lt_count", "loss", "per_sample", "probs")
+    for (d, rest), adaptive in zip(calls, (1, 0, 1, 1)):
+        assert set(d) == set(names) and set(outputs) < set(names)
+        assert (d["logits"], d["x0"], d["xt"], d["t_dev"], d["pt"]) == tuple(v.data_ptr() for v in (logits, x0, xt, t, pt))
+        assert (d["B"], d["L"], d["K"], d["T"]) == (B, L, K, T)
+        assert d["sched"] == [s.data_ptr() for s in sched] and len(set(d["sched"])) == 8
+        assert d["mask_weight"] == [1.5, 0.25] and d["aux_weight"] == 0.125 and d["adaptive_aux"] == adaptive
+    for (d, rest), out in zip(calls[:3], (with_probs, no_probs, fused)):
+        assert d["kl"] and d["nll"] == d["kl"] + 4 * B * L and d["aux"] == d["kl"] + 8 * B * L
+        assert (d["x0_recon"], d["xt1_recon"], d["loss"], d["per_sample"]) == tuple(
+            out[k].data_ptr() for k in ("x0_recon", "xt1_recon", "loss", "per_sample"))
+        assert (d["Lt_history"], d["Lt_count"]) == (hist.data_ptr(), cnt.data_ptr())
+        assert out["loss"].shape == (1,) and out["per_sample"].shape == (B, 4) and out["x0_recon"].shape == out["xt1_recon"].shape == (B, L)
+        assert out["x0_recon"].dtype == out["xt1_recon"].dtype == torch.int64
+    assert calls[0][0]["probs"] == with_probs["probs"].data_ptr() and with_probs["probs"].shape == (B, K + 1, L)
+    assert calls[1][0]["probs"] is None and no_probs["probs"] is None
+    assert calls[2][0]["probs"] is None and fused["probs"] is None
+    assert all(calls[3][0][n] is None for n in outputs)
+    # the gradient buffer: the second argument of the two backward entry points, shaped like the logits
+    assert len(calls[0][1]) == 1 and calls[2][1][0].value == dl_fused.data_ptr() and calls[3][1][0].value == dl_bwd.data_ptr()
+    assert dl_fused.shape == dl_bwd.shape == logits.shape and dl_fused.dtype == dl_bwd.dtype == logits.dtype

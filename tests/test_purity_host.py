@@ -245,3 +245,26 @@ def test_selection_rule_is_a_draw_without_replacement():
     # ties go to the lower index; zero weights are never drawn
     assert select_numpy([1, 1, 1], [0.5, 0.5, 0.5], 2).tolist() == [0, 1]
     assert set(select_numpy([0, 1, 0, 1], [0.9, 0.1, 0.9, 0.2], 2).tolist()) == {1, 3}
+
+
+def test_both_plans_answer_what_the_sampling_loop_asks():
+    """n_steps, t0, q_sample and draws of SamplePlan and PurityPlan: the step count, the denoiser's first timestep, whether the chain
+    starts from a q_sample draw, and the noise streams a run spends -- one per step plus the q_sample draw for a SamplePlan, two per
+    call plus the closing plain step for a PurityPlan."""
+    from gsdd_amd.d3pm import PurityPlan, SamplePlan, sample_plan
+    read = lambda p: (p.n_steps, p.t0, bool(p.q_sample), p.draws)
+    assert read(sample_plan(100)) == (100, 99, False, 100)
+    assert read(sample_plan(100, start_step=50)) == (50, 49, True, 51)
+    assert read(sample_plan(100, skip_step=3)) == (26, 99, False, 26)
+    calls = ((99, 11), (99, 4), (97, 10))
+    assert read(PurityPlan(calls, True, 2, 1.0)) == (3, 99, False, 7)
+    assert read(PurityPlan(calls, False, 1, 0.0)) == (3, 99, False, 6)
+    assert read(PurityPlan((), True, 1, 0.0)) == (0, 0, False, 1)
+    assert read(PurityPlan((), False, 1, 0.0)) == (0, 0, False, 0)
+    for p in (sample_plan(100), sample_plan(100, start_step=50), sample_plan(100, skip_step=3)):
+        assert p.draws == p.n_steps + p.q_sample
+    for p in (PurityPlan(calls, True, 2, 1.0), PurityPlan(calls, False, 1, 0.0), PurityPlan((), True, 1, 0.0)):
+        assert p.draws == 2 * len(p.calls) + p.final
+    # still the tuples they were
+    assert SamplePlan._fields == ("t0", "n_steps", "dt", "post_skip", "q_sample") and PurityPlan._fields == ("calls", "final", "rule", "weight")
+    assert sample_plan(100) == (99, 100, 1, 0, False) and PurityPlan(calls, True, 2, 1.0) == (calls, True, 2, 1.0)
