@@ -19,6 +19,7 @@ EXPORTS = [
     "gsdd_batch_rowsum", "gsdd_colsum", "gsdd_d3pm_attention_train", "gsdd_d3pm_attention_bwd", "gsdd_d3pm_attention_bwd_workspace_bytes", "gsdd_d3pm_embed_bwd", "gsdd_small_linear_bwd",
     "gsdd_adaln_bwd", "gsdd_adam", "gsdd_adam_multi", "gsdd_adam_multi_dev", "gsdd_advance", "gsdd_advance_floor",
     "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan",
+    "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
 ]
@@ -182,6 +183,9 @@ def lib():
         L.gsdd_d3pm_purity_step.argtypes = [C.POINTER(PurityDesc), _p]
         L.gsdd_d3pm_purity_select.argtypes = [C.POINTER(PuritySelectDesc), _p]
         L.gsdd_advance_plan.argtypes = [_p, _p, _p, _i64, _p, _i, _p, _p, _i64, _p]
+        L.gsdd_text_embed.argtypes = [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]
+        L.gsdd_text_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]
+        L.gsdd_text_pool.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p]
         L.gsdd_philox_uniform.argtypes = [C.c_uint64, _i64, _i64, _i64, _i, _p, _p]
         L.gsdd_graph_begin.argtypes = [_p]
         L.gsdd_graph_end.argtypes = [_p, C.POINTER(_p)]

@@ -43,6 +43,23 @@ def select(state, prefix):
     return dict(state)
 
 
+# (the reference holds the provider as DiscreteDiffusion.textencoder, so a whole-model file has it under "generator." as well)
+CLIP_TEXT_PREFIXES = ("textencoder.clip_model.", "generator.textencoder.clip_model.")
+
+
+def extract_clip_text_tower(path_or_state):
+    """The CLIP text tower of a reference Lightning checkpoint: the tensors under `textencoder.clip_model.` (or `generator.textencoder.clip_model.`) in the `clip` package's
+    layout (what `gsdd_amd.text.ClipTextTower.from_openai_state_dict` takes), prefix stripped, the visual tower (`visual.*`) and the
+    image-side scalars it alone uses left out.  None when the checkpoint carries none.  load_reference_checkpoint keeps dropping
+    `textencoder.*` as dead keys: the generator's own state does not depend on them."""
+    state = read_state(path_or_state)
+    text = ("token_embedding.", "positional_embedding", "transformer.", "ln_final.", "text_projection")
+    out = {}
+    for prefix in CLIP_TEXT_PREFIXES:
+        out.update({k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix) and k[len(prefix):].startswith(text)})
+    return out or None
+
+
 def load_reference_checkpoint(module, path_or_state, prefix="auto"):
     """Load into `module` (strictly, apart from the documented dead keys).  prefix: "generator." / "autoencoder." / None /
     "auto" (use the one prefix under which the module's keys are found).  Returns the list of dropped dead keys."""

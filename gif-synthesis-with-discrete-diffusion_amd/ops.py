@@ -473,6 +473,50 @@ def advance_plan(step_dev, plan_t, plan_n, t_dev, n_dev, stream_dev, ds, stream=
                                   ptr(stream_dev), ds, stream_ptr(stream)))
 
 
+# ----------------------------------------------------------------------------- CLIP text tower (text.py)
+def _host_ptr(t, what):
+    """Pointer of a HOST int64 tensor (the optional host copy the text entry points range-check before they launch); None -> NULL."""
+    if t is None:
+        return None
+    if t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
+        raise GsddError(f"{what} must be a contiguous int64 CPU tensor")
+    return C.c_void_p(t.data_ptr())
+
+
+def text_embed(ids, tok_emb, pos_emb, x, S, ids_host=None, stream=None):
+    """x[b*S + s] = tok_emb[ids[b][s]] + pos_emb[s], s < S (gsdd_text_embed).  ids: int64 (B, pitch >= S) on the device; ids_host: the
+    same matrix on the host, checked against the vocabulary before the launch."""
+    B, pitch = ids.shape
+    if ids.dtype != torch.int64:
+        raise GsddError(f"text_embed: ids must be int64, got {ids.dtype}")
+    if ids_host is not None and tuple(ids_host.shape) != (B, pitch):
+        raise GsddError(f"text_embed: ids_host has shape {tuple(ids_host.shape)}, ids {(B, pitch)}")
+    check(lib().gsdd_text_embed(ptr(ids), _host_ptr(ids_host, "ids_host"), B, S, pitch, tok_emb.shape[1], ptr(tok_emb), tok_emb.shape[0],
+                                ptr(pos_emb), pos_emb.shape[0], ptr(x), stream_ptr(stream)))
+    return x
+
+
+def text_attention(qkv, B, S, n_head, out, scale=None, stream=None):
+    """Causal self-attention over fused q|k|v rows [B*S][3C] -> out [B*S][C] (gsdd_text_attention); scale defaults to d^-0.5."""
+    C_ = qkv.shape[1] // 3
+    if qkv.shape[0] != B * S or qkv.shape[1] != 3 * C_ or tuple(out.shape) != (B * S, C_):
+        raise GsddError(f"text_attention: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
+    if scale is None:
+        scale = float(C_ // n_head) ** -0.5
+    check(lib().gsdd_text_attention(ptr(qkv), B, S, C_, n_head, scale, ptr(out), stream_ptr(stream)))
+    return out
+
+
+def text_pool(x, eot, B, S, out, eot_host=None, stream=None):
+    """out[b] = x[b*S + eot[b]] (gsdd_text_pool).  eot: int64 (B,) on the device; eot_host: its host copy, checked before the launch."""
+    if eot.dtype != torch.int64 or tuple(eot.shape) != (B,) or (eot_host is not None and tuple(eot_host.shape) != (B,)):
+        raise GsddError("text_pool: eot (and eot_host) must be int64 of shape (B,)")
+    if x.shape[0] != B * S or tuple(out.shape) != (B, x.shape[1]):
+        raise GsddError(f"text_pool: x {tuple(x.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
+    check(lib().gsdd_text_pool(ptr(x), ptr(eot), _host_ptr(eot_host, "eot_host"), B, S, x.shape[1], ptr(out), stream_ptr(stream)))
+    return out
+
+
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):
     out = torch.empty((n_rows, n_cols), dtype=torch.float32, device=device)
     check(lib().gsdd_philox_uniform(seed, stream_id, row0, n_rows, n_cols, ptr(out), stream_ptr()))

@@ -515,6 +515,27 @@ int gsdd_advance_plan(int64_t* step_dev, const int64_t* plan_t, const int64_t* p
 int gsdd_philox_uniform(uint64_t seed, int64_t stream_id, int64_t row0, int64_t n_rows, int n_cols,
                         float* out, void* stream);
 
+/* ------------------------------------------------------------------ CLIP text tower (text-conditioned sampling)
+ * The three pieces of clip.model.CLIP.encode_text (called by the reference at src/models/text_models/clip_text_embedding.py:56-65)
+ * that are not a gsdd_gemm / gsdd_row_stats call; gif-synthesis-with-discrete-diffusion_amd/text.py strings the tower together.
+ * `ids_host` / `eot_host` are the one exception to "every pointer is a device pointer": an optional HOST copy of the same integers
+ * (the tokenizer produces them on the host).  When given, every value is range-checked before anything is launched and an
+ * out-of-range one returns GSDD_E_ARG; without it (NULL) the kernels still never read out of range: the offending output row is
+ * NaN. */
+/* x[b][s][:] = tok_emb[ids[b][s]] + pos_emb[s] for s < S   (encode_text: token_embedding(text) + positional_embedding).
+ * ids: int64 [B][ids_pitch] (the first S of each row are used), tok_emb [vocab][C], pos_emb [n_pos][C], x rows [B*S][C];
+ * 1 <= S <= 77, S <= n_pos, C % 4 == 0. */
+int gsdd_text_embed(const int64_t* ids, const int64_t* ids_host, int B, int S, int ids_pitch, int C, const float* tok_emb, int vocab,
+                    const float* pos_emb, int n_pos, float* x, void* stream);
+/* Causal multi-head self-attention over fused rows qkv[B*S][3C] = (q | k | v), head h at columns h*d of each third, d = C / n_head
+ * in {64, 32, 16} (ViT-B/32's and ViT-L/14's towers have d = 64; the narrow ones serve small test towers); out rows [B*S][C] = softmax(scale q k^T + causal mask) v; 1 <= S <= 77.  Exact-f32 matrix instructions
+ * (v_mfma_f32_16x16x4_f32); key tiles above the diagonal are never computed.
+ * Replaces the nn.MultiheadAttention of every ResidualAttentionBlock under encode_text's build_attention_mask. */
+int gsdd_text_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
+/* out[b][:] = x[b*S + eot[b]][:]   (encode_text: x[arange(B), text.argmax(-1)]; the final LayerNorm is per row, so it and the
+ * projection then run on these B rows).  eot: int64 [B], each in [0, S). */
+int gsdd_text_pool(const float* x, const int64_t* eot, const int64_t* eot_host, int B, int S, int C, float* out, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */
 int gsdd_graph_begin(void* stream);

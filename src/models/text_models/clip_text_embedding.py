@@ -7,24 +7,34 @@ Neither the package nor the weights nor the BPE vocabulary exist offline, and th
 contract.  When a LOCAL copy of the text tower is supplied (`weights=<directory>` in the Hugging Face layout: config.json,
 model.safetensors, vocab.json, merges.txt of `openai/clip-vit-base-patch32`), the real tower runs instead, reproducing the reference's
 recipe: tokenise with context length 22 (start + 20 + end, truncated), zero-pad the ids to 77, take the projected feature at the end-of-text
-token (`clip_model.encode_text`, :56-64).  Nothing is ever fetched: the directory must exist.  **Parity unpinned**: no reference output of
-this tower can be produced in the build container; the plumbing (tokenisation recipe, padding, pooling position, frozen weights) is
-tested on a small randomly initialised tower of the same architecture (tests/test_host_logic.py).  It is off the hot path
-(frozen, one call per batch) and runs as plain PyTorch on whatever device the module lives on."""
+token (`clip_model.encode_text`, :56-64).  Nothing is ever fetched: the directory must exist.
+
+Where the tower runs: the Hugging Face module `self.clip_model` owns the weights.  On a CPU module it also computes (plain PyTorch, the
+path tests/test_host_logic.py checks).  On a GPU module the forward pass is `gsdd_amd.text.ClipTextTower`: the HIP kernels of libgsdd.so,
+fp32 (the reference runs the tower in fp16, `clip.model.convert_weights`), built lazily from `clip_model.state_dict()` and rebuilt
+after the module moves.  `native=None` (auto: native on a GPU, PyTorch on the CPU) | True (native; an error on a CPU module) | False
+(PyTorch wherever the module lives).  **Parity**: the native tower is pinned against the `transformers` implementation on a small
+seeded tower (tests/golden/clip_text_small.npz, tests/test_gpu_text_tower.py); it is NOT pinned against ViT-B/32 or against
+`clip.encode_text` itself, neither of which exists offline."""
 import hashlib
 import os
 
 import torch
 import torch.nn as nn
 
+from gsdd_amd import GsddError
+from gsdd_amd.text import ClipTextTower
+
 
 class CLIPTextEmbedding(nn.Module):
     MAX_TEXT_LEN = 20                  # :57 (the reference hard-codes HumanML's limit)
     CONTEXT_DEFAULT = 77               # :58
 
-    def __init__(self, clip_dim=512, weights=None, **kwargs):
+    def __init__(self, clip_dim=512, weights=None, native=None, **kwargs):
         super().__init__()
         self.clip_dim = clip_dim
+        self.native = native
+        self._tower = None                                         # ClipTextTower of the current device (not a sub-module)
         self.register_buffer("_anchor", torch.zeros(1))
         self.tokenizer, self.clip_model = None, None
         if weights:
@@ -56,9 +66,20 @@ class CLIPTextEmbedding(nn.Module):
             rows.append(ids + [0] * (self.CONTEXT_DEFAULT - len(ids)))
         return torch.tensor(rows, dtype=torch.int64)
 
+    def _native_tower(self, dev):
+        if self._tower is None or self._tower.device != dev:
+            cfg = self.clip_model.config
+            if cfg.hidden_act != "quick_gelu":
+                raise GsddError(f"the native text tower implements CLIP's QuickGELU, the supplied tower uses {cfg.hidden_act!r}: "
+                                "pass native=False to run it as PyTorch")
+            self._tower = ClipTextTower.from_hf_state_dict(self.clip_model.state_dict(), cfg.num_attention_heads,
+                                                           eps=cfg.layer_norm_eps).to(dev)
+        return self._tower
+
     @torch.no_grad()
-    def forward(self, texts, force_mask=False):
+    def forward(self, texts, force_mask=False, native=None):
         dev = self._anchor.device
+        native = self.native if native is None else native
         if self.clip_model is None:
             rows = []
             for t in texts:
@@ -67,6 +88,12 @@ class CLIPTextEmbedding(nn.Module):
                 v = torch.randn(self.clip_dim, generator=g)
                 rows.append(v / v.norm())
             return torch.stack(rows).to(dev)
+        if native and dev.type != "cuda":
+            raise GsddError("CLIPTextEmbedding(native=True): the native text tower needs the module on a GPU device (no CPU fallback)")
+        if native or (native is None and dev.type == "cuda"):
+            ids = self.tokenize(texts)                             # host ids: the end-of-text positions cost no device sync
+            eot = (ids == self.tokenizer.eos_token_id).int().argmax(dim=1)
+            return self._native_tower(dev)(ids, eot=eot)
         ids = self.tokenize(texts).to(dev)
         # encode_text: token + positional embedding, causal transformer, ln_final, the feature AT THE END-OF-TEXT TOKEN times the text
         # projection.  (The zero padding behind it is invisible to that position under the causal mask.)

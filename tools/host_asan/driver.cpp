@@ -285,6 +285,56 @@ int main() {
         EXPECT(gsdd_gemm(&g, st), GSDD_E_ARG, false);
     }
 
+    // ---------------------------------------------------------------- CLIP text tower: the host copies of ids / eot are read HERE
+    {
+        const int Bt = 64, S = 22, pitch = 77, C = 512, vocab = 49408, heads = 8;
+        int64_t* ids = devp<int64_t>();
+        int64_t* eot = devp<int64_t>();
+        float *tok = devp(), *pos = devp(), *x = devp(), *qkv = devp(), *att = devp(), *pooled = devp();
+        std::vector<int64_t> ids_h((size_t)Bt * pitch, 0), eot_h(Bt, S - 1);
+        for (int b = 0; b < Bt; ++b) { ids_h[(size_t)b * pitch] = vocab - 2; ids_h[(size_t)b * pitch + S - 1] = vocab - 1; }
+        EXPECT(gsdd_text_embed(ids, ids_h.data(), Bt, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_OK, true);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_OK, true);
+        EXPECT(gsdd_text_embed(ids, ids_h.data(), Bt, 77, pitch, C, tok, vocab, pos, 77, x, st), GSDD_OK, true);   // the last row's last id is read
+        ids_h[(size_t)(Bt - 1) * pitch + S - 1] = vocab;
+        EXPECT(gsdd_text_embed(ids, ids_h.data(), Bt, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, ids_h.data(), Bt, S - 1, pitch, C, tok, vocab, pos, 77, x, st), GSDD_OK, true);  // behind S: not looked at
+        ids_h[(size_t)(Bt - 1) * pitch + S - 1] = -1;
+        EXPECT(gsdd_text_embed(ids, ids_h.data(), Bt, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(nullptr, nullptr, Bt, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, pitch, C, nullptr, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, 78, 78, C, tok, vocab, pos, 78, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, S - 1, C, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, pitch, C, tok, vocab, pos, S - 1, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, pitch, 510, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, 0, S, pitch, C, tok, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_embed(ids, nullptr, Bt, S, pitch, C, tok + 1, vocab, pos, 77, x, st), GSDD_E_ARG, false);
+
+        for (int s : {1, 16, 17, 77}) EXPECT(gsdd_text_attention(qkv, Bt, s, C, heads, 0.125f, att, st), GSDD_OK, true);
+        EXPECT(gsdd_text_attention(qkv, Bt, S, 64, 2, 0.1767767f, att, st), GSDD_OK, true);                  // d = 32
+        EXPECT(gsdd_text_attention(qkv, Bt, S, 32, 2, 0.25f, att, st), GSDD_OK, true);                       // d = 16
+        EXPECT(gsdd_text_attention(qkv, Bt, 78, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, Bt, 0, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, Bt, S, C, 3, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, Bt, S, C, 4, 0.125f, att, st), GSDD_E_ARG, false);                   // d = 128
+        EXPECT(gsdd_text_attention(qkv, Bt, S, C, 0, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, Bt, S, C, heads, 0.f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(nullptr, Bt, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, Bt, S, C, heads, 0.125f, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_attention(qkv, 1 << 29, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);          // grid beyond 2^31
+
+        EXPECT(gsdd_text_pool(x, eot, eot_h.data(), Bt, S, C, pooled, st), GSDD_OK, true);
+        EXPECT(gsdd_text_pool(x, eot, nullptr, Bt, S, C, pooled, st), GSDD_OK, true);
+        eot_h[Bt - 1] = S;
+        EXPECT(gsdd_text_pool(x, eot, eot_h.data(), Bt, S, C, pooled, st), GSDD_E_ARG, false);
+        eot_h[Bt - 1] = -1;
+        EXPECT(gsdd_text_pool(x, eot, eot_h.data(), Bt, S, C, pooled, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_pool(x, nullptr, nullptr, Bt, S, C, pooled, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_pool(nullptr, eot, nullptr, Bt, S, C, pooled, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_pool(x, eot, nullptr, Bt, 78, C, pooled, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_text_pool(x, eot, nullptr, Bt, S, 6, pooled, st), GSDD_E_ARG, false);
+    }
+
     // ---------------------------------------------------------------- graph capture misuse, events
     {
         void* exec = nullptr;
