@@ -162,12 +162,19 @@ __device__ __forceinline__ void kv_image_store_v(const float (&vs)[4], int64_t r
 // attention kernel adds the tiles of a (b, h) to the mean key, which gives it a lower bound of every FINAL row sum before it has seen a
 // key (Jensen: log2 sum_j 2^s_j >= log2 L + mean_j s_j = log2 L + q . kmean).
 // Workspace layout (gsdd_d3pm_attention_workspace_bytes): K image 32 B per (key, head) | V image 32 B | ksum 16 B per 32 keys | knorm 4 B
-// per 32 keys.
+// per 32 keys | (32-byte aligned) kstat 32 B per (batch row, head): what the adaptive attention kernels need of a whole (b, h) --
+// {sum of its keys}, {largest tile norm, inf / NaN flag, 0, 0} -- reduced from ksum / knorm by d3pm_attn_stats_kernel ahead of them.
 __host__ __device__ __forceinline__ float4* kv_image_ksum(void* workspace, int64_t rows) {
     return reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + rows * 64);
 }
 __host__ __device__ __forceinline__ float* kv_image_knorm(void* workspace, int64_t rows) {
     return reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + rows * 64 + ((rows + 31) / 32) * 16);
+}
+__host__ __device__ __forceinline__ int64_t kv_image_kstat_offset(int64_t rows) {
+    return (rows * 64 + ((rows + 31) / 32) * 20 + 31) & ~(int64_t)31;
+}
+__host__ __device__ __forceinline__ float4* kv_image_kstat(void* workspace, int64_t rows) {
+    return reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kv_image_kstat_offset(rows));
 }
 template <int CTRL>
 __device__ __forceinline__ float dpp_max(float v) {

@@ -390,6 +390,37 @@ __global__ __launch_bounds__(256) void d3pm_attn_prep_kernel(const float* __rest
     }
 }
 
+// PM >= 2: the statistics of one (b, h) that every one of its query blocks needs before it can decide anything -- the largest tile norm,
+// whether a tile norm is inf or NaN (fmaxf drops a NaN: the maximum alone would not show it) and the sum of all keys -- reduced once
+// per (b, h) by one wave instead of once per workgroup (16 query blocks per (b, h) at L = 4096).  The lane assignment, the order of
+// the per-lane loop and the reduction trees are the ones wave 0 of every attention workgroup used to run, so the numbers have the same
+// bits.  Record (b, h) = 2 float4 at kstat[2 (h B + b)]: {ks.x, ks.y, ks.z, ks.w}, {knm, odd flag (bits 0 / 1), 0, 0}.
+__global__ __launch_bounds__(64) void d3pm_attn_stats_kernel(const float* __restrict__ knorm, const float4* __restrict__ ksum, int B,
+                                                            int L, float4* __restrict__ kstat) {
+    const int lane = threadIdx.x;
+    const int h = blockIdx.x / B, b = blockIdx.x % B;
+    const int64_t tile0 = ((int64_t)h * B * L + (int64_t)b * L) >> 5;
+    const float* knh = knorm + tile0;
+    const float4* ksh = ksum + tile0;
+    float knm = 0.f;
+    float4 ks = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool kn_odd = false;
+    for (int i = lane; i < (L >> 5); i += 64) {
+        const float n = knh[i];
+        knm = fmaxf(knm, n);
+        kn_odd = kn_odd || !(n < 3.0e38f);
+        const float4 t = ksh[i];
+        ks.x += t.x; ks.y += t.y; ks.z += t.z; ks.w += t.w;
+    }
+    knm = wave_max(knm);
+    ks.x = wave_sum(ks.x); ks.y = wave_sum(ks.y); ks.z = wave_sum(ks.z); ks.w = wave_sum(ks.w);
+    const bool odd = __any(kn_odd);
+    if (lane == 0) {
+        kstat[2 * (int64_t)blockIdx.x] = ks;
+        kstat[2 * (int64_t)blockIdx.x + 1] = make_float4(knm, __uint_as_float(odd ? 1u : 0u), 0.f, 0.f);
+    }
+}
+
 // One pass over the pair-tiles of a staged chunk for the wave's 4 x 16 queries.  MODE 1: P = hi + lo; 0: hi only; 2: hi, and lo only
 // where a tile holds a probability above the lane's threshold thr2 (see the kernel's note) -- returns the number of (pair-tile,
 // query sub-tile) pairs that skipped the lo half.  (Deciding once per pair-tile for the four sub-tiles together, with the rare path
@@ -465,7 +496,7 @@ __device__ __forceinline__ int attn_tiles(const AttnSmem4<KC4>& sm, int buf, int
 template <int KC4, int PM = 1>
 __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __restrict__ q, const uint4* __restrict__ kp,
                                                                 const uint4* __restrict__ vp, const float* __restrict__ knorm,
-                                                                const float4* __restrict__ ksum, int B, int L, int H,
+                                                                const float4* __restrict__ kstat, int B, int L, int H,
                                                                 float* __restrict__ out,
                                                                 float* __restrict__ lse, unsigned long long* __restrict__ redo, int lean) {
     __shared__ AttnSmem4<KC4> sm;
@@ -485,55 +516,38 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     const uint4* kph = kp + ((int64_t)h * M + (int64_t)b * L) * 2;        // 2 uint4 per key
     const uint4* vph = vp + (((int64_t)h * M + (int64_t)b * L) >> 5) * 64; // 64 uint4 per 32-key pair-tile
     const float* knh = knorm + (((int64_t)h * M + (int64_t)b * L) >> 5);   // one float per 32-key pair-tile
-    const float4* ksh = ksum + (((int64_t)h * M + (int64_t)b * L) >> 5);  // one float4 per 32-key pair-tile
     const int li = lane & 15, lg = lane >> 4;
     const int q0 = qblk * 256 + wave * 64;
 
-    // PM >= 2: the tile norms and key sums of this (b, h), requested first so that their latency hides behind the q splits and the
-    // first chunk's loads.  They are the same numbers in every wave of the workgroup: wave 0 reduces them and hands them to the others
-    // through two unused entries of sm.ones, ahead of the barrier that follows the first chunk's staging.
-    float knm = 0.f;
-    float4 ks = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool kn_odd = false;                        // some tile norm is inf or NaN (fmaxf drops a NaN: knm alone would not show it)
-    if (PM >= 2 && wave == 0) {
-        for (int i = lane; i < (L >> 5); i += 64) {
-            const float n = knh[i];
-            knm = fmaxf(knm, n);
-            kn_odd = kn_odd || !(n < 3.0e38f);
-            const float4 t = ksh[i];
-            ks.x += t.x; ks.y += t.y; ks.z += t.z; ks.w += t.w;
-        }
-    }
-
-    if (tid < 16) sm.ones[tid] = (tid == 0 || tid == 1) ? make_uint4(0x3F803F80u, 0x00003F80u, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-
+    // PM >= 2: the statistics record of this (b, h) (d3pm_attn_stats_kernel) and the lane's own query row, requested first.  The
+    // record's address is the same for the whole workgroup: two scalar loads, no vector instruction and no hand-over between waves.
     const float qscale = 0.5f * 1.4426950408889634f;
-    uint4 qfrag[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qi = q0 + 16 * j + li;
-        qi = qi < L ? qi : L - 1;
-        const float4 qv = *reinterpret_cast<const float4*>(qh + (int64_t)qi * 4);
-        const float qs[4] = {qv.x * qscale, qv.y * qscale, qv.z * qscale, qv.w * qscale};
-        uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) split3(qs[d], q1[d], q2[d], q3[d]);
-        const uint4 f0 = pack8(q1, q1), f1 = pack8(q2, q2), f2 = pack8(q1, q3);
-        qfrag[j] = lg == 0 ? f0 : (lg == 1 ? f1 : (lg == 2 ? f2 : make_uint4(0u, 0u, 0u, 0u)));
-    }
-    // PM >= 2: the bound numbers belong to a query, not to a fragment: lane l computes those of query q0 + l (= sub-tile lg, row li) once,
-    // where the fragment layout above would have the four lanes (li, 0..3) each evaluate the same four queries.
-    float qno = 0.f;                            // ||q'|| of the lane's own query, rounded up
-    float rqno = 0.f;                           // 1 / that: the score bound's slope
-    float4 qso = make_float4(0.f, 0.f, 0.f, 0.f);   // its q' (log2 domain), for the row-sum lower bound
+    float knm = 0.f;                            // largest tile norm of the (b, h), rounded up
+    float4 ks = make_float4(0.f, 0.f, 0.f, 0.f);   // sum of its keys
+    uint32_t kn_odd = 0u;                       // some tile norm is inf or NaN
+    float4 qso = make_float4(0.f, 0.f, 0.f, 0.f);   // the lane's own q' (log2 domain): query q0 + lane = sub-tile lg, row li
     if (PM >= 2) {
+        const float4* st = kstat + 2 * ((int64_t)h * B + b);
+        const float4 s1 = st[1];
+        ks = st[0];
+        knm = s1.x * 1.0001f;
+        kn_odd = __float_as_uint(s1.y);
         int qi = q0 + lane;
         qi = qi < L ? qi : L - 1;
         const float4 qv = *reinterpret_cast<const float4*>(qh + (int64_t)qi * 4);
         qso = make_float4(qv.x * qscale, qv.y * qscale, qv.z * qscale, qv.w * qscale);
-        // 1.0001: the split products, the norms' own rounding and v_rcp/v_log/v_sqrt (1 ulp each) are all below 2^-20 relative
-        qno = sqrtf((qso.x * qso.x + qso.y * qso.y) + (qso.z * qso.z + qso.w * qso.w)) * 1.0001f + 1e-30f;
-        rqno = 1.0f / qno;
+    }
+
+    if (tid < 16) sm.ones[tid] = (tid == 0 || tid == 1) ? make_uint4(0x3F803F80u, 0x00003F80u, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
+
+    // (the four rows are requested together and the first chunk right behind them; the splits follow those requests, so one load
+    // latency runs ahead of all the prologue's arithmetic instead of one ahead of each split and another ahead of the staging)
+    float4 qrow[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int qi = q0 + 16 * j + li;
+        qi = qi < L ? qi : L - 1;
+        qrow[j] = *reinterpret_cast<const float4*>(qh + (int64_t)qi * 4);
     }
 
     const int nchunks = (L + KC4 - 1) / KC4;
@@ -580,15 +594,55 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
     load_chunk(0, true);
-    if (PM >= 2 && wave == 0) {
-        // (after the sm.ones initialisation above: the same wave, and a wave's LDS writes land in program order)
-        knm = wave_max(knm);
-        ks.x = wave_sum(ks.x); ks.y = wave_sum(ks.y); ks.z = wave_sum(ks.z); ks.w = wave_sum(ks.w);
-        const bool odd = __any(kn_odd);
-        if (lane == 0) {
-            sm.ones[2] = make_uint4(__float_as_uint(ks.x), __float_as_uint(ks.y), __float_as_uint(ks.z), __float_as_uint(ks.w));
-            sm.ones[3] = make_uint4(__float_as_uint(knm), odd ? 1u : 0u, 0u, 0u);
-        }
+    uint4 qfrag[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 qv = qrow[j];
+        const float qs[4] = {qv.x * qscale, qv.y * qscale, qv.z * qscale, qv.w * qscale};
+        uint32_t q1[4], q2[4], q3[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) split3(qs[d], q1[d], q2[d], q3[d]);
+        const uint4 f0 = pack8(q1, q1), f1 = pack8(q2, q2), f2 = pack8(q1, q3);
+        qfrag[j] = lg == 0 ? f0 : (lg == 1 ? f1 : (lg == 2 ? f2 : make_uint4(0u, 0u, 0u, 0u)));
+    }
+    // PM >= 2: the bound numbers, while the first chunk's loads are in flight.  They belong to a query, not to a fragment: lane l
+    // computes those of query q0 + l (= sub-tile lg, row li) once, where the fragment layout above would have the four lanes
+    // (li, 0..3) each evaluate the same four queries.  Everything here depends on the lane's q row and the (b, h) record only, so its
+    // IEEE square root, divide and logarithms run ahead of the first barrier instead of after the first-keys maximum.
+    float qno = 0.f;                            // ||q'|| of the lane's own query, rounded up
+    float rqno = 0.f;                           // 1 / that: the score bound's slope
+    float jbo = -INFINITY;                      // log2 of a lower bound of the FINAL row sum of the lane's own query (absolute scale)
+    float kmin = 0.f;                           // the smallest per-query bound number of the lane's sub-tile
+    float kbj[4] = {0.f, 0.f, 0.f, 0.f};        // the bound's per-sub-tile numbers (wave-uniform values); 0 = clears nothing
+    if (PM >= 2) {
+        // 1.0001: the split products, the norms' own rounding and v_rcp/v_log/v_sqrt (1 ulp each) are all below 2^-20 relative
+        qno = sqrtf((qso.x * qso.x + qso.y * qso.y) + (qso.z * qso.z + qso.w * qso.w)) * 1.0001f + 1e-30f;
+        rqno = 1.0f / qno;
+        // A priori form of the bound, before any key has been seen: the FINAL row sum of query q is at least L * 2^(-||q'|| KNmax - m)
+        // (every score is at least -||q'|| ||k||; KNmax = the largest tile norm of this (b, h)), and the error budget is relative to the
+        // final row sum, so a tile whose probabilities stay below 2^-PM of that lower bound may take the hi half only:
+        //     ||q'|| knorm[u] - m < log2(L) - PM - ||q'|| KNmax - m   <=>   knorm[u] < (log2(L) - PM - slack) / ||q'|| - KNmax.
+        // With near-flat rows (||q'|| ||k|| << log2(L) - PM = 4 at L = 4096) this clears every tile of every chunk, the first included,
+        // and the running-sum form below never has to be computed.
+        const float budget = log2f((float)L) - (float)PM - 0.02f;
+        // Sharper, and per query: Jensen -- log2 sum_j 2^(q'.k_j) >= log2(L) + q'.kmean, kmean from the per-tile key sums the K image's
+        // producer left next to the tile norms (fixed summation order: the same bits in every workgroup and every run).  It is within
+        // sigma^2 / 2 nats of the true log row sum for scores of spread sigma, where the bound above is off by ||q'|| (KNmax + ||kmean||).
+        // It replaces the a priori row sum in the tile bound, and it gives the measured test a threshold relative to the FINAL row sum from
+        // the first chunk on (the running sum after one chunk of eleven is 3.5 bits short of it, which made early chunks of rows that are
+        // nowhere near peaked take the lo half: trained-like weights, DESIGN.md section 4).
+        const float invL = 1.0f / (float)L;
+        const float dx = qso.x * ks.x, dy = qso.y * ks.y, dz = qso.z * ks.z, dw = qso.w * ks.w;
+        const float mean = ((dx + dy) + (dz + dw)) * invL, mag = ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw))) * invL;
+        jbo = log2f((float)L) + mean - 1e-5f * mag - 0.02f;             // slack: the float sums behind kmean and the dot product
+        // (a query with a NaN in it has a NaN output row whatever its tiles do: it must not take the lo-half decision away from
+        // the fifteen queries that share its sub-tile, so it drops out of the minimum)
+        const float kbq0 = fmaxf(fmaxf(budget * rqno - knm, (jbo - (float)PM) * rqno), 0.f);
+        // DPP row j holds the 16 queries of sub-tile j: its minimum, read out of the row's first lane into a scalar register
+        kmin = row16_min(qno != qno ? INFINITY : kbq0);
+        asm volatile("" : "+v"(kmin));          // pinned here: hipcc otherwise sinks the whole chain below the barrier, behind its first use
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kbj[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kmin), 16 * j));
     }
     store_chunk(0, 0);
     __syncthreads();
@@ -629,52 +683,21 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
     // that a chunk runs the adaptive loop, and if fewer than half of its tiles could skip the lo half the wave goes back to the plain
     // hi + lo loop (no per-tile test, one basic block per pair-tile) and probes again later, each time twice as much later (a row
     // that was not flat after 384 keys seldom becomes flat): chunks 1, 6, 15, 32, ...
-    bool adapt = PM >= 2;                       // (the row-sum lower bound below gives the first chunk a threshold too)
+    bool adapt = PM >= 2;                       // (the row-sum lower bound gives the first chunk a threshold too)
     int probe = 1, backoff = 4;
-    float jbo = -INFINITY;                      // log2 of a lower bound of the FINAL row sum of the lane's own query (absolute scale)
-    float kbj[4] = {0.f, 0.f, 0.f, 0.f};        // the bound's per-sub-tile numbers (wave-uniform values); 0 = clears nothing
-    int kb_next = 1, kb_gap = 1;                // chunk of the next recomputation, and the gap after it
-    if (PM >= 2) {
-        // A priori form of the bound, before any key has been seen: the FINAL row sum of query q is at least L * 2^(-||q'|| KNmax - m)
-        // (every score is at least -||q'|| ||k||; KNmax = the largest tile norm of this (b, h)), and the error budget is relative to the
-        // final row sum, so a tile whose probabilities stay below 2^-PM of that lower bound may take the hi half only:
-        //     ||q'|| knorm[u] - m < log2(L) - PM - ||q'|| KNmax - m   <=>   knorm[u] < (log2(L) - PM - slack) / ||q'|| - KNmax.
-        // With near-flat rows (||q'|| ||k|| << log2(L) - PM = 4 at L = 4096) this clears every tile of every chunk, the first included,
-        // and the running-sum form below never has to be computed.
-        const uint4 shk = sm.ones[2], shn = sm.ones[3];             // wave 0's reductions (the same bits each wave used to compute)
-        knm = __uint_as_float(shn.x) * 1.0001f;
-        ks = make_float4(__uint_as_float(shk.x), __uint_as_float(shk.y), __uint_as_float(shk.z), __uint_as_float(shk.w));
-        const float budget = log2f((float)L) - (float)PM - 0.02f;
-        // Sharper, and per query: Jensen -- log2 sum_j 2^(q'.k_j) >= log2(L) + q'.kmean, kmean from the per-tile key sums the K image's
-        // producer left next to the tile norms (fixed summation order: the same bits in every workgroup and every run).  It is within
-        // sigma^2 / 2 nats of the true log row sum for scores of spread sigma, where the bound above is off by ||q'|| (KNmax + ||kmean||).
-        // It replaces the a priori row sum in the tile bound, and it gives the measured test a threshold relative to the FINAL row sum from
-        // the first chunk on (the running sum after one chunk of eleven is 3.5 bits short of it, which made early chunks of rows that are
-        // nowhere near peaked take the lo half: trained-like weights, DESIGN.md section 4).
-        const float invL = 1.0f / (float)L;
-        const float dx = qso.x * ks.x, dy = qso.y * ks.y, dz = qso.z * ks.z, dw = qso.w * ks.w;
-        const float mean = ((dx + dy) + (dz + dw)) * invL, mag = ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw))) * invL;
-        jbo = log2f((float)L) + mean - 1e-5f * mag - 0.02f;             // slack: the float sums behind kmean and the dot product
-        // (a query with a NaN in it has a NaN output row whatever its tiles do: it must not take the lo-half decision away from
-        // the fifteen queries that share its sub-tile, so it drops out of the minimum)
-        const float kbq0 = fmaxf(fmaxf(budget * rqno - knm, (jbo - (float)PM) * rqno), 0.f);
-        // DPP row j holds the 16 queries of sub-tile j: its minimum, read out of the row's first lane into a scalar register
-        const float kmin = row16_min(qno != qno ? INFINITY : kbq0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) kbj[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kmin), 16 * j));
+    int kb_next = 1, kb_gap = 1;                // chunk of the next recomputation of kbj, and the gap after it
+    if (PM >= 2 && lean != 0) {
         // A "quiet" wave (wave-uniform, decided once): nothing the general loop's bookkeeping guards against can happen in any chunk.
         //  (a) every tile of the (b, h) is cleared: knm bounds every tile norm from above and the kbj in hand only ever grow, so each
         //      chunk's masks would come out all ones and each chunk would run the hi-only loop;
         //  (b) no probability gets near the f16 overflow the screen looks for: every score of query q is at most ||q'|| KNmax
         //      (Cauchy-Schwarz, the 1.0001 factors cover the roundings), so 2^(s - m) <= 2^15: a full octave below 2^16, and the f32
         //      accumulators cannot overflow on f16-range products either.  No overflow: no redo, and the offsets m never move.
-        // Both compares are false for a NaN, and an inf or NaN among the tile norms is flagged by wave 0: such waves stay general.
-        if (lean != 0) {
-            // (per query: the lane's own row minimum and the offset of its own query, mq[lg]; all 64 lanes = all four sub-tiles)
-            const float mqo = lg == 0 ? mq[0] : (lg == 1 ? mq[1] : (lg == 2 ? mq[2] : mq[3]));
-            const bool ok = shn.y == 0u && (knm < kmin) && (qno * knm - mqo <= 15.f);
-            quiet = __all(ok);
-        }
+        // Both compares are false for a NaN, and an inf or NaN among the tile norms is flagged in the record: such waves stay general.
+        // (per query: the lane's own row minimum and the offset of its own query, mq[lg]; all 64 lanes = all four sub-tiles)
+        const float mqo = lg == 0 ? mq[0] : (lg == 1 ? mq[1] : (lg == 2 ? mq[2] : mq[3]));
+        const bool ok = kn_odd == 0u && (knm < kmin) && (qno * knm - mqo <= 15.f);
+        quiet = __all(ok);
     }
     if (PM >= 2 && quiet) {
         // The lean chunk loop: the tile sequence of the general loop's cleared chunks (the same MFMAs in the same order, hence the same
@@ -937,7 +960,9 @@ static int attn_p_mode(int mode, int L) {
 
 extern "C" int64_t gsdd_d3pm_attention_workspace_bytes(int B, int L, int H) {
     const int64_t rows = (int64_t)B * L * H;
-    return rows * 64 + ((rows + 31) / 32) * 20;  // 32 B (K pieces) + 32 B (V image) per key and head; a key sum (16 B) and a norm bound (4 B) per 32 keys
+    // 32 B (K pieces) + 32 B (V image) per key and head; a key sum (16 B) and a norm bound (4 B) per 32 keys; then, 32-byte aligned,
+    // the statistics record of every (b, h) (32 B: d3pm_attn_stats_kernel)
+    return kv_image_kstat_offset(rows) + (int64_t)B * H * 32;
 }
 
 int gsdd_attention_valu(const float* q, const float* k, const float* v, int B, int L, int H, float* out, float* lse,
@@ -964,6 +989,7 @@ extern "C" int gsdd_d3pm_attention(const float* q, const float* k, const float* 
         uint4* vp = kp + rows * 2;
         float* kn = kv_image_knorm(workspace, rows);
         float4* ksm = kv_image_ksum(workspace, rows);
+        float4* kst = kv_image_kstat(workspace, rows);
         unsigned long long* redo = reinterpret_cast<unsigned long long*>(redo_events);
         if (!premade) {
             hipLaunchKernelGGL(d3pm_attn_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, k, v, rows, kp, vp, kn, ksm);
@@ -972,11 +998,15 @@ extern "C" int gsdd_d3pm_attention(const float* q, const float* k, const float* 
         const bool kc256 = mode == GSDD_ATTN_KC256;          // development variant: 256-key chunks, hi + lo everywhere
         const int pmode = attn_p_mode(mode, L);
         float* nolse = nullptr;
-        if (kc256) hipLaunchKernelGGL(d3pm_attention_v4_kernel<256>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
-        else if (pmode == 0) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 0>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
-        else if (pmode == 8) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
-        else if (pmode == 12) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 12>), grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
-        else hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, grid, dim3(256), 0, st, q, kp, vp, kn, ksm, B, L, H, out, nolse, redo, lean);
+        if (!kc256 && pmode >= 2) {           // the adaptive kernels read the (b, h) statistics; the others never look at them
+            hipLaunchKernelGGL(d3pm_attn_stats_kernel, dim3((unsigned)(B * H)), dim3(64), 0, st, kn, ksm, B, L, kst);
+            GSDD_CHECK_LAUNCH();
+        }
+        if (kc256) hipLaunchKernelGGL(d3pm_attention_v4_kernel<256>, grid, dim3(256), 0, st, q, kp, vp, kn, kst, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 0) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 0>), grid, dim3(256), 0, st, q, kp, vp, kn, kst, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 8) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), grid, dim3(256), 0, st, q, kp, vp, kn, kst, B, L, H, out, nolse, redo, lean);
+        else if (pmode == 12) hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 12>), grid, dim3(256), 0, st, q, kp, vp, kn, kst, B, L, H, out, nolse, redo, lean);
+        else hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, grid, dim3(256), 0, st, q, kp, vp, kn, kst, B, L, H, out, nolse, redo, lean);
     } else {
         hipLaunchKernelGGL(d3pm_attention_kernel, grid, dim3(256), 0, st, q, k, v, B, L, H, out);      // (never redoes a chunk)
     }
@@ -1002,6 +1032,7 @@ int gsdd_attention_v4_with_lse(const float* q, const float* k, const float* v, i
     uint4* vp = kp + rows * 2;
     float* kn = kv_image_knorm(workspace, rows);
     float4* ksm = kv_image_ksum(workspace, rows);
+    float4* kst = kv_image_kstat(workspace, rows);
     unsigned long long* noredo = nullptr;
     hipLaunchKernelGGL(d3pm_attn_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, k, v, rows, kp, vp, kn, ksm);
     GSDD_CHECK_LAUNCH();
@@ -1009,12 +1040,15 @@ int gsdd_attention_v4_with_lse(const float* q, const float* k, const float* v, i
     // priori): its output error <= 2e-5 of the row scale is below what the gradient parity tests resolve (full-size gradient parity and
     // the 2e-5 attention-backward bar pass unchanged) and the step is 3.2 ms shorter (64.6 -> 61.4 ms).  mode GSDD_ATTN_P22: hi + lo
     // everywhere, the round-2 behaviour; GSDD_ATTN_A8: adaptive at any L.
-    if (mode == GSDD_ATTN_A8 || (mode == GSDD_ATTN_AUTO && L >= 2048))
-        hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, ksm,
+    if (mode == GSDD_ATTN_A8 || (mode == GSDD_ATTN_AUTO && L >= 2048)) {
+        hipLaunchKernelGGL(d3pm_attn_stats_kernel, dim3((unsigned)(B * H)), dim3(64), 0, st, kn, ksm, B, L, kst);
+        GSDD_CHECK_LAUNCH();
+        hipLaunchKernelGGL((d3pm_attention_v4_kernel<384, 8>), dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, kst,
                            B, L, H, out, lse, noredo, lean);
-    else
-        hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, ksm,
+    } else {
+        hipLaunchKernelGGL(d3pm_attention_v4_kernel<384>, dim3((unsigned)(B * H * ((L + 255) / 256))), dim3(256), 0, st, q, kp, vp, kn, kst,
                            B, L, H, out, lse, noredo, lean);
+    }
     GSDD_CHECK_LAUNCH();
     *done = 1;
     return GSDD_OK;

@@ -191,8 +191,11 @@ int gsdd_small_linear(const float* x, int R, int Cin, const float* w, const floa
  * (32 B per key and head), the V image (32 B) and, per (head, 32-key pair-tile), the sum of the tile's keys (float4) and one f32
  * bounding the tile's largest ||k||.  The norms let the kernel prove from ||q|| ||k|| alone that a tile holds no probability above
  * 2^-8 of its row sum (then only the f16 hi half of P is used for it); the sums give it the mean key, hence a lower bound of every
- * final row sum before a key has been seen.  NULL selects the workspace-free kernel (exact-f32 P.V on
- * v_mfma_f32_4x4x1). */
+ * final row sum before a key has been seen.  Behind them, 32-byte aligned, 32 B per (batch row, head): the
+ * sum of all its keys (float4), its largest tile norm, an inf / NaN flag and two zero words -- what the adaptive kernels need of a
+ * whole (b, h), reduced from the per-tile numbers by one small launch ahead of them (they read nothing else of the kind; the other
+ * modes never touch these bytes).  Layout: K image | V image | key sums | tile norms | (b, h) records.  NULL selects the
+ * workspace-free kernel (exact-f32 P.V on v_mfma_f32_4x4x1). */
 int64_t gsdd_d3pm_attention_workspace_bytes(int B, int L, int H);
 /* k = v = NULL: the workspace already holds the images, key sums and norms (written by gsdd_d3pm_layer through kv_img).
  * redo_events: optional device counter (caller-owned, caller-zeroed) to which the kernel adds one per (wave, chunk) it had to

@@ -3,9 +3,10 @@
 Cross-compiles d3pm_attention.hip to assembly with build.sh's flags (no GPU needed), from the working tree and, with --rev, from a git
 revision, then walks the listing along the path of a QUIET wave of a long row (L >= 768, a chunk in the middle of the row, lean loop,
 no log-sum-exp) and counts v_* instructions and s_nop per part:
-  prologue    entry .. first barrier: q splits, the lane's own query numbers, first chunk's staging
+  prologue    entry .. first barrier: q splits, first chunk's staging, and (since the (b, h) statistics kernel) the lane's own query
+              numbers, the Jensen bound and the row minima
   first_keys  .. the fourth v_ceil_f32: the offsets m from the first 64 keys (a rolled loop is walked four times)
-  bounds      .. the chunk loop's header: Jensen bound, row minima, quiet decision
+  bounds      .. the chunk loop's header: the quiet decision (before that kernel: also the Jensen bound and the row minima)
   loop        one pass through the chunk loop with ONE pair-tile iteration (loop bodies are walked once)
   epilogue    after the chunk loop's barrier: merge, divide, store
 Branches on exec are decided by rule (execz falls through, execnz is taken, back edges are not taken); every forward branch on scc / vcc
@@ -28,7 +29,12 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form",
          "-Wno-unused-function", "-w"]
 FILES = [f"{PKG}/csrc/d3pm_attention.hip", f"{PKG}/csrc/common.hpp", "include/gsdd.h"]
-PARENT_DECISIONS = "NTNNNNNNNNTNNTT"       # the commit before the per-query prologue (git revision given with --rev)
+# Decision strings by build.  --rev-decisions defaults to the one of the commit right before the (b, h) statistics kernel (what
+# profiles/rF_attn_census.csv was made against); any other revision needs its own string on the command line: the one of the commit
+# before the per-query prologue, against which profiles/rB_attn_census.csv was made, is BEFORE_PER_QUERY_PROLOGUE.  A wrong string does
+# not fail, it walks another path: check the part counts of a known build first.
+BEFORE_PER_QUERY_PROLOGUE = "NTNNNNNNNNTNNTT"
+PARENT_DECISIONS = "NTTTTTNNNNTNNTT"
 THIS_DECISIONS = "NTTTTTNNNNTNNTT"
 PARTS = ["prologue", "first_keys", "bounds", "loop", "epilogue"]
 
@@ -107,7 +113,8 @@ def census(lines, decisions):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rev", default=None, help="also count this git revision (the parent build)")
-    ap.add_argument("--rev-decisions", default=PARENT_DECISIONS)
+    ap.add_argument("--rev-decisions", default=PARENT_DECISIONS,
+                    help="branch decisions of --rev; the default fits only the commit right before the (b, h) statistics kernel")
     ap.add_argument("--decisions", default=THIS_DECISIONS)
     ap.add_argument("--kernel", default="ILi384ELi8E", help="mangled template arguments of the instantiation")
     ap.add_argument("out", nargs="?", default="-")
