@@ -18,7 +18,7 @@ EXPORTS = [
     "gsdd_d3pm_attention", "gsdd_d3pm_attention_workspace_bytes", "gsdd_d3pm_layer", "gsdd_d3pm_layer_pack", "gsdd_d3pm_layer_pack_h2", "gsdd_rows_linear_pack_many", "gsdd_rows_linear", "gsdd_d3pm_logits", "gsdd_d3pm_cross_attention", "gsdd_d3pm_step", "gsdd_d3pm_q_sample", "gsdd_d3pm_train_loss", "gsdd_d3pm_train_loss_bwd", "gsdd_d3pm_train_loss_grad", "gsdd_gelu2", "gsdd_ln_fwd", "gsdd_ln_bwd", "gsdd_wgrad",
     "gsdd_batch_rowsum", "gsdd_colsum", "gsdd_d3pm_attention_train", "gsdd_d3pm_attention_bwd", "gsdd_d3pm_attention_bwd_workspace_bytes", "gsdd_d3pm_embed_bwd", "gsdd_small_linear_bwd",
     "gsdd_adaln_bwd", "gsdd_adam", "gsdd_adam_multi", "gsdd_adam_multi_dev", "gsdd_advance", "gsdd_advance_floor",
-    "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan",
+    "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan", "gsdd_d3pm_forward_jump",
     "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
@@ -71,6 +71,13 @@ class PuritySelectDesc(C.Structure):
     ]
 
 
+class JumpDesc(C.Structure):
+    _fields_ = [
+        ("tok_in", _p), ("tok_out", _p), ("B", _i), ("L", _i), ("K", _i), ("T", _i), ("table", _p), ("jump", _i),
+        ("t_dev", _p), ("hold", _p), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
+    ]
+
+
 class TrainDesc(C.Structure):
     _fields_ = [
         ("logits", _p), ("x0", _p), ("xt", _p), ("t_dev", _p), ("pt", _p),
@@ -116,9 +123,9 @@ def lib():
         if not hasattr(L, "gsdd_abi_sizeof"):
             raise GsddError(f"{LIB_PATH} predates this binding (no gsdd_abi_sizeof): rebuild it with ./build.sh")
         L.gsdd_abi_sizeof.argtypes, L.gsdd_abi_sizeof.restype = [_i], _i64
-        for which, (name, cls) in enumerate((("gsdd_gemm_desc", GemmDesc), ("gsdd_layer_desc", LayerDesc), ("gsdd_step_desc", StepDesc),
-                                             ("gsdd_train_desc", TrainDesc), ("gsdd_purity_desc", PurityDesc),
-                                             ("gsdd_purity_select_desc", PuritySelectDesc))):
+        for which, name, cls in ((0, "gsdd_gemm_desc", GemmDesc), (1, "gsdd_layer_desc", LayerDesc), (2, "gsdd_step_desc", StepDesc),
+                                 (3, "gsdd_train_desc", TrainDesc), (4, "gsdd_purity_desc", PurityDesc),
+                                 (5, "gsdd_purity_select_desc", PuritySelectDesc), (7, "gsdd_jump_desc", JumpDesc)):      # (6 is not assigned)
             if L.gsdd_abi_sizeof(which) != C.sizeof(cls):
                 raise GsddError(f"{LIB_PATH} was built from another revision of include/gsdd.h: sizeof({name}) is {L.gsdd_abi_sizeof(which)} "
                                 f"there and {C.sizeof(cls)} in this binding -- rebuild it with ./build.sh")
@@ -182,6 +189,7 @@ def lib():
         L.gsdd_advance_floor.argtypes = [_p, _i, _i64, _i64, _p, _i64, _p]
         L.gsdd_d3pm_purity_step.argtypes = [C.POINTER(PurityDesc), _p]
         L.gsdd_d3pm_purity_select.argtypes = [C.POINTER(PuritySelectDesc), _p]
+        L.gsdd_d3pm_forward_jump.argtypes = [C.POINTER(JumpDesc), _p]
         L.gsdd_advance_plan.argtypes = [_p, _p, _p, _i64, _p, _i, _p, _p, _i64, _p]
         L.gsdd_text_embed.argtypes = [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]
         L.gsdd_text_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]

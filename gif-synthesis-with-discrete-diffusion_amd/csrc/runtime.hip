@@ -9,7 +9,7 @@ void set_error(const std::string& s) { g_err = s; }
 using namespace gsdd;
 
 extern "C" const char* gsdd_last_error(void) { return g_err.c_str(); }
-extern "C" int gsdd_version(void) { return 103; }
+extern "C" int gsdd_version(void) { return 104; }
 extern "C" int64_t gsdd_abi_sizeof(int which) {
     switch (which) {
         case 0: return (int64_t)sizeof(gsdd_gemm_desc);
@@ -18,6 +18,7 @@ extern "C" int64_t gsdd_abi_sizeof(int which) {
         case 3: return (int64_t)sizeof(gsdd_train_desc);
         case 4: return (int64_t)sizeof(gsdd_purity_desc);
         case 5: return (int64_t)sizeof(gsdd_purity_select_desc);
+        case 7: return (int64_t)sizeof(gsdd_jump_desc);          // (6 stays unassigned: -1)
         default: return -1;
     }
 }

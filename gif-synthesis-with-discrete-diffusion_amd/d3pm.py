@@ -437,6 +437,86 @@ def plan_timesteps(plan):
     return out
 
 
+class ResamplePlan(collections.namedtuple("ResamplePlan", "T jump times ops")):
+    """A known-token chain with RePaint's resampling jumps: `ops` is the order of execution, ("step", t) -- the ordinary reverse step
+    with the denoiser at t, which leaves the state at level t - 1 -- and ("jump", a) -- the whole state diffused forward from level a to
+    a + jump.  t0, n_steps, q_sample and draws read like SamplePlan's; every step is the plain one (dt 1, post_skip 0)."""
+    __slots__ = ()
+    q_sample, dt, post_skip = False, 1, 0
+
+    @property
+    def t0(self):
+        return self.T - 1
+
+    @property
+    def n_steps(self):
+        return sum(1 for kind, _ in self.ops if kind == "step")
+
+    @property
+    def n_jumps(self):
+        return len(self.ops) - self.n_steps
+
+    @property
+    def draws(self):
+        """Noise streams a run spends: one per step and one per jump, in order of execution."""
+        return len(self.ops)
+
+
+def resample_plan(T, jump, times):
+    """The chain sample(resample_jump=jump, resample_times=times) runs, host-side and pure (RePaint, Algorithm 1, on the levels of this
+    sampler).  The landing levels T-1-m*jump (m = 1 .. (T-1)//jump, all >= 0) are each left upwards times - 1 times: whenever the
+    chain arrives at one that has visits left, the state jumps forward by `jump` levels and the steps in between run again.
+    T + (times-1) * jump * ((T-1)//jump) steps and (times-1) * ((T-1)//jump) jumps; never a jump from the clean level -1, the last
+    op is the step at t = 0, and times = 1 is sample_plan(T)'s chain."""
+    left = {T - 1 - m * jump: times - 1 for m in range(1, (T - 1) // jump + 1)}
+    ops, t = [], T - 1
+    while t >= 0:
+        ops.append(("step", t))
+        t -= 1
+        if left.get(t, 0) > 0:
+            left[t] -= 1
+            ops.append(("jump", t))
+            t += jump
+    return ResamplePlan(T, jump, times, tuple(ops))
+
+
+def jump_table(T, K, jump):
+    """-> f32 (T + 1, 3): log(alpha~ + beta~), log(beta~), log(gamma~) of the forward move from level a to a + jump (the product of
+    the one-step matrices a + 1 ... a + jump in closed form), row a mod (T + 1) -- row T is the clean level -1.  With abar / gbar the
+    cumulative arrays of alpha_schedule (index T: 1 / 0): alpha~ = abar_b / abar_a, gamma~ = (gbar_b - gbar_a) / (1 - gbar_a),
+    beta~ = (1 - alpha~ - gamma~) / K, all in fp64 (beta~ is a difference of numbers of size 1e-5 at the top of the schedule).  Rows
+    whose target a + jump lies above T - 1 are NaN: the chain never asks for them.  What gsdd_d3pm_forward_jump reads."""
+    import numpy as np
+    _, _, _, att, _, ctt = alpha_schedule(T, N=K)
+    out = np.full((T + 1, 3), np.nan, dtype=np.float64)
+    for row in range(T + 1):
+        a = -1 if row == T else row
+        b = a + jump
+        if b > T - 1:
+            continue
+        al = att[b] / att[row]
+        ga = (ctt[b] - ctt[row]) / (1.0 - ctt[row])
+        be = (1.0 - al - ga) / K
+        out[row] = np.log(al + be), np.log(be), np.log(ga)
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def check_resample(jump, times, T, known_mask):
+    """Validates sample()'s resample_jump / resample_times.  -> None (the plain chain) or (jump, times) with times >= 2."""
+    is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not is_int(times) or times < 1:
+        raise GsddError(f"resample_times must be an int >= 1, got {times!r}")
+    if jump is None:
+        if times != 1:
+            raise GsddError(f"resample_times = {times} needs resample_jump (how many levels every resampling jumps back up)")
+        return None
+    if not is_int(jump) or not 1 <= jump <= T - 1:
+        raise GsddError(f"resample_jump must be None or an int in [1, {T - 1}] (num_timesteps - 1), got {jump!r}")
+    if known_mask is None:
+        raise GsddError("resample_jump needs known_mask: resampling harmonises sampled positions with given ones")
+    return (int(jump), int(times)) if times > 1 else None
+
+
 class PurityPlan(collections.namedtuple("PurityPlan", "calls final rule weight")):
     """A purity-prior chain (sample() with prior_rule 1 / 2): the (t, n) of every p_sample call at t > 0 -- denoiser at t, reveal n
     [MASK] positions per sample -- whether a plain reverse step at t = 0 closes it, the rule and the prior weight r.
@@ -661,6 +741,14 @@ class DiffusionTransformer(nn.Module):
     def _sched(self):
         return [getattr(self, n) for n in SCHED_ORDER]
 
+    def _jump_table(self, jump, dev):
+        """The device copy of jump_table(T, K, jump), made once per jump (and device)."""
+        cache = self.__dict__.setdefault("_jump_tables", {})
+        key = (int(jump), str(dev))
+        if key not in cache:
+            cache[key] = jump_table(self.num_timesteps, self.num_classes - 1, int(jump)).to(dev).contiguous()
+        return cache[key]
+
     def update_n_sample(self):
         """diffusion_transformer.py:166-179: the reference's list for this num_timesteps / prior_ps (unchanged for any other T)."""
         ns = reference_n_sample(self.num_timesteps, self.prior_ps)
@@ -705,7 +793,8 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
-               print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", **kwargs):
+               print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", resample_jump=None,
+               resample_times=1, **kwargs):
         """diffusion_transformer.py:568-644.  The loop itself is `_sample_once`, driven by `sample_plan`; `_sample_checked` repeats it
         on the bf16x3 layer kernel if an activation left the f16 operand range.
         filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
@@ -718,7 +807,12 @@ class DiffusionTransformer(nn.Module):
         interpolation, inpainting; `frame_mask`).  From all-[MASK], prior_rule 0.  Those positions skip the learned reverse step:
         known_mode "renoise" draws them from the forward marginal q(x_{t-1} | x_0) at every step (RePaint's construction for the
         absorbing chain; x_0 itself at t = 0), "hold" writes x_0 at every step.  Every other position is sampled as without the mask
-        and sees the known ones through self-attention.  None launches exactly the plain chain."""
+        and sees the known ones through self-attention.  None launches exactly the plain chain.
+        resample_jump / resample_times (with known_mask): RePaint's resampling -- `resample_plan`: after every `resample_jump` reverse
+        steps the whole state is diffused forward by that many levels (gsdd_d3pm_forward_jump; "hold" copies the known positions
+        through, "renoise" moves them like every other position) and denoised again, `resample_times` times over, so that the sampled
+        positions see the known content more than once per level.  Every step and every jump spends one noise stream.  None or
+        resample_times = 1: the call without them, launch for launch."""
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
         if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
@@ -726,8 +820,10 @@ class DiffusionTransformer(nn.Module):
         known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
                                                             L=self.shape, K=self.num_classes - 1, start_step=start_step,
                                                             prior_rule=self.prior_rule)
+        resample = check_resample(resample_jump, resample_times, self.num_timesteps, known_mask)
         if known is not None:
-            return self._sample_checked(sample_plan(self.num_timesteps), condition_token, condition_embed, cf_condition_embed,
+            plan = sample_plan(self.num_timesteps) if resample is None else resample_plan(self.num_timesteps, *resample)
+            return self._sample_checked(plan, condition_token, condition_embed, cf_condition_embed,
                                         return_logits=return_logits, use_graph=use_graph, trace=trace, truncation_rate=trunc,
                                         known=known, **kwargs)
         if self.prior_rule != 0:        # purity-prior inference (:304-346): reveal n_sample[t] trusted positions per timestep
@@ -750,6 +846,8 @@ class DiffusionTransformer(nn.Module):
         unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit.
         known_mask / known_mode: as in sample(); a known position is re-noised to the level the step's posterior jumps to."""
         T = self.num_timesteps
+        if "resample_jump" in kwargs or "resample_times" in kwargs:
+            raise GsddError("sample_fast takes no resample_jump / resample_times: the skip-step chain has no resampling jumps (use sample)")
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
                                                             L=self.shape, K=self.num_classes - 1, start_step=int(T * filter_ratio))
@@ -798,6 +896,7 @@ class DiffusionTransformer(nn.Module):
         # through the same arithmetic as the stacked pass, at half the denoiser work.  (One host comparison per sample() call;
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
         same_cond = (guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape and bool(torch.equal(cond, cf)))
+        resample = isinstance(plan, ResamplePlan)   # RePaint's jumps: the host issues plan.ops in order, steps and forward jumps
         purity = isinstance(plan, PurityPlan)       # prior_rule 1 / 2: the calls at t > 0 come from device plan arrays; the rest is shared
         n_steps = plan.n_steps
         stream0 = self.noise_stream + (1 if plan.q_sample else 0)      # the partially noised start spends one draw on q_sample
@@ -849,7 +948,13 @@ class DiffusionTransformer(nn.Module):
                                    seed=self.noise_seed, stream_add=1, row0=lane.row0, stream=lane.st)
             ops.advance_plan(lane.step_dev, lane.plan_t, lane.plan_n, lane.t2, lane.n_dev, lane.sid, 2, stream=lane.st)
 
+        def jump_op(lane):                      # the state at level t2 moves forward to t2 + jump; one noise stream, like a step
+            ops.d3pm_forward_jump(lane.tok, lane.tok, lane.jump_table, lane.t2, lane.sid, K=K, T=T, jump=plan.jump, seed=self.noise_seed,
+                                  row0=lane.row0, hold=lane.jump_hold, stream=lane.st)
+            ops.advance(lane.t2, plan.jump, lane.sid, 1, stream=lane.st)
+
         one_step = purity_step if purity else chain_step
+        lane_list = []
         cur = torch.cuda.current_stream()
         tr.packed()                                 # packed weights, AdaLN tables and the fragment images are (re)built HERE, on the
         tr.fragment_images()                        # caller's stream: each lane's wait_stream(cur) below then orders its reads after them
@@ -876,6 +981,11 @@ class DiffusionTransformer(nn.Module):
                 # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they
                 # are constants of the chain, so the captured graph is still one step; nothing at all without a mask
                 lane.known_kw = _known_kwargs(known, dev, sl)
+                if resample:                    # the jump's table and, in hold mode, the positions it copies through
+                    lane.jump_table = self._jump_table(plan.jump, dev)
+                    lane.jump_hold = lane.known_kw["known"] if lane.known_kw["known_mode"] == KNOWN_MODES["hold"] else None
+                    lane.jump_graph = None
+                    lane_list.append(lane)
                 if purity:
                     # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
                     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
@@ -896,13 +1006,37 @@ class DiffusionTransformer(nn.Module):
                     one_step(lane)              # recorded, not executed
                     g.end(st)
                     graphs.append(g)
+                elif resample:                  # eager: every op of the plan in order (a trace gets one entry per op)
+                    for kind, _ in plan.ops:
+                        (one_step if kind == "step" else jump_op)(lane)
+                        if trace is not None:
+                            trace.append(lane.tok.clone())
                 else:
                     for _ in range(n_steps):
                         one_step(lane)
                         if trace is not None:
                             trace.append(lane.tok.clone())
                 toks.append(lane.tok)
-        if graphs:
+        if graphs and resample:
+            # the plan's ops in order, the lanes alternating per op.  Two linear graphs per lane: the step (above) and the jump kernel with
+            # its counter update; a lane's first jump runs eagerly (arguments validated outside capture) and is recorded right after
+            for kind, _ in plan.ops[1:]:
+                for ln, lane in enumerate(lane_list):
+                    if kind == "step":
+                        graphs[ln].launch(lane.st)
+                    elif lane.jump_graph is None:
+                        with torch.cuda.stream(lane.st):
+                            jump_op(lane)
+                            lane.jump_graph = ops.Graph()
+                            lane.jump_graph.begin(lane.st)
+                            jump_op(lane)       # recorded, not executed
+                            lane.jump_graph.end(lane.st)
+                    else:
+                        lane.jump_graph.launch(lane.st)
+            self._last_graph = graphs[0]
+            self._last_graphs = graphs
+            self._last_jump_graphs = [lane.jump_graph for lane in lane_list]
+        elif graphs:
             for _ in range(n_steps - 1):        # the lanes' replays are issued alternately so that both queues stay fed
                 for ln, g in enumerate(graphs):
                     g.launch(self._streams[ln])
@@ -921,6 +1055,8 @@ class DiffusionTransformer(nn.Module):
         self._range_flags = range_flags
         self._last_lanes = lanes
         self._last_plan = plan
+        if not (graphs and resample):           # (the jump graphs belong to the call that made them)
+            self._last_jump_graphs = []
         self._last_draws = plan.draws
         self.noise_stream += self._last_draws
         out = {"content_token": tok}
@@ -1102,11 +1238,14 @@ class DiscreteDiffusion(nn.Module):
     0 < r < 1; VQ-Diffusion's inference uses 0.86).
     sample_condition_frames: null, an int k in [1, t_latent) or a list of latent frame indices: forward(do_inference=True) then keeps
     those latent frames of the input clip (its own codes) and samples the rest (frame prediction / interpolation; `frame_mask`);
-    sample_known_mode "renoise" / "hold" is the sampler's known_mode.  Not with sample_prior_rule > 0."""
+    sample_known_mode "renoise" / "hold" is the sampler's known_mode.  Not with sample_prior_rule > 0.
+    sample_resample_jump / sample_resample_times: the sampler's resample_jump / resample_times (RePaint's resampling jumps), handed to
+    sample() when a mask is in use; null leaves the plain known chain.  Not with sample_skip_step (sample_fast has no jumps)."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
-                 sample_condition_frames=None, sample_known_mode="renoise", **kwargs):
+                 sample_condition_frames=None, sample_known_mode="renoise", sample_resample_jump=None, sample_resample_times=None,
+                 **kwargs):
         super().__init__()
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -1160,6 +1299,15 @@ class DiscreteDiffusion(nn.Module):
             raise GsddError(f"sample_known_mode must be one of {sorted(KNOWN_MODES)}, got {sample_known_mode!r}")
         self.sample_condition_frames = sample_condition_frames
         self.sample_known_mode = sample_known_mode
+        for name, v, lo in (("sample_resample_jump", sample_resample_jump, 1), ("sample_resample_times", sample_resample_times, 1)):
+            if v is not None and not (is_int(v) and v >= lo):
+                raise GsddError(f"{name} must be null or an int >= {lo}, got {v!r}")
+        if sample_resample_times is not None and sample_resample_times > 1 and sample_resample_jump is None:
+            raise GsddError(f"sample_resample_times = {sample_resample_times} needs sample_resample_jump")
+        if sample_resample_jump is not None and self.sample_skip_step is not None:
+            raise GsddError("sample_resample_jump and sample_skip_step cannot be combined: sample_fast has no resampling jumps")
+        self.sample_resample_jump = None if sample_resample_jump is None else int(sample_resample_jump)
+        self.sample_resample_times = None if sample_resample_times is None else int(sample_resample_times)
 
     def condition_frame_mask(self, latent_shape):
         """-> None or the (L,) bool mask of sample_condition_frames on this latent grid (validated here, at sampling time)."""
@@ -1260,6 +1408,9 @@ class DiscreteDiffusion(nn.Module):
             content, known_kw = None, {}
         else:
             content, known_kw = known_tokens, {"known_mask": known_mask, "known_mode": self.sample_known_mode}
+            if self.sample_resample_jump is not None:
+                known_kw.update(resample_jump=self.sample_resample_jump,
+                                resample_times=1 if self.sample_resample_times is None else self.sample_resample_times)
         if self.sample_skip_step is None:
             out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=content, filter_ratio=0, **known_kw)
         else:

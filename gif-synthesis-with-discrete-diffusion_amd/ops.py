@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib as abi
-from ._lib import GemmDesc, GsddError, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, check, lib, ptr, stream_ptr
+from ._lib import GemmDesc, GsddError, JumpDesc, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, check, lib, ptr, stream_ptr
 
 ACT_NONE, ACT_RELU, ACT_GELU2 = 0, 1, 2
 
@@ -374,6 +374,30 @@ def d3pm_q_sample(x0, xt, sched, t_dev, stream_dev, *, K, T, seed, row0=0, strea
     check(lib().gsdd_d3pm_q_sample(ptr(x0), ptr(xt), B, L, K, T, arr, ptr(t_dev), seed, ptr(stream_dev), row0,
                                    stream_ptr(stream)))
     return xt
+
+
+def d3pm_forward_jump(tok_in, tok_out, table, t_dev, stream_dev, *, K, T, jump, seed, row0=0, hold=None, stream=None):
+    """tok_out ~ q(x_{a + jump} | x_a = tok_in) per position (gsdd_d3pm_forward_jump; tok_out may be tok_in).  table: the device f32
+    [(T + 1), 3] log-probabilities of this jump (d3pm.jump_table), t_dev: int64 [B] from-levels a (-1 / T: clean), hold: None or a
+    (B, L) uint8 / bool tensor, non-zero where the token is copied through."""
+    B, L = tok_in.shape
+    d = JumpDesc()
+    if table.dtype != torch.float32 or table.numel() != (T + 1) * 3:
+        raise GsddError(f"d3pm_forward_jump: table must hold {(T + 1) * 3} float32 values, got {tuple(table.shape)} {table.dtype}")
+    if tok_in.dtype != torch.int64 or tok_out.dtype != torch.int64 or tuple(tok_out.shape) != (B, L) or t_dev.dtype != torch.int64 or t_dev.numel() < B:
+        raise GsddError("d3pm_forward_jump: tok_in / tok_out must be int64 (B, L) tensors and t_dev int64 with at least B entries")
+    if not (tok_in.is_contiguous() and tok_out.is_contiguous() and t_dev.is_contiguous() and table.is_contiguous()):
+        raise GsddError("d3pm_forward_jump: tok_in, tok_out, t_dev and table must be contiguous")
+    if hold is not None:
+        if hold.dtype not in (torch.uint8, torch.bool) or tuple(hold.shape) != (B, L) or not hold.is_contiguous():
+            raise GsddError(f"d3pm_forward_jump: hold must be a contiguous uint8 / bool {(B, L)} tensor, got {tuple(hold.shape)} {hold.dtype}")
+        d.hold = ptr(hold)
+    d.tok_in, d.tok_out = ptr(tok_in), ptr(tok_out)
+    d.B, d.L, d.K, d.T = B, L, K, T
+    d.table, d.jump = ptr(table), int(jump)
+    d.t_dev, d.seed, d.stream_dev, d.row0 = ptr(t_dev), seed, ptr(stream_dev), row0
+    check(lib().gsdd_d3pm_forward_jump(C.byref(d), stream_ptr(stream)))
+    return tok_out
 
 
 def _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux):

@@ -33,7 +33,7 @@ extern "C" {
 const char* gsdd_last_error(void);
 int gsdd_version(void);
 /* sizeof of a descriptor struct as this build of the library sees it (which: 0 gsdd_gemm_desc, 1 gsdd_layer_desc, 2 gsdd_step_desc,
- * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc; anything else: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
+ * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc, 7 gsdd_jump_desc; anything else, 6 included: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
  * library built from another revision of this header fails at load time instead of misreading a descriptor. */
 int64_t gsdd_abi_sizeof(int which);
 
@@ -410,6 +410,29 @@ int gsdd_d3pm_purity_select(const gsdd_purity_select_desc* d, void* stream);
 int gsdd_d3pm_q_sample(const int64_t* x0, int64_t* xt, int B, int L, int K, int T,
                        const float* const* sched, const int64_t* t_dev, uint64_t seed,
                        const int64_t* stream_dev, int64_t row0, void* stream);
+
+/* Forward jump of a state from level a to level b = a + jump (RePaint's resampling: after `jump` reverse steps the chain is diffused
+ * forward again and denoised once more), per position and independently, the levels as gsdd_d3pm_step's t: the state the denoiser
+ * sees at t is at level t, level -1 is clean and wraps to index T.  With abar / gbar the cumulative schedule (index -1 = T: 1 / 0),
+ *   alpha~ = abar_b / abar_a,   1 - gamma~ = (1 - gbar_b) / (1 - gbar_a),   beta~ = (1 - alpha~ - gamma~) / K:
+ *   a [MASK] stays [MASK] (no uniforms read); a code i becomes [MASK] with gamma~, stays i with alpha~ + beta~, becomes any other
+ *   code with beta~ each -- the product of the one-step matrices of levels a + 1 ... b.
+ * The draw is the Gumbel arg-max (first index on ties) over the K + 1 classes on the position's own counters of the (B, K+1, L) Philox
+ * draw at stream stream_dev[0], as in gsdd_d3pm_step.  The three log-probabilities are read from `table`, which the host makes in
+ * fp64 for this `jump`: row (a mod (T + 1)) holds log(alpha~ + beta~), log(beta~), log(gamma~) as f32. */
+typedef struct {
+    const int64_t* tok_in;      /* [B*L] tokens in [0, K], K = [MASK]                                                           */
+    int64_t* tok_out;           /* [B*L]; may alias tok_in                                                                      */
+    int B, L, K, T;
+    const float* table;         /* device float[(T + 1) * 3]: (hit, miss, mask) per from-level, the level wrapped modulo T + 1    */
+    int jump;                   /* >= 1: the jump `table` was made for (levels a + jump > T - 1 have NaN rows there)            */
+    const int64_t* t_dev;       /* device int64[B]: the from-level of every batch row, read on the device, wrapped modulo T + 1 */
+    const uint8_t* hold;        /* [B*L] or NULL; non-zero: the position is copied through, no uniforms read                    */
+    uint64_t seed;
+    const int64_t* stream_dev;  /* device int64[1] Philox stream id                                                             */
+    int64_t row0;               /* global row (position) offset of this shard                                                   */
+} gsdd_jump_desc;
+int gsdd_d3pm_forward_jump(const gsdd_jump_desc* d, void* stream);
 
 /* Training objective, forward value: _train_loss + the loss tail of forward (diffusion_transformer.py:391-457, :548)
  * from the denoiser logits of x_t.  Per-position scratch (kl, nll, aux: float[B*L]; x0_recon, xt1_recon: int64[B*L]),

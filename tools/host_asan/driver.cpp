@@ -176,6 +176,37 @@ int main() {
         d.K = K; d.sched[3] = nullptr;
         EXPECT(gsdd_d3pm_step(&d, st), GSDD_E_ARG, false);
         EXPECT(gsdd_d3pm_q_sample(devp<int64_t>(), devp<int64_t>(), B, L, K, T, sched, devp<int64_t>(), 1, devp<int64_t>(), 0, st), GSDD_OK, true);
+        {   // forward jump (RePaint's resampling): every class width, in place, with and without a hold mask; bad arguments
+            gsdd_jump_desc j;
+            std::memset(&j, 0, sizeof j);
+            j.tok_in = devp<int64_t>(); j.tok_out = devp<int64_t>();
+            j.B = B; j.L = L; j.K = K; j.T = T; j.table = devp(); j.jump = 10;
+            j.t_dev = devp<int64_t>(); j.stream_dev = devp<int64_t>(); j.seed = 1; j.row0 = 1000;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
+            j.hold = devp<uint8_t>(); j.tok_out = const_cast<int64_t*>(j.tok_in);
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
+            for (int k : {4, 32, 768, 1024, 2048, 4092, 8192}) { j.K = k; EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true); }
+            for (int bad : {0, 2, 30, 8196, -4}) { j.K = bad; EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false); }
+            j.K = K;
+            for (int bad : {0, -1, T + 1}) { j.jump = bad; EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false); }
+            j.jump = 1;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
+            j.table = nullptr;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.table = devp(); j.tok_in = nullptr;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.tok_in = devp<int64_t>(); j.tok_out = nullptr;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.tok_out = devp<int64_t>(); j.t_dev = nullptr;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.t_dev = devp<int64_t>(); j.stream_dev = nullptr;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.stream_dev = devp<int64_t>(); j.B = 0;
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_E_ARG, false);
+            j.B = B;
+            EXPECT(gsdd_d3pm_forward_jump(nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
+        }
         {   // purity-prior step: scores + candidates, selection, plan counter
             gsdd_purity_desc p;
             std::memset(&p, 0, sizeof p);
