@@ -20,6 +20,7 @@ EXPORTS = [
     "gsdd_adaln_bwd", "gsdd_adam", "gsdd_adam_multi", "gsdd_adam_multi_dev", "gsdd_advance", "gsdd_advance_floor",
     "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan", "gsdd_d3pm_forward_jump",
     "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
+    "gsdd_ln_apply", "gsdd_d3pm_cross_attention_train", "gsdd_d3pm_cross_attention_bwd", "gsdd_d3pm_cross_attention_bwd_workspace_bytes",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
 ]
@@ -131,6 +132,7 @@ def lib():
                                 f"there and {C.sizeof(cls)} in this binding -- rebuild it with ./build.sh")
         L.gsdd_gemm.argtypes = [C.POINTER(GemmDesc), _p]
         L.gsdd_row_stats.argtypes = [_p, _i64, _i, C.c_float, _p, _p]
+        L.gsdd_ln_apply.argtypes = [_p, _p, _p, _p, _i64, _i, _p, _p]
         L.gsdd_ncdhw_to_rows.argtypes = [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]
         L.gsdd_preprocess_clip.argtypes = [_p] + [_i] * 10 + [_p, _p]
         L.gsdd_axial_attention.argtypes = [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p]
@@ -164,6 +166,10 @@ def lib():
         L.gsdd_rows_linear.argtypes = [_p, _i64, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p]
         L.gsdd_d3pm_logits.argtypes = [_p, _i64, _i, _p, _p, _p, _p, _i, _p, _p]
         L.gsdd_d3pm_cross_attention.argtypes = [_p, _p, _p, _i, _i, _i, _i, _p, _p]
+        L.gsdd_d3pm_cross_attention_train.argtypes = [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]
+        L.gsdd_d3pm_cross_attention_bwd_workspace_bytes.argtypes = [_i, _i, _i, _i]
+        L.gsdd_d3pm_cross_attention_bwd_workspace_bytes.restype = _i64
+        L.gsdd_d3pm_cross_attention_bwd.argtypes = [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]
         L.gsdd_d3pm_step.argtypes = [C.POINTER(StepDesc), _p]
         L.gsdd_d3pm_q_sample.argtypes = [_p, _p, _i, _i, _i, _i, C.POINTER(_p), _p, C.c_uint64, _p, _i64, _p]
         L.gsdd_d3pm_train_loss.argtypes = [C.POINTER(TrainDesc), _p]

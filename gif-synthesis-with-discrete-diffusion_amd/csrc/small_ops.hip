@@ -483,9 +483,38 @@ __global__ __launch_bounds__(256) void preprocess_clip_kernel(const uint8_t* __r
     }
 }
 
+// y[m][c] = (x[m][c] - mean_m) rstd_m gamma[c] + beta[c] with stats[m] = {mean, rstd} from gsdd_row_stats: LayerNorm rows of any width
+// (a multiple of 4), one lane per float4.  gsdd_ln_fwd does statistics and rows in one pass but is specialised for 64 features; the text
+// tower is 512 wide (128 in the test fixture), so its per-token output takes this kernel behind gsdd_row_stats.
+__global__ __launch_bounds__(256) void ln_apply_kernel(const float* x, const float* stats, const float* gamma, const float* beta, int64_t M, int C, float* y) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c4 = C >> 2;
+    if (i >= M * c4) return;
+    const int64_t m = i / c4;
+    const int c = (int)(i - m * c4) * 4;
+    const float mean = stats[2 * m], rstd = stats[2 * m + 1];
+    const float4 v = *reinterpret_cast<const float4*>(x + m * C + c);
+    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
+    const float4 b = *reinterpret_cast<const float4*>(beta + c);
+    *reinterpret_cast<float4*>(y + m * C + c) = make_float4((v.x - mean) * rstd * g.x + b.x, (v.y - mean) * rstd * g.y + b.y,
+                                                            (v.z - mean) * rstd * g.z + b.z, (v.w - mean) * rstd * g.w + b.w);
+}
+
 }  // namespace gsdd
 
 using namespace gsdd;
+
+extern "C" int gsdd_ln_apply(const float* x, const float* stats, const float* gamma, const float* beta, int64_t M, int C, float* y,
+                             void* stream) {
+    GSDD_CHECK_ARG(x && stats && gamma && beta && y, "null pointer");
+    GSDD_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "C must be a multiple of 4");
+    const int64_t n = M * (C / 4);
+    GSDD_CHECK_ARG((n + 255) / 256 < (1ll << 31), "grid too large");
+    hipLaunchKernelGGL(ln_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, stats, gamma, beta, M, C,
+                       y);
+    GSDD_CHECK_LAUNCH();
+    return GSDD_OK;
+}
 
 extern "C" int gsdd_d3pm_embed(const int64_t* tok, int B, int L, int D, const float* emb, int n_embed, const float* pos,
                                int rep, float* x, void* stream) {

@@ -1320,8 +1320,8 @@ class DiscreteDiffusion(nn.Module):
         return frame_mask(latent_shape, frames)
 
     def _text(self, texts, dev):
-        emb = self.textencoder(texts)
-        emb = emb.unsqueeze(1).to(dev)
+        emb = self.textencoder(texts)                                  # (B, C) pooled, or (B, Te, C) from a per-token provider
+        emb = (emb.unsqueeze(1) if emb.dim() == 2 else emb).to(dev)
         return torch.zeros_like(emb) if self.zero_text_emb else emb.float()
 
     def forward(self, batch, autoencoder, length_estimator=None, do_inference=False):
@@ -1421,4 +1421,5 @@ class DiscreteDiffusion(nn.Module):
         return autoencoder.decode(out["content_token"].view(B, *shape))
 
     def get_text_embeddings(self, features):                                           # discrete_diffusion.py:91-94
-        return self.textencoder(features).unsqueeze(1)
+        emb = self.textencoder(features)
+        return emb.unsqueeze(1) if emb.dim() == 2 else emb

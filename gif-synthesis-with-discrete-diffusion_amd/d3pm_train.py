@@ -23,17 +23,19 @@ class _LinearImages:
     operands), all refreshed by ONE launch per optimiser step.  The descriptor table points at the parameters themselves (the
     optimisers update them in place); `refresh` rebuilds it if a parameter has moved."""
     NAMES = ("qkv", "qkv_t", "proj", "proj_t", "w1", "w1_t", "w2", "w2_t")
+    CROSS_NAMES = ("q2", "q2_t", "proj2", "proj2_t")      # attn2.query / attn2.proj: from the first step with more than one condition token
 
     def __init__(self, tr):
         self.tr = tr
         self.ptrs = None
+        self.cross = False
+        self._retired = None       # (buf, table) from before `cross` was switched on: a step captured earlier still replays on them
 
-    @staticmethod
-    def _pieces(blk):
+    def _pieces(self, blk):
         a, m = blk.attn1, blk.mlp
         q, k, v = a.query.weight, a.key.weight, a.value.weight
         # name -> (n_out, n_in, [(weight, rows of the image matrix it fills, columns, transpose, fragment offset)])
-        return {
+        pieces = {
             "qkv": (192, 64, [(w, 64, 64, 0, 8 * j) for j, w in enumerate((q, k, v))]),
             "qkv_t": (64, 192, [(w, 64, 64, 1, 8 * j) for j, w in enumerate((q, k, v))]),
             "proj": (64, 64, [(a.proj.weight, 64, 64, 0, 0)]),
@@ -43,6 +45,15 @@ class _LinearImages:
             "w2": (64, 256, [(m[2].weight, 64, 256, 0, 0)]),
             "w2_t": (256, 64, [(m[2].weight, 256, 64, 1, 0)]),
         }
+        if self.cross:
+            a2 = blk.attn2
+            pieces.update({
+                "q2": (64, 64, [(a2.query.weight, 64, 64, 0, 0)]),
+                "q2_t": (64, 64, [(a2.query.weight, 64, 64, 1, 0)]),
+                "proj2": (64, 64, [(a2.proj.weight, 64, 64, 0, 0)]),
+                "proj2_t": (64, 64, [(a2.proj.weight, 64, 64, 1, 0)]),
+            })
+        return pieces
 
     def _build(self):
         import numpy as np
@@ -69,7 +80,15 @@ class _LinearImages:
     def _current_ptrs(self):
         return [w.data_ptr() for blk in self.tr.blocks for _, _, pieces in self._pieces(blk).values() for w, *_ in pieces]
 
-    def refresh(self):
+    def refresh(self, cross=False):
+        """cross: the step needs the attn2.query / attn2.proj images too.  Once asked for they stay in the table (a one-token step
+        that follows does not rebuild it); a trainer that only ever sees one token never packs them."""
+        if cross and not self.cross:
+            # A step captured before this one replays the pack launch on the old table and images, so they stay allocated.  One retired
+            # set is enough: `cross` only ever goes from False to True, so this rebuild happens at most once per trainer.
+            if self.ptrs is not None:
+                self._retired = (self.buf, self.table)
+            self.cross, self.ptrs = True, None
         if self.ptrs is None or self.ptrs != self._current_ptrs():
             self._build()
         ops.rows_linear_pack_many(self.table, self.n_desc, 256, 256)
@@ -101,10 +120,11 @@ class D3PMTrainer:
         dev = xt.device
         f = dict(dtype=torch.float32, device=dev)
         cond = cond.float().contiguous()
-        if cond.shape[1] != 1:
-            raise NotImplementedError("the training step is built for one condition token (the reference call site)")
-        flat = cond.reshape(B, -1).contiguous()
-        sv = {"xt": xt, "t": t, "cond": flat, "layers": []}
+        if cond.dim() != 3 or cond.shape[0] != B:
+            raise GsddError(f"the condition must be (B, Te, cond_dim) with B = {B}, got {tuple(cond.shape)}")
+        Te = cond.shape[1]
+        flat = cond.reshape(B * Te, -1).contiguous()             # the condition rows [B Te][cond_dim]
+        sv = {"xt": xt, "t": t, "cond": flat, "Te": Te, "layers": []}
         x = torch.empty((M, D), **f)
         ops.d3pm_embed(xt, p["emb"], p["pos"], x)
         aws = ops.d3pm_attention_workspace(B, L, H, dev) if L % 32 == 0 else None     # pre-split K/V images (matrix-pipe forward)
@@ -114,10 +134,41 @@ class D3PMTrainer:
         if fast:
             if self._images is None:
                 self._images = _LinearImages(tr)
-            imgs = self._images.refresh()
+            imgs = self._images.refresh(cross=Te > 1)
         sv["imgs"] = imgs if fast else None
         for li_, lay in enumerate(p["layers"]):
             s = {"x_in": x}
+            if Te > 1:
+                # the general block (transformer_utils.py:266-282): x1a = x + proj(attn1); x1 = x1a + proj2(attn2(ln1_1(x1a), cond))
+                im = imgs[li_] if fast else None
+
+                def lin(x_, image, w, bias, n_out, head_major=False, residual=None):
+                    """one row GEMM of the block on the branch this step takes: fragment image, or the generic GEMM"""
+                    out = torch.empty((n_out // 4, M, 4) if head_major else (M, n_out), **f)
+                    if fast:
+                        return ops.rows_linear(x_, im[image], n_out, out, bias=bias, head_major=head_major, residual=residual)
+                    return ops.linear(x_, w, out, bias=bias, out_mode=2 if head_major else 0, residual=residual)
+
+                s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
+                                                  rows_per_batch=L)
+                s["qkv"] = lin(s["hn"], "qkv", lay["wqkv"], lay["bqkv"], 3 * D, head_major=True)
+                s["y"], s["lse"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
+                ops.d3pm_attention_train(s["qkv"][0:H], s["qkv"][H:2 * H], s["qkv"][2 * H:], B, L, H, s["y"], s["lse"], ws=aws)
+                s["x1a"] = lin(s["y"], "proj", lay["wproj"], lay["bproj"], D, residual=x)
+                ada2 = tr._ada2(li_).view(-1)
+                s["stats11"], s["hq"] = ops.ln_fwd(s["x1a"], ada2, ada2[D:], sel=t, gstride=2 * D, rows_per_batch=L)
+                s["q2"] = lin(s["hq"], "q2", lay["wq2"], lay["bq2"], D, head_major=True)
+                s["k2"] = ops.small_linear(flat, lay["wk2"], lay["bk2"])
+                s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
+                s["y2"], s["lse2"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
+                ops.d3pm_cross_attention_train(s["q2"], s["k2"], s["v2"], B, L, Te, H, s["y2"], s["lse2"])
+                s["x1"] = lin(s["y2"], "proj2", lay["wproj2"], lay["bproj2"], D, residual=s["x1a"])
+                s["stats2"], s["h2"] = ops.ln_fwd(s["x1"], lay["g2"], lay["b2"])
+                s["a"] = lin(s["h2"], "w1", lay["w1"], lay["bb1"], lay["w1"].shape[0])
+                s["u"] = ops.gelu2(s["a"])
+                x = lin(s["u"], "w2", lay["w2"], lay["bb2"], D, residual=s["x1"])
+                sv["layers"].append(s)
+                continue
             if fast:
                 im = imgs[li_]
                 s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
@@ -222,6 +273,8 @@ class D3PMTrainer:
         del dlogits
         bucket()
         bws = ops.d3pm_attention_bwd_workspace(B, L, H, dx.device) if L % 32 == 0 else None     # operand images (matrix-pipe backward)
+        Te = sv["Te"]
+        cws = ops.d3pm_cross_attention_bwd_workspace(B, L, Te, H, dx.device) if Te > 1 else None  # delta + the dK / dV partials
         for i in reversed(range(len(p["layers"]))):
             lay, s = p["layers"][i], sv["layers"][i]
             pre = f"blocks.{i}."
@@ -237,18 +290,39 @@ class D3PMTrainer:
             dh2 = lin_t(da, "w1_t", lay["w1"], D)
             dx1 = ops.ln_bwd(dh2, s["x1"], s["stats2"], lay["g2"], dx_in=dx, dgamma=z(pre + "ln2.weight", lay["g2"]),
                              dbeta=z(pre + "ln2.bias", lay["b2"]), gacc_stride=D)
-            # ---- attention output projection + the broadcast cross-attention vector
-            ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
-            dcvec = ops.batch_rowsum(dx1, B, L)
-            dv2 = ops.small_linear_bwd(dcvec, s["v2"], lay["wproj2"], z(pre + "attn2.proj.weight", lay["wproj2"]),
-                                       z(pre + "attn2.proj.bias", lay["bproj2"]))
-            ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
-                                 z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
-            for nm, ref in (("attn2.key.weight", lay["wk2"]), ("attn2.key.bias", lay["bk2"]),
-                            ("attn2.query.weight", lay["wq2"]), ("attn2.query.bias", lay["bq2"]),
-                            ("ln1_1.emb.weight", blk.ln1_1.emb.weight), ("ln1_1.linear.weight", blk.ln1_1.linear.weight),
-                            ("ln1_1.linear.bias", blk.ln1_1.linear.bias)):
-                z(pre + nm, ref)                # softmax over a single key: exactly zero gradient
+            if Te > 1:
+                # ---- cross-attention over the condition tokens: proj, attention, query, ln1_1; keys / values against the condition rows
+                ops.wgrad(dx1, s["y2"], z(pre + "attn2.proj.weight", lay["wproj2"]), z(pre + "attn2.proj.bias", lay["bproj2"]))
+                dy2 = lin_t(dx1, "proj2_t", lay["wproj2"], D)
+                dq2, dk2, dv2 = ops.d3pm_cross_attention_bwd(s["q2"], s["k2"], s["v2"], s["y2"], dy2, s["lse2"], B, L, Te, H, cws)
+                dq2 = dq2.permute(1, 0, 2).reshape(B * L, D).contiguous()          # head-major -> rows, the layout wgrad and the row GEMMs take
+                ops.wgrad(dq2, s["hq"], z(pre + "attn2.query.weight", lay["wq2"]), z(pre + "attn2.query.bias", lay["bq2"]))
+                dhq = lin_t(dq2, "q2_t", lay["wq2"], D)
+                ada2 = tr._ada2(i).view(-1)
+                dtab2 = torch.zeros((B, 2 * D), **f)
+                dx1 = ops.ln_bwd(dhq, s["x1a"], s["stats11"], ada2, sel=t, gstride=2 * D, rows_per_batch=L, dx_in=dx1, dgamma=dtab2,
+                                 dbeta=dtab2.view(-1)[D:], gacc_stride=2 * D, acc_by_batch=True)
+                ops.adaln_bwd(dtab2, t, blk.ln1_1.emb.weight.contiguous(), blk.ln1_1.linear.weight.contiguous(),
+                              z(pre + "ln1_1.emb.weight", blk.ln1_1.emb.weight), z(pre + "ln1_1.linear.weight", blk.ln1_1.linear.weight),
+                              z(pre + "ln1_1.linear.bias", blk.ln1_1.linear.bias))
+                ops.small_linear_bwd(dk2, sv["cond"], lay["wk2"], z(pre + "attn2.key.weight", lay["wk2"]),
+                                     z(pre + "attn2.key.bias", lay["bk2"]), want_dx=False)
+                ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
+                                     z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+                ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
+            else:
+                # ---- attention output projection + the broadcast cross-attention vector
+                ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
+                dcvec = ops.batch_rowsum(dx1, B, L)
+                dv2 = ops.small_linear_bwd(dcvec, s["v2"], lay["wproj2"], z(pre + "attn2.proj.weight", lay["wproj2"]),
+                                           z(pre + "attn2.proj.bias", lay["bproj2"]))
+                ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
+                                     z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+                for nm, ref in (("attn2.key.weight", lay["wk2"]), ("attn2.key.bias", lay["bk2"]),
+                                ("attn2.query.weight", lay["wq2"]), ("attn2.query.bias", lay["bq2"]),
+                                ("ln1_1.emb.weight", blk.ln1_1.emb.weight), ("ln1_1.linear.weight", blk.ln1_1.linear.weight),
+                                ("ln1_1.linear.bias", blk.ln1_1.linear.bias)):
+                    z(pre + nm, ref)                # softmax over a single key: exactly zero gradient
             dy = lin_t(dx1, "proj_t", lay["wproj"], D)
             # ---- self-attention
             qkv = s["qkv"]
@@ -301,7 +375,7 @@ class D3PMTrainer:
         """Single-process steps only: with a data-parallel group the bucketed all-reduces run between the backward's launches through
         torch.distributed, outside any capture (the eager path; its launch gaps are covered by the collectives' own latency)."""
         return (os.environ.get("GSDD_TRAIN_GRAPH", "1") != "0" and not getattr(self, "_graph_failed", False) and x0.is_cuda
-                and not self.reducer.active() and world_size() == 1 and cond.shape[1] == 1 and x0.shape[1] % 32 == 0)
+                and not self.reducer.active() and world_size() == 1 and x0.shape[1] % 32 == 0)
 
     def _capture(self, x0, cond):
         """Everything of a step that runs on the device -- re-pack of the weight images and AdaLN tables, q_sample, forward, loss +

@@ -145,6 +145,14 @@ def row_stats(x, stats, eps=1e-5, stream=None):
     return stats
 
 
+def ln_apply(x, stats, gamma, beta, out=None, stream=None):
+    """LayerNorm rows of any width from row_stats' statistics (gsdd_ln_apply) -> out [M][C]."""
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib().gsdd_ln_apply(ptr(x), ptr(stats), ptr(gamma), ptr(beta), x.shape[0], x.shape[1], ptr(out), stream_ptr(stream)))
+    return out
+
+
 def ncdhw_to_rows(x, cpad, padw, out=None, stream=None):
     N, Cc, D, H, W = x.shape
     if out is None:
@@ -336,6 +344,28 @@ def d3pm_logits(x, g, b, w, bias, out, stream=None):
 def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None):
     check(lib().gsdd_d3pm_cross_attention(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), stream_ptr(stream)))
     return out
+
+
+def d3pm_cross_attention_train(q, kc, vc, B, L, Te, H, out, lse, stream=None):
+    """Training forward of the general cross-attention: out rows [M][4 H] and lse [H][M] (log2 domain)."""
+    check(lib().gsdd_d3pm_cross_attention_train(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), ptr(lse), stream_ptr(stream)))
+    return out
+
+
+def d3pm_cross_attention_bwd_workspace(B, L, Te, H, device):
+    n = lib().gsdd_d3pm_cross_attention_bwd_workspace_bytes(B, L, Te, H)
+    return torch.empty(((n + 3) // 4,), dtype=torch.float32, device=device)
+
+
+def d3pm_cross_attention_bwd(q, kc, vc, o, dO, lse, B, L, Te, H, ws, dq=None, dkc=None, dvc=None, stream=None):
+    """-> (dq head-major [H][M][4], dkc, dvc rows [B Te][4 H]), all overwritten; ws from d3pm_cross_attention_bwd_workspace."""
+    f = dict(dtype=torch.float32, device=q.device)
+    dq = torch.empty((H, B * L, 4), **f) if dq is None else dq
+    dkc = torch.empty((B * Te, 4 * H), **f) if dkc is None else dkc
+    dvc = torch.empty((B * Te, 4 * H), **f) if dvc is None else dvc
+    check(lib().gsdd_d3pm_cross_attention_bwd(ptr(q), ptr(kc), ptr(vc), ptr(o), ptr(dO), ptr(lse), B, L, Te, H, ptr(dq), ptr(dkc), ptr(dvc),
+                                              ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream_ptr(stream)))
+    return dq, dkc, dvc
 
 
 def d3pm_step(logits_c, logits_u, tok_in, tok_out, sched, t_dev, stream_dev, *, K, T, guidance, seed, row0=0,

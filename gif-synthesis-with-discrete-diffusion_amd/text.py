@@ -138,10 +138,12 @@ class ClipTextTower:
         return buf
 
     @torch.no_grad()
-    def forward(self, ids, eot=None, trim=True):
+    def forward(self, ids, eot=None, trim=True, tokens=False):
         """ids: int64 (B, S <= 77), on the host or on the tower's device; eot: int64 (B,) end-of-text positions, default the first
         position holding the row's largest id (`text.argmax(dim=-1)` of encode_text) -> (B, P) fp32 on the tower's device.
-        trim=False runs the whole width of `ids` instead of the first max(eot) + 1 positions (the result does not depend on it)."""
+        trim=False runs the whole width of `ids` instead of the first max(eot) + 1 positions (the result does not depend on it).
+        tokens=True: the per-token features instead -- the final LayerNorm of every position that ran, (B, S, width) fp32, no projection
+        and no pooling (upstream VQ-Diffusion's condition; a position sees only the ones before it, so a row does not depend on S)."""
         if not self.device.type == "cuda":
             raise GsddError("ClipTextTower.forward needs the weights on a ROCm device (no CPU fallback): call .to(device) first")
         if ids.dim() != 2 or ids.dtype != torch.int64:
@@ -170,6 +172,9 @@ class ClipTextTower:
             ops.row_stats(y, stats, eps=self.eps)
             ops.linear(y, lay["w1"], h, bias=lay["b1"], ln=(stats, lay["g2"], lay["be2"], None, 0), act=ops.ACT_GELU2)
             ops.linear(h, lay["w2"], x, bias=lay["b2"], residual=y)
+        if tokens:
+            ops.row_stats(x, stats, eps=self.eps)
+            return ops.ln_apply(x, stats, self.gf, self.bf).view(B, S, self.width)
         ops.text_pool(x, eot_dev, B, S, buf["pooled"], eot_host=eot_host)
         ops.row_stats(buf["pooled"], buf["pstats"], eps=self.eps)
         out = torch.empty((B, self.proj.shape[0]), dtype=torch.float32, device=dev)

@@ -89,6 +89,10 @@ int gsdd_gemm(const gsdd_gemm_desc* d, void* stream);
 /* per-row LayerNorm statistics (mean, rstd) of x[M][C] (eps inside rsqrt).
  * Replaces the statistics half of nn.LayerNorm: transformer_utils.py:147,157,217,354 */
 int gsdd_row_stats(const float* x, int64_t M, int C, float eps, float* stats, void* stream);
+/* y[m][:] = (x[m][:] - mean) * rstd * gamma + beta with stats from gsdd_row_stats: LayerNorm rows of any width C % 4 == 0 as an
+ * output of their own (the text tower's per-token features; elsewhere the normalisation is a GEMM prologue, and gsdd_ln_fwd, which
+ * writes normalised rows too, takes C == 64 only while the tower is 512 wide). */
+int gsdd_ln_apply(const float* x, const float* stats, const float* gamma, const float* beta, int64_t M, int C, float* y, void* stream);
 
 /* ------------------------------------------------------------------ layout at the NCDHW boundary
  * videogpt_vq_vae.py:58-60 hands (B,3,T,H,W); kernels are channels-last. */
@@ -300,6 +304,18 @@ int gsdd_d3pm_logits(const float* x, int64_t M, int n_embd, const float* ln_g, c
  * kc/vc rows [B*Te][H*4]; out rows [M][H*4].  transformer_utils.py:95-113. */
 int gsdd_d3pm_cross_attention(const float* q, const float* kc, const float* vc, int B, int L, int Te,
                               int H, float* out, void* stream);
+
+/* The same cross-attention for training (1 <= Te <= 77, anything else is GSDD_E_ARG).  The forward also writes lse[H][M], the
+ * log-sum-exp per (head, row) in the log2 domain (as gsdd_d3pm_attention_train keeps it).  The backward takes the forward's out as o
+ * and OVERWRITES dq (head-major [H][M][4]), dkc and dvc (rows [B*Te][H*4]); exact f32.  dkc / dvc are sums over the L rows of a batch
+ * element: per-chunk partials go into the caller's workspace (gsdd_d3pm_cross_attention_bwd_workspace_bytes) and are added in a fixed
+ * order -- no atomics, the same bits on every run, and a batch element's results do not depend on the others in the launch. */
+int gsdd_d3pm_cross_attention_train(const float* q, const float* kc, const float* vc, int B, int L, int Te, int H, float* out,
+                                    float* lse, void* stream);
+int64_t gsdd_d3pm_cross_attention_bwd_workspace_bytes(int B, int L, int Te, int H);
+int gsdd_d3pm_cross_attention_bwd(const float* q, const float* kc, const float* vc, const float* o, const float* dO,
+                                  const float* lse, int B, int L, int Te, int H, float* dq, float* dkc, float* dvc,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* One fused reverse-diffusion step on int64 tokens:
  *   predict_start (fp log_softmax, clamp) x2 -> cf guidance mix -> q_posterior -> Gumbel arg-max.

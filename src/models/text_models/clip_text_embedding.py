@@ -1,5 +1,7 @@
 """Text-conditioning provider with the reference's call contract (src/models/text_models/clip_text_embedding.py:11-69):
-`CLIPTextEmbedding(clip_dim=512)(list[str]) -> (B, clip_dim)` float tensor.
+`CLIPTextEmbedding(clip_dim=512)(list[str]) -> (B, clip_dim)` float tensor; with `per_token=True` (needs a tower) the token features of
+the recipe's 22 context positions instead, (B, 22, clip_dim): the final LayerNorm of every position, no pooling and no projection, the
+condition upstream VQ-Diffusion's cross-attention is written for (the training step and the sampler take any number of tokens).
 
 The reference builds a frozen OpenAI CLIP ViT-B/32 text tower through the `clip` package, which downloads its weights (:22-29).
 Neither the package nor the weights nor the BPE vocabulary exist offline, and the generator zeroes the embedding anyway
@@ -30,9 +32,10 @@ class CLIPTextEmbedding(nn.Module):
     MAX_TEXT_LEN = 20                  # :57 (the reference hard-codes HumanML's limit)
     CONTEXT_DEFAULT = 77               # :58
 
-    def __init__(self, clip_dim=512, weights=None, native=None, **kwargs):
+    def __init__(self, clip_dim=512, weights=None, native=None, per_token=False, **kwargs):
         super().__init__()
         self.clip_dim = clip_dim
+        self.per_token = bool(per_token)
         self.native = native
         self._tower = None                                         # ClipTextTower of the current device (not a sub-module)
         self.register_buffer("_anchor", torch.zeros(1))
@@ -48,6 +51,9 @@ class CLIPTextEmbedding(nn.Module):
                 p.requires_grad = False
             if self.clip_model.config.projection_dim != clip_dim:
                 raise ValueError(f"the supplied tower projects to {self.clip_model.config.projection_dim} dimensions, clip_dim is {clip_dim}")
+            if self.per_token and self.clip_model.config.hidden_size != clip_dim:
+                raise ValueError(f"per_token=True returns the tower's token features, {self.clip_model.config.hidden_size} wide; "
+                                 f"clip_dim is {clip_dim}")
 
     def train(self, mode=True):                                    # the tower stays frozen in eval mode, as in the reference
         super().train(mode)
@@ -81,6 +87,8 @@ class CLIPTextEmbedding(nn.Module):
         dev = self._anchor.device
         native = self.native if native is None else native
         if self.clip_model is None:
+            if self.per_token:
+                raise GsddError("CLIPTextEmbedding(per_token=True) needs a text tower (weights=<directory>): the hash embedding has no tokens")
             rows = []
             for t in texts:
                 seed = int.from_bytes(hashlib.sha256(t.encode()).digest()[:8], "little")
@@ -93,11 +101,19 @@ class CLIPTextEmbedding(nn.Module):
         if native or (native is None and dev.type == "cuda"):
             ids = self.tokenize(texts)                             # host ids: the end-of-text positions cost no device sync
             eot = (ids == self.tokenizer.eos_token_id).int().argmax(dim=1)
+            if self.per_token:
+                # the token features of the recipe's fixed context (start + 20 + end = 22 positions, untrimmed: Te is one constant and
+                # the captured training step is not re-captured per batch); positions behind a caption's end-of-text are kept, as upstream
+                # VQ-Diffusion keeps them (its CrossAttention has no key mask)
+                ctx = self.MAX_TEXT_LEN + 2
+                return self._native_tower(dev)(ids[:, :ctx].contiguous(), eot=eot, trim=False, tokens=True)
             return self._native_tower(dev)(ids, eot=eot)
         ids = self.tokenize(texts).to(dev)
         # encode_text: token + positional embedding, causal transformer, ln_final, the feature AT THE END-OF-TEXT TOKEN times the text
         # projection.  (The zero padding behind it is invisible to that position under the causal mask.)
         hidden = self.clip_model.text_model(input_ids=ids, attention_mask=None).last_hidden_state
+        if self.per_token:
+            return hidden[:, :self.MAX_TEXT_LEN + 2].float()
         eot = (ids == self.tokenizer.eos_token_id).int().argmax(dim=1)
         pooled = hidden[torch.arange(ids.shape[0], device=dev), eot]
         return self.clip_model.text_projection(pooled).float()

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Time one D3PM training step (config C4 per-rank shape: bs 16, 16x16x16 tokens, 19 layers, K = 4096) on the HIP path."""
+"""Time one D3PM training step (config C4 per-rank shape: bs 16, 16x16x16 tokens, 19 layers, K = 4096) on the HIP path.
+usage: bench_train.py [B [steps]] [--cond-tokens N]   (N condition tokens per clip, default 1: the pooled text embedding)"""
 import os
 import sys
 import time
@@ -12,6 +13,11 @@ from gsdd_amd.d3pm_train import D3PMTrainer  # noqa: E402
 
 
 def main():
+    Te = 1
+    if "--cond-tokens" in sys.argv:
+        i = sys.argv.index("--cond-tokens")
+        Te = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     L, K = 4096, 4096
     torch.manual_seed(0)
@@ -23,7 +29,7 @@ def main():
     trainer = D3PMTrainer(dm, lr=1e-4)
     g = torch.Generator().manual_seed(1)
     tok = torch.randint(0, K, (B, L), generator=g).cuda()
-    cond = torch.zeros(B, 1, 512).cuda()
+    cond = torch.zeros(B, 1, 512).cuda() if Te == 1 else torch.randn(B, Te, 512, generator=g).cuda()
     losses = []
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     times = []

@@ -84,6 +84,43 @@ int main() {
         EXPECT(gsdd_d3pm_attention_bwd(q, k, v, o, nullptr, lse, B, L, H, dqkv, scratch, bws, bneed, 0, st), GSDD_E_ARG, false);
     }
 
+    // ---------------------------------------------------------------- cross-attention over Te condition tokens (training)
+    {
+        const int Te = 22;
+        float *q = devp(), *kc = devp(), *vc = devp(), *out = devp(), *lse = devp(), *dO = devp(), *dq = devp(), *dkc = devp(), *dvc = devp();
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, B, L, Te, H, out, lse, st), GSDD_OK, true);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, 3, 1, 77, 1, out, lse, st), GSDD_OK, true);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, B, L, 0, H, out, lse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, B, L, 78, H, out, lse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, 0, L, Te, H, out, lse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, kc, vc, B, L, Te, H, out, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_train(q, nullptr, vc, B, L, Te, H, out, lse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_train(nullptr, kc, vc, B, L, Te, H, out, lse, st), GSDD_E_ARG, false);
+        const int64_t need = gsdd_d3pm_cross_attention_bwd_workspace_bytes(B, L, Te, H);
+        if (need <= 0 || gsdd_d3pm_cross_attention_bwd_workspace_bytes(B, L, 77, H) <= need) {
+            std::fprintf(stderr, "FAIL gsdd_d3pm_cross_attention_bwd_workspace_bytes: %lld\n", (long long)need);
+            ++g_failed;
+        }
+        void* ws = devp<void>(need);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_OK, true);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, 3, 1, 1, 1, dq, dkc, dvc, ws, need, st), GSDD_OK, true);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, dkc, dvc, ws, need - 1, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, dkc, dvc, nullptr, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, 0, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, 78, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, nullptr, lse, B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, nullptr, B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, nullptr, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, nullptr, dvc, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, dkc, nullptr, ws, need, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, 0, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        // LayerNorm rows of any width (the text tower's per-token features)
+        EXPECT(gsdd_ln_apply(q, kc, vc, dO, 16 * 22, 512, out, st), GSDD_OK, true);
+        EXPECT(gsdd_ln_apply(q, kc, vc, dO, 16 * 22, 510, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_ln_apply(q, nullptr, vc, dO, 16 * 22, 512, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_ln_apply(q, kc, vc, dO, 0, 512, out, st), GSDD_E_ARG, false);
+    }
+
     // ---------------------------------------------------------------- fused layer
     {
         gsdd_layer_desc d;
