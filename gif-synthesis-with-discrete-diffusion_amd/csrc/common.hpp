@@ -257,4 +257,14 @@ bool axial_attention_mfma_launch(const float* qkv, int N, int T, int H, int W, i
 bool axial_attention_bwd_mfma_launch(const float* qkv, const float* datt, int N, int T, int H, int W, int C, int n_head, int axis,
                                      float* dqkv, hipStream_t st);
 
+// The LDS kernels of the axial attention (small_ops.hip forward, vqvae_bwd.hip backward) keep one (line, head) in dynamic LDS: q, k, v
+// (and dO) as [S][d + 1] plus one (two) [S][S] score images.  gsdd_axial_attention and gsdd_axial_attention_bwd accept exactly the same
+// shapes: every axis length S <= 64 whose BACKWARD image fits the 160 KiB a workgroup may hold (the forward image is never larger).
+constexpr int64_t AXIAL_LDS_CAP = 160 * 1024;
+inline int64_t axial_lds_bytes(int S, int d, bool backward) {
+    const int64_t rows = (int64_t)S * (d + 1), sq = (int64_t)S * S;
+    return (backward ? 4 * rows + 2 * sq : 3 * rows + sq) * (int64_t)sizeof(float);
+}
+inline bool axial_line_fits(int S, int d) { return S >= 1 && S <= 64 && d >= 1 && axial_lds_bytes(S, d, true) <= AXIAL_LDS_CAP; }
+
 }  // namespace gsdd

@@ -9,7 +9,7 @@ void set_error(const std::string& s) { g_err = s; }
 using namespace gsdd;
 
 extern "C" const char* gsdd_last_error(void) { return g_err.c_str(); }
-extern "C" int gsdd_version(void) { return 105; }
+extern "C" int gsdd_version(void) { return 106; }
 extern "C" int64_t gsdd_abi_sizeof(int which) {
     switch (which) {
         case 0: return (int64_t)sizeof(gsdd_gemm_desc);

@@ -557,17 +557,25 @@ extern "C" int gsdd_axial_attention_bwd(const float* qkv, const float* datt, int
     GSDD_CHECK_ARG(N > 0 && T > 0 && H > 0 && W > 0 && C > 0 && n_head > 0 && C % n_head == 0, "bad sizes");
     GSDD_CHECK_ARG(T <= 64 && H <= 64 && W <= 64, "axis length > 64 unsupported");
     const int d = C / n_head;
+    // the whole shape is judged before the first launch (the same rule as the forward: common.hpp)
+    GSDD_CHECK_ARG(axial_line_fits(W, d) && axial_line_fits(H, d) && axial_line_fits(T, d), "line does not fit LDS");
     const int axes_len[3] = {W, H, T};
     const int64_t pos = (int64_t)N * T * H * W;
     const bool force_valu = variant == GSDD_AXIAL_VALU;
+    const int longest = W > H ? (W > T ? W : T) : (H > T ? H : T);
+    if (axial_lds_bytes(longest, d, true) > 64 * 1024) {
+        GSDD_ONCE_PER_DEVICE(attr_done,
+            GSDD_CHECK_HIP(hipFuncSetAttribute((const void*)axial_attention_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)AXIAL_LDS_CAP));
+        );
+    }
     for (int axis = 0; axis < 3; ++axis) {
         if (!force_valu && axial_attention_bwd_mfma_launch(qkv, datt, N, T, H, W, C, n_head, axis, dqkv, (hipStream_t)stream)) {
             GSDD_CHECK_LAUNCH();
             continue;
         }
         const int S = axes_len[axis];
-        const size_t lds = (size_t)(4 * S * (d + 1) + 2 * S * S) * sizeof(float);
-        GSDD_CHECK_ARG(lds <= 64 * 1024, "line does not fit LDS");
+        const size_t lds = (size_t)axial_lds_bytes(S, d, true);
         hipLaunchKernelGGL(axial_attention_bwd_kernel, dim3((unsigned)(pos / S), n_head, 1), dim3(64), lds, (hipStream_t)stream, qkv,
                            datt, N, T, H, W, C, n_head, axis, dqkv);
         GSDD_CHECK_LAUNCH();

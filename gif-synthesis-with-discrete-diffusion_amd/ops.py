@@ -740,8 +740,8 @@ def lincomb(a, b, c, alpha, stream=None):
     return out
 
 
-def axial_attention_bwd(qkv, datt, dims, C_, n_head, valu=None, stream=None):
+def axial_attention_bwd(qkv, datt, dims, C_, n_head, valu=None, stream=None, out=None):
     N, T, H, W = dims
-    dqkv = torch.empty_like(qkv)
+    dqkv = out if out is not None else torch.empty_like(qkv)
     check(lib().gsdd_axial_attention_bwd(ptr(qkv), ptr(datt), N, T, H, W, C_, n_head, ptr(dqkv), axial_variant(valu), stream_ptr(stream)))
     return dqkv

@@ -104,9 +104,16 @@ int gsdd_ncdhw_to_rows(const float* x, int N, int C, int D, int H, int W, int Cp
  * qkv row layout: [9*C] = (axis a: q,k,v) for a in (w,h,t); out row layout [3*C] = (a_w|a_h|a_t).
  * Replaces AxialAttention + scaled_dot_product_attention: model_utils.py:318-337, :586-600. */
 #define GSDD_AXIAL_AUTO 0           /* register-resident MFMA kernel where the line length and head dim allow (16-position lines) */
-#define GSDD_AXIAL_VALU 1           /* the LDS / vector kernel for every axis (any line length <= 64): the cross-check variant    */
+#define GSDD_AXIAL_VALU 1           /* the LDS / vector kernel for every axis: the cross-check variant                            */
 int gsdd_axial_attention(const float* qkv, int N, int T, int H, int W, int C, int n_head,
                          float* out, int variant, void* stream);
+/* Shapes.  gsdd_axial_attention and gsdd_axial_attention_bwd accept exactly the same (T, H, W, C, n_head), whatever the variant:
+ * C % n_head == 0 and, with d = C / n_head, every axis length S in 1 .. 64 with (4 S (d + 1) + 2 S^2) * 4 <= 163,840 -- the bytes
+ * of LDS the backward LDS kernel keeps per (line, head) against the 160 KiB of a workgroup (the forward keeps (3 S (d + 1) + S^2) * 4,
+ * never more).  That is every S <= 64 at d <= 64, S <= 63 at d = 128, S <= 37 at d = 256.  Anything else is GSDD_E_ARG from both,
+ * decided for all three axes before the first launch: a refused call has written nothing.
+ * gsdd_axial_attention_lds_bytes: those bytes (backward != 0: of the backward kernel) for one axis, or -1 where (S, d) is refused. */
+int64_t gsdd_axial_attention_lds_bytes(int S, int d, int backward);
 
 /* Nearest codebook entry: idx[m] = argmin_k (|z_m|^2 - 2 z_m.e_k + |e_k|^2), first minimum wins.
  * Replaces Codebook.forward distance+argmin: videogpt_vq_vae.py:178-183.

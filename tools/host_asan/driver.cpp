@@ -333,6 +333,25 @@ int main() {
         EXPECT(gsdd_axial_attention(devp(), 2, 16, 16, 16, 256, 2, devp(), 5, st), GSDD_E_ARG, false);
         EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 2, 16, 16, 16, 256, 2, devp(), GSDD_AXIAL_AUTO, st), GSDD_OK, true);
         EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 2, 16, 16, 16, 256, 2, devp(), -2, st), GSDD_E_ARG, false);
+        // one rule for both directions, judged before the first launch: lines above 64 KB of LDS run (the attribute is requested for
+        // them), S = 64 at d = 128 is refused by both although its W and H axes could have been launched
+        for (int variant = GSDD_AXIAL_AUTO; variant <= GSDD_AXIAL_VALU; ++variant) {
+            EXPECT(gsdd_axial_attention(devp(), 1, 4, 32, 32, 256, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 1, 4, 32, 32, 256, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention(devp(), 1, 63, 64, 64, 128, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 1, 63, 64, 64, 128, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention(devp(), 1, 63, 1, 1, 256, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 1, 63, 1, 1, 256, 2, devp(), variant, st), GSDD_OK, true);
+            EXPECT(gsdd_axial_attention(devp(), 1, 64, 16, 16, 256, 2, devp(), variant, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 1, 64, 16, 16, 256, 2, devp(), variant, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_axial_attention(devp(), 1, 2, 2, 65, 8, 2, devp(), variant, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_axial_attention_bwd(devp(), devp(), 1, 2, 2, 65, 8, 2, devp(), variant, st), GSDD_E_ARG, false);
+        }
+        if (gsdd_axial_attention_lds_bytes(64, 64, 1) != 99328 || gsdd_axial_attention_lds_bytes(32, 128, 0) != 53632 ||
+            gsdd_axial_attention_lds_bytes(64, 128, 0) != -1 || gsdd_axial_attention_lds_bytes(0, 8, 0) != -1) {
+            std::fprintf(stderr, "FAIL gsdd_axial_attention_lds_bytes\n");
+            ++g_failed;
+        }
         // the generic GEMM at the decoder's largest shape, both back ends, and the weight gradient
         gsdd_gemm_desc g;
         std::memset(&g, 0, sizeof g);
