@@ -8,7 +8,7 @@ The directory name carries a hyphen, so import it through the root-level ``gsdd_
 from . import ops  # noqa: F401
 from ._lib import GsddError, LIB_PATH, EXPORTS, lib  # noqa: F401
 from .d3pm import (DalleMaskImageEmbedding, DiffusionTransformer, DiscreteDiffusion,  # noqa: F401
-                   Text2ImageTransformer)
+                   Text2ImageTransformer, cond_drop_rows)
 from .i3d import InceptionI3d  # noqa: F401
 from .text import ClipTextTower  # noqa: F401
 from .vqvae import VQVAE  # noqa: F401

@@ -21,6 +21,7 @@ EXPORTS = [
     "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan", "gsdd_d3pm_forward_jump",
     "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
     "gsdd_ln_apply", "gsdd_d3pm_cross_attention_train", "gsdd_d3pm_cross_attention_bwd", "gsdd_d3pm_cross_attention_bwd_workspace_bytes",
+    "gsdd_cond_dropout", "gsdd_cond_null_grad", "gsdd_set_deterministic",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
 ]
@@ -202,7 +203,10 @@ def lib():
         L.gsdd_text_embed.argtypes = [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]
         L.gsdd_text_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]
         L.gsdd_text_pool.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p]
-        L.gsdd_philox_uniform.argtypes = [C.c_uint64, _i64, _i64, _i64, _i, _p, _p]
+        L.gsdd_set_deterministic.argtypes = [_i]
+        L.gsdd_cond_dropout.argtypes = [_p, _p, _i, _i, _i, C.c_float, C.c_uint64, _p, _i64, _p, _p, _p, _p]
+        L.gsdd_cond_null_grad.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]
+        L.gsdd_philox_uniform.argtypes =[C.c_uint64, _i64, _i64, _i64, _i, _p, _p]
         L.gsdd_graph_begin.argtypes = [_p]
         L.gsdd_graph_end.argtypes = [_p, C.POINTER(_p)]
         L.gsdd_graph_launch.argtypes = [_p, _p]

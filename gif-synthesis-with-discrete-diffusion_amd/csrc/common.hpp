@@ -12,6 +12,7 @@
 namespace gsdd {
 
 void set_error(const std::string& s);
+int deterministic();            // gsdd_set_deterministic: the gradient reductions of the training step in their reproducible form
 
 #define GSDD_CHECK_ARG(cond, msg)                                                      \
     do {                                                                               \

@@ -430,6 +430,30 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* dx, const i
     }
 }
 
+// Reproducible form (gsdd_set_deterministic): one thread per (table row or position, column) walks all rows in ascending order and adds
+// the ones that are its own -- no atomics, one writer per address.  O((n_embed + L) rows) reads per column: meant for tests and
+// reproducibility runs, not for the production shape.
+__global__ __launch_bounds__(256) void embed_bwd_det_kernel(const float* dx, const int64_t* tok, int64_t rows, int L, int D, int n_embed,
+                                                            float* demb, float* dpos) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)(n_embed + L) * D) return;
+    const int e = (int)(i / D), c = (int)(i % D);
+    float s = 0.f;
+    if (e < n_embed) {
+        bool any = false;
+        for (int64_t row = 0; row < rows; ++row) {
+            int64_t t = tok[row];
+            t = t < 0 ? 0 : (t >= n_embed ? n_embed - 1 : t);
+            if (t == e) { s += dx[row * D + c]; any = true; }
+        }
+        if (any) demb[(int64_t)e * D + c] += s;
+    } else {
+        const int l = e - n_embed;
+        for (int64_t row = l; row < rows; row += L) s += dx[row * D + c];
+        dpos[(int64_t)l * D + c] += s;
+    }
+}
+
 // ------------------------------------------------------------------ tiny linears over a handful of rows (one thread per output)
 // y[r][j] = W[j][:] . x[r][:] + b[j] backward:  dx[r][k] = sum_j dy[r][j] W[j][k] ; dW[j][k] += sum_r dy[r][j] x[r][k] ; db[j] += sum_r dy
 __global__ void small_linear_bwd_kernel(const float* dy, const float* x, const float* w, int R, int Cin, int Cout, float* dx,
@@ -462,7 +486,7 @@ __global__ void small_linear_bwd_kernel(const float* dy, const float* x, const f
 // walks B dependent (t[b] -> emb row) loads with an expf each, which made this 58 us of pure latency per layer.
 template <bool SMEM>
 __global__ __launch_bounds__(256) void adaln_bwd_kernel(const float* dtab, const int64_t* t, int B, int D, const float* emb, const float* w,
-                                                        float* demb, float* dw, float* db) {
+                                                        float* demb, float* dw, float* db, int det) {
     extern __shared__ float adaln_lds[];
     float* sl = adaln_lds;                 // silu(e)   [B][D]
     float* dsl = adaln_lds + B * D;        // silu'(e)  [B][D]
@@ -503,7 +527,24 @@ __global__ __launch_bounds__(256) void adaln_bwd_kernel(const float* dtab, const
         float ds;
         if (SMEM) ds = dsl[i];
         else { const float e = emb[t[b] * D + k]; const float sg = 1.f / (1.f + expf(-e)); ds = sg * (1.f + e * (1.f - sg)); }
-        atomicAdd(demb + t[b] * D + k, s * ds);
+        if (!det) {
+            atomicAdd(demb + t[b] * D + k, s * ds);
+        } else {
+            // reproducible form: the first batch element of every timestep adds the shares of all batch elements with that timestep, in
+            // ascending b, with a plain store (one writer per address)
+            bool first = true;
+            for (int b2 = 0; b2 < b; ++b2) first = first && t[b2] != t[b];
+            if (first) {
+                float total = s * ds;
+                for (int b2 = b + 1; b2 < B; ++b2) {
+                    if (t[b2] != t[b]) continue;
+                    float s2 = 0.f;
+                    for (int j = 0; j < D2; ++j) s2 = fmaf(dtab[b2 * D2 + j], w[(int64_t)j * D + k], s2);
+                    total += s2 * ds;                      // (the same timestep: the same e, the same silu')
+                }
+                demb[t[b] * D + k] += total;
+            }
+        }
     }
 }
 
@@ -612,6 +653,29 @@ extern "C" int gsdd_ln_bwd(const float* dh, const float* x, const float* stats, 
     GSDD_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "dgamma/dbeta come together");
     // 16-row groups per block: fewer, fatter atomics.  With acc_by_batch a block's rows must not span two batch elements at rit > 1;
     // when rows_per_batch % 16 != 0 (rit = 1) the blocks that do span two take a per-row atomic path
+    if (deterministic() && dgamma != nullptr && M < (1ll << 30)) {
+        // reproducible form: every gamma / beta gradient address gets the sum of ONE block (fixed order inside it) -- one block for the
+        // whole call, or one launch of one block per batch element when the sums go to per-batch slots
+        if (!acc_by_batch) {
+            const int rit1 = (int)((M + 15) / 16);
+            hipLaunchKernelGGL(ln_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dh, x, stats, gamma, sel, gstride, rows_per_batch,
+                               M, dx_in, dx_out, dgamma, dbeta, gacc_stride, 0, rit1);
+            GSDD_CHECK_LAUNCH();
+            return GSDD_OK;
+        }
+        if (M % rows_per_batch == 0) {
+            const int64_t R = rows_per_batch;
+            const int rit1 = (int)((R + 15) / 16);
+            for (int64_t b = 0; b < M / R; ++b) {
+                hipLaunchKernelGGL(ln_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dh + b * R * 64, x + b * R * 64,
+                                   stats + 2 * b * R, gamma, sel != nullptr ? sel + b : nullptr, gstride, rows_per_batch, R,
+                                   dx_in != nullptr ? dx_in + b * R * 64 : nullptr, dx_out + b * R * 64, dgamma + b * gacc_stride,
+                                   dbeta + b * gacc_stride, gacc_stride, 0, rit1);
+                GSDD_CHECK_LAUNCH();
+            }
+            return GSDD_OK;
+        }
+    }
     int rit = 4;
     while (rit > 1 && ((acc_by_batch && rows_per_batch % (16 * rit) != 0) || M < (int64_t)16 * rit * 512)) rit >>= 1;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)((M + 16 * rit - 1) / (16 * rit))), dim3(256), 0, (hipStream_t)stream, dh, x, stats,
@@ -629,6 +693,8 @@ extern "C" int gsdd_wgrad(const float* dY, int ldy, const float* X, int ldx, int
     int slabs = 8;
     const int64_t tiles = (int64_t)((N + 63) / 64) * ((K + 63) / 64);
     while (slabs > 1 && ((M + (int64_t)WG_ROWS * slabs - 1) / ((int64_t)WG_ROWS * slabs)) * tiles < 512) slabs >>= 1;
+    // reproducible form: one workgroup per output tile walks all rows, so every dW / db address gets a single add
+    if (deterministic() && M < (1ll << 30)) slabs = (int)((M + WG_ROWS - 1) / WG_ROWS);
     const dim3 grid((unsigned)((M + (int64_t)WG_ROWS * slabs - 1) / ((int64_t)WG_ROWS * slabs)), (N + 63) / 64, (K + 63) / 64);
     hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, dY, ldy, X, ldx, M, N, K, dW, slabs, db);
     GSDD_CHECK_LAUNCH();
@@ -637,7 +703,9 @@ extern "C" int gsdd_wgrad(const float* dY, int ldy, const float* X, int ldx, int
 
 extern "C" int gsdd_colsum(const float* Y, int ld, int64_t M, int N, float* out, void* stream) {
     GSDD_CHECK_ARG(Y && out && M > 0 && N > 0, "bad args");
-    const int cpb = colsum_cpb(N), rows = (N <= 256 && M < 262144) ? 64 : 256;
+    const int cpb = colsum_cpb(N);
+    // (reproducible form: one block per column group takes all rows)
+    const int rows = (deterministic() && M < (1ll << 30)) ? (int)M : ((N <= 256 && M < 262144) ? 64 : 256);
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((M + rows - 1) / rows), (N + cpb - 1) / cpb), dim3(256), 0,
                        (hipStream_t)stream, Y, ld, M, N, out, cpb, rows);
     GSDD_CHECK_LAUNCH();
@@ -648,6 +716,14 @@ extern "C" int gsdd_batch_rowsum(const float* Y, int B, int L, int C, float* out
     GSDD_CHECK_ARG(Y && out && B > 0 && L > 0 && C > 0, "bad args");
     GSDD_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)B * C * sizeof(float), (hipStream_t)stream));
     const int cpb = colsum_cpb(C);
+    if (deterministic()) {                         // reproducible form: the column sums of one batch element by one block per column group
+        for (int b = 0; b < B; ++b) {
+            hipLaunchKernelGGL(colsum_kernel, dim3(1, (C + cpb - 1) / cpb), dim3(256), 0, (hipStream_t)stream, Y + (int64_t)b * L * C, C,
+                               (int64_t)L, C, out + (int64_t)b * C, cpb, L);
+            GSDD_CHECK_LAUNCH();
+        }
+        return GSDD_OK;
+    }
     hipLaunchKernelGGL(batch_rowsum_kernel, dim3((L + CS_ROWS - 1) / CS_ROWS, (C + cpb - 1) / cpb, B), dim3(256), 0, (hipStream_t)stream,
                        Y, L, C, out, cpb);
     GSDD_CHECK_LAUNCH();
@@ -705,6 +781,15 @@ extern "C" int gsdd_d3pm_embed_bwd(const float* dx, const int64_t* tok, int B, i
                                    float* dpos, void* stream) {
     GSDD_CHECK_ARG(dx && tok && demb && dpos && B > 0 && L > 0 && D % 4 == 0, "bad args");
     const int64_t rows = (int64_t)B * L;
+    if (deterministic()) {
+        GSDD_CHECK_ARG(n_embed > 0, "bad args");
+        const int64_t n = (int64_t)(n_embed + L) * D;
+        GSDD_CHECK_ARG((n + 255) / 256 < (1ll << 31), "too many elements");
+        hipLaunchKernelGGL(embed_bwd_det_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dx, tok, rows, L, D,
+                           n_embed, demb, dpos);
+        GSDD_CHECK_LAUNCH();
+        return GSDD_OK;
+    }
     hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((rows + EB_ROWS - 1) / EB_ROWS)), dim3(256), 0, (hipStream_t)stream, dx, tok,
                        rows, L, D, n_embed, demb, dpos);
     GSDD_CHECK_LAUNCH();
@@ -730,10 +815,10 @@ extern "C" int gsdd_adaln_bwd(const float* dtab, const int64_t* t, int B, int D,
     const size_t lds = (size_t)2 * B * D * sizeof(float);
     if (lds <= 48 * 1024)
         hipLaunchKernelGGL(adaln_bwd_kernel<true>, dim3((n + 255) / 256), dim3(256), lds, (hipStream_t)stream, dtab, t, B, D, emb, w, demb,
-                           dw, db);
+                           dw, db, deterministic());
     else
         hipLaunchKernelGGL(adaln_bwd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dtab, t, B, D, emb, w, demb,
-                           dw, db);
+                           dw, db, deterministic());
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }

@@ -4,12 +4,15 @@
 namespace gsdd {
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
+static std::atomic<int> g_deterministic{0};
+int deterministic() { return g_deterministic.load(std::memory_order_relaxed); }
 }  // namespace gsdd
 
 using namespace gsdd;
 
 extern "C" const char* gsdd_last_error(void) { return g_err.c_str(); }
-extern "C" int gsdd_version(void) { return 106; }
+extern "C" int gsdd_version(void) { return 108; }
+extern "C" int gsdd_set_deterministic(int on) { return g_deterministic.exchange(on != 0 ? 1 : 0); }
 extern "C" int64_t gsdd_abi_sizeof(int which) {
     switch (which) {
         case 0: return (int64_t)sizeof(gsdd_gemm_desc);

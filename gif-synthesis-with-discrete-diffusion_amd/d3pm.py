@@ -14,6 +14,7 @@ import numbers
 import os
 import types
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -602,6 +603,33 @@ def check_truncation_rate(rate, name="truncation_rate"):
     return float(rate)
 
 
+def check_cond_drop_prob(p, name="cond_drop_prob"):
+    """-> the probability as a float; None is 0 (no condition dropout).  Anything but a real number in [0, 1] raises."""
+    if p is None:
+        return 0.0
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0 <= p <= 1:
+        raise GsddError(f"{name} must be null or a real number in [0, 1], got {p!r}")
+    return float(p)
+
+
+def cond_drop_rows(seed, stream, B, row0, p):
+    """The drop flags gsdd_cond_dropout draws for global sample rows row0 .. row0 + B - 1 (numpy restatement): row r is dropped iff
+    u < float32(p), u = (w >> 8) * 2^-24, w = word 0 of Philox4x32-10 with key `seed` and counter (r [64 bit], stream, 1).  `stream` is
+    the stream id of the step's q_sample draw; every other draw has 0 in counter word 3.  -> bool (B,)"""
+    rows = np.arange(B, dtype=np.uint64) + np.uint64(row0)
+    c0, c1 = (rows & np.uint64(0xFFFFFFFF)).astype(np.uint32), (rows >> np.uint64(32)).astype(np.uint32)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    c2, c3 = np.full(B, int(stream) & 0xFFFFFFFF, dtype=np.uint64), np.ones(B, dtype=np.uint64)
+    c0, c1 = c0.astype(np.uint64), c1.astype(np.uint64)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & np.uint64(0xFFFFFFFF),
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & np.uint64(0xFFFFFFFF))
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    u = (c0.astype(np.uint32) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return u < np.float32(p)
+
+
 def _trunc_kwargs(rate):
     """The keyword a truncated launch adds to ops.d3pm_step / ops.d3pm_purity_step; nothing at all without truncation."""
     return {} if rate is None else {"trunc_rate": float(rate)}
@@ -723,6 +751,8 @@ class DiffusionTransformer(nn.Module):
         self.update_n_sample()
         self.truncation_rate = None  # None: no truncation; 0 < r < 1: top-r truncated sampling (upstream's "top0.86r" is 0.86)
         self.learnable_cf = learnable_cf
+        self.cond_drop_prob = 0.0    # training: probability that a sample's condition is replaced by the null condition (classifier-free
+                                     # training; the null condition is empty_text_embed[:Te] with learnable_cf, else the caller's)
         self.guidance_scale = guidance_scale
         self.noise_seed = 0          # Philox key; the stream id advances with every draw
         self.noise_stream = 0
@@ -740,6 +770,41 @@ class DiffusionTransformer(nn.Module):
 
     def _sched(self):
         return [getattr(self, n) for n in SCHED_ORDER]
+
+    def check_learned_null(self, Te, cond_dim):
+        rows, width = self.empty_text_embed.shape
+        if Te > rows or cond_dim != width:
+            raise GsddError(f"learnable_cf: the learned null embedding is ({rows}, {width}); the condition has Te = {Te} tokens of "
+                            f"width {cond_dim} (needs Te <= {rows} and cond_dim == {width})")
+
+    def null_condition(self, Te, cond_dim, null_cond=None):
+        """-> the (Te, cond_dim) f32 null condition of classifier-free training and guidance: with learnable_cf rows [:Te] of
+        empty_text_embed rounded to f32 (Improved VQ-Diffusion's learned null embedding; diffusion_transformer.py:541-543), else the
+        caller's `null_cond`, (Te, cond_dim) or (1, Te, cond_dim)."""
+        if self.learnable_cf:
+            self.check_learned_null(Te, cond_dim)
+            return self.empty_text_embed.detach()[:Te].float().contiguous()
+        if Te > 77:
+            raise GsddError(f"the null condition holds up to 77 condition tokens, got Te = {Te}")
+        if null_cond is None:
+            raise GsddError("condition dropout without learnable_cf needs a null condition (null_cond / "
+                            "input['null_condition_embed_token']): the (Te, cond_dim) embedding that stands for 'no caption'")
+        n = null_cond[0] if (null_cond.dim() == 3 and null_cond.shape[0] == 1) else null_cond
+        if tuple(n.shape) != (Te, cond_dim):
+            raise GsddError(f"the null condition must be (Te, cond_dim) = {(Te, cond_dim)} or (1, Te, cond_dim), got {tuple(null_cond.shape)}")
+        return n.detach().float().contiguous()
+
+    def _cf_embed(self, condition_embed, cf_condition_embed):
+        """The unconditional condition of a guided sampling call: the caller's, else (learnable_cf) the learned null rows repeated over
+        the batch."""
+        guided = abs(self.guidance_scale - 1) >= 1e-3
+        if cf_condition_embed is not None or not guided:
+            return cf_condition_embed
+        if not self.learnable_cf:
+            raise GsddError("guided sampling (guidance_scale != 1) needs cf_condition_embed")
+        cond = condition_embed if condition_embed.dim() == 3 else condition_embed.unsqueeze(1)
+        B, Te, cd = cond.shape
+        return self.null_condition(Te, cd).to(cond.device).unsqueeze(0).expand(B, Te, cd).contiguous()
 
     def _jump_table(self, jump, dev):
         """The device copy of jump_table(T, K, jump), made once per jump (and device)."""
@@ -815,6 +880,7 @@ class DiffusionTransformer(nn.Module):
         resample_times = 1: the call without them, launch for launch."""
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
         if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
             raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
         known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
@@ -857,8 +923,7 @@ class DiffusionTransformer(nn.Module):
                             "must be 0 (diffusion_transformer.py:686)")
         if isinstance(skip_step, bool) or not isinstance(skip_step, numbers.Integral) or skip_step < 0:
             raise GsddError(f"skip_step must be a non-negative int, got {skip_step!r}")
-        if abs(self.guidance_scale - 1) >= 1e-3 and cf_condition_embed is None:
-            raise GsddError("guided sampling (guidance_scale != 1) needs cf_condition_embed")
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
         return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
@@ -1149,8 +1214,11 @@ class DiffusionTransformer(nn.Module):
             raise NotImplementedError("cond_emb=None is not used by the reference call sites")
         if torch.is_grad_enabled() and is_train and self.training and any(p.requires_grad for p in self.transformer.parameters()):
             # the loss carries a grad_fn into the HIP backward (d3pm_train.py): loss.backward() fills the transformer's .grad
+            # (condition dropout -- cond_drop_prob, or the explicit input["condition_drop"] (B,) bool mask -- applies here only: the
+            # no-grad objective below and the sampler never drop a condition)
             from .d3pm_train import train_forward
-            loss, r = train_forward(self, tok, cond.float(), want_probs=return_logits)
+            loss, r = train_forward(self, tok, cond.float(), want_probs=return_logits, null_cond=input.get("null_condition_embed_token"),
+                                    drop=input.get("condition_drop"))
             out = {"pred_data": r["x0_recon"]}
             if return_logits:
                 out["logits"] = r["probs"]
@@ -1240,19 +1308,27 @@ class DiscreteDiffusion(nn.Module):
     those latent frames of the input clip (its own codes) and samples the rest (frame prediction / interpolation; `frame_mask`);
     sample_known_mode "renoise" / "hold" is the sampler's known_mode.  Not with sample_prior_rule > 0.
     sample_resample_jump / sample_resample_times: the sampler's resample_jump / resample_times (RePaint's resampling jumps), handed to
-    sample() when a mask is in use; null leaves the plain known chain.  Not with sample_skip_step (sample_fast has no jumps)."""
+    sample() when a mask is in use; null leaves the plain known chain.  Not with sample_skip_step (sample_fast has no jumps).
+    train_cond_drop_prob: null, or the probability in [0, 1] with which a training sample's text condition is replaced by the null
+    condition (classifier-free training; sets the diffusion model's cond_drop_prob).  The null condition is the learned
+    empty_text_embed when the diffusion model has learnable_cf, else the provider's embedding of "" -- the unconditional branch the
+    sampler guides with."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
                  sample_condition_frames=None, sample_known_mode="renoise", sample_resample_jump=None, sample_resample_times=None,
-                 **kwargs):
+                 train_cond_drop_prob=None, **kwargs):
         super().__init__()
+        p_drop = None if train_cond_drop_prob is None else check_cond_drop_prob(train_cond_drop_prob, "train_cond_drop_prob")
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
         if not isinstance(diffusion_model, nn.Module):
             diffusion_model = _instantiate(diffusion_model)
         self.textencoder = textencoder
         self.diffusion_model = diffusion_model
+        if p_drop is not None:
+            diffusion_model.cond_drop_prob = p_drop
+        self._null_text = None         # the provider's embedding of "" (1, Te, C): the null condition without learnable_cf
         self.zero_text_emb = bool(zero_text_emb)
         if sample_skip_step is not None and (isinstance(sample_skip_step, bool) or not isinstance(sample_skip_step, numbers.Integral)
                                              or sample_skip_step < 0):
@@ -1324,6 +1400,17 @@ class DiscreteDiffusion(nn.Module):
         emb = (emb.unsqueeze(1) if emb.dim() == 2 else emb).to(dev)
         return torch.zeros_like(emb) if self.zero_text_emb else emb.float()
 
+    def null_condition(self, dev):
+        """The null condition a training step with condition dropout needs from the caller: None when nothing is dropped or the
+        diffusion model learns its own (learnable_cf), else the provider's embedding of "" (1, Te, C), computed once."""
+        dm = self.diffusion_model
+        if not getattr(dm, "cond_drop_prob", 0.0) or dm.learnable_cf:
+            return None
+        if self._null_text is None or self._null_text.device != torch.device(dev):
+            with torch.no_grad():
+                self._null_text = self._text([""], dev)
+        return self._null_text
+
     def forward(self, batch, autoencoder, length_estimator=None, do_inference=False):
         """discrete_diffusion.py:16-83: encode -> diffusion objective -> [sample] -> decode; same output-dict keys.
         `losses` carries the HIP backward's grad_fn when autograd is enabled and the denoiser is in train mode, so the caller's
@@ -1340,7 +1427,8 @@ class DiscreteDiffusion(nn.Module):
         quant_flat = quant.view(x.shape[0], -1)
         with torch.no_grad():
             text_emb = self._text(batch["text"], dev)
-        diffusion_out = self.diffusion_model({"condition_embed_token": text_emb, "content_token": quant_flat},
+        diffusion_out = self.diffusion_model({"condition_embed_token": text_emb, "content_token": quant_flat,
+                                              "null_condition_embed_token": self.null_condition(dev)},
                                              return_loss=True, return_logits=False)   # (`logits` = exp(log_model_prob), a (B, K+1, L)
         # tensor the reference computes here and never reads (discrete_diffusion.py:38-41, :66-81): not asked for, so the loss and its gradient take the one-pass kernel)
         # arg-max over K+1 classes can only return [MASK] when every code row sits at the -70 clamp; the reference would
@@ -1388,8 +1476,11 @@ class DiscreteDiffusion(nn.Module):
         B = len(texts)
         if text_emb is None:
             text_emb = self._text(texts, dev)
-        cf_emb = self._text([""] * B, dev)                                              # :46-49
         dm = self.diffusion_model
+        if dm.learnable_cf:                     # the learned null embedding is the unconditional condition (diffusion_transformer.py:541-543)
+            cf_emb = dm._cf_embed(text_emb, None)
+        else:
+            cf_emb = self._text([""] * B, dev)                                          # :46-49
         if self.sample_prior_rule is not None:
             dm.prior_rule = self.sample_prior_rule
         if self.sample_prior_weight is not None:

@@ -96,8 +96,13 @@ class _LinearImages:
 
 
 class D3PMTrainer:
-    def __init__(self, dm, lr=1e-4, betas=(0.5, 0.999), eps=1e-8):
+    def __init__(self, dm, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, deterministic=None):
+        """deterministic: True runs the backward's reductions in their reproducible form (ops.set_deterministic: one workgroup per
+        output address instead of float atomics) -- two calls on the same inputs then give the same gradient bits, at a cost in step
+        time; None reads GSDD_TRAIN_DETERMINISTIC=1.  The default (False) is the fast form, whose gradients differ from run to run in
+        their last bits."""
         self.dm, self.lr, self.betas, self.eps = dm, lr, betas, eps
+        self.deterministic = (os.environ.get("GSDD_TRAIN_DETERMINISTIC") == "1") if deterministic is None else bool(deterministic)
         self.step_count = 0
         self.state = {}
         self.reducer = GradReducer()
@@ -206,14 +211,76 @@ class D3PMTrainer:
         return sv
 
     # ------------------------------------------------------------------ loss + gradients
+    # ------------------------------------------------------------------ classifier-free training: condition dropout
+    NULL_NAME = "empty_text_embed"       # the learned null embedding in the gradient dict and the optimiser's parameter list
+
+    def _dropout_plan(self, cond, null_cond, drop):
+        """Validates the step's condition dropout on the host (no device call) -> None when the step drops nothing (cond_drop_prob == 0
+        and no mask: the step then launches exactly what it launches without the feature), else (p, learnable)."""
+        dm = self.dm
+        from .d3pm import check_cond_drop_prob
+        p = check_cond_drop_prob(getattr(dm, "cond_drop_prob", 0.0))
+        if p == 0.0 and drop is None:
+            return None
+        if cond.dim() != 3:
+            raise GsddError(f"the condition must be (B, Te, cond_dim), got {tuple(cond.shape)}")
+        B, Te, cd = cond.shape
+        if drop is not None and (drop.dtype not in (torch.bool, torch.uint8) or tuple(drop.shape) != (B,)):
+            raise GsddError(f"the drop mask must be a bool (B,) = {(B,)} tensor, got {tuple(drop.shape)} {drop.dtype}")
+        if cd % 4 != 0:
+            raise GsddError(f"condition dropout needs cond_dim % 4 == 0, got {cd}")
+        learnable = bool(dm.learnable_cf)
+        if learnable:
+            dm.check_learned_null(Te, cd)
+        elif null_cond is None or Te > 77:
+            dm.null_condition(Te, cd, None)                        # (raises: no null condition, or more tokens than the kernel takes)
+        return p, learnable
+
+    def _drop_condition(self, cond, plan, null_cond, drop, sid):
+        """-> (condition with the dropped samples' rows replaced by the null rows, the uint8 (B,) decisions).  With learnable_cf the null
+        rows are the first Te of an f32 copy of dm.empty_text_embed made here, every step: the fp64 parameter stays the single source of
+        truth (load_state_dict, a torch optimiser and a resumed run need no bookkeeping)."""
+        dm = self.dm
+        p, learnable = plan
+        B, Te, cd = cond.shape
+        dev = cond.device
+        if learnable:
+            if getattr(self, "_null32", None) is None or self._null32.device != dev:
+                self._null32 = torch.empty(tuple(dm.empty_text_embed.shape), dtype=torch.float32, device=dev)
+            self._null32.copy_(dm.empty_text_embed.detach())                   # fp64 -> f32, one copy node
+            rows = self._null32[:Te]
+        else:
+            rows = dm.null_condition(Te, cd, null_cond).to(dev)
+        if drop is not None:
+            drop = drop.to(dev)
+            drop = (drop if drop.dtype == torch.uint8 else drop.to(torch.uint8)).contiguous()
+        return ops.cond_dropout(cond, rows, p, seed=dm.noise_seed, sid=sid, row0=dm.row_offset, drop=drop)
+
+    def loss_and_grads(self, *args, **kwargs):
+        """`_loss_and_grads` (see there), bracketed by the reproducible-reductions switch when the trainer is `deterministic`."""
+        if not self.deterministic:
+            return self._loss_and_grads(*args, **kwargs)
+        prev = ops.set_deterministic(True)
+        try:
+            return self._loss_and_grads(*args, **kwargs)
+        finally:
+            ops.set_deterministic(prev)
+
     @torch.no_grad()
-    def loss_and_grads(self, x0, cond, t=None, pt=None, want_probs=False, reduce=False, sid=None):
+    def _loss_and_grads(self, x0, cond, t=None, pt=None, want_probs=False, reduce=False, sid=None, null_cond=None, drop=None):
         """-> (loss tensor [1], {state_dict name: gradient}) for the transformer's parameters.  The gradients are views of one
         arena that the next call re-uses; `self.last_fwd` keeps the forward's dict (x0_recon, per_sample, probs if asked).
         reduce=True: the gradients come back averaged over the data-parallel group; the all-reduce runs in buckets of
         BUCKET_LAYERS blocks issued while the backward of the earlier blocks is still being enqueued.
         sid: int64[1] device tensor holding the Philox stream id of this step's q_sample draw (the captured step keeps it on the device);
-        None: made from dm.noise_stream."""
+        None: made from dm.noise_stream.
+        Condition dropout (classifier-free training): with dm.cond_drop_prob = p > 0 sample b's (Te, cond_dim) condition rows are
+        replaced by the null condition iff u_b < p, u_b drawn on the device from (noise_seed, global sample row, this step's stream id)
+        -- `cond_drop_rows` restates it; the draw shares no counter with q_sample's, so x_t is that of the step without dropout.
+        `drop`, a (B,) bool mask, overrides the draw.  The null condition is dm.empty_text_embed[:Te] with dm.learnable_cf -- the
+        gradient dict then carries its gradient under "empty_text_embed", (77, 512) with rows >= Te exactly zero -- else `null_cond`,
+        (Te, cond_dim) or (1, Te, cond_dim).  `self.last_drop` keeps the uint8 (B,) decisions (None: no dropout in this step)."""
+        plan = self._dropout_plan(cond, null_cond, drop)
         self._sync_start()
         dm, tr = self.dm, self.dm.transformer
         if not x0.is_cuda:
@@ -234,6 +301,9 @@ class D3PMTrainer:
         x0 = x0.contiguous().long()
         xt = torch.empty_like(x0)
         ops.d3pm_q_sample(x0, xt, sched, t, sid, K=K, T=T, seed=dm.noise_seed, row0=dm.row_offset * L)
+        self.last_drop = None
+        if plan is not None:          # the substituted condition is what the forward, every saved activation and every gradient see
+            cond, self.last_drop = self._drop_condition(cond.to(dev).float().contiguous(), plan, null_cond, drop, sid)
         sv = self._forward(xt, cond, t)
         kw = dict(K=K, T=T, mask_weight=dm.mask_weight, aux_weight=dm.auxiliary_loss_weight,
                   adaptive_aux=dm.adaptive_auxiliary_loss)
@@ -264,6 +334,10 @@ class D3PMTrainer:
 
         def tw(w):                              # transposed copy for the data-gradient GEMMs
             return w.t().contiguous()
+
+        # the learned null embedding's gradient: every block leaves its (dk2, dv2, Wk2, Wv2) here; the sums over the dropped samples
+        # are formed after the last block, into the arena's last gradient (a bucket that is already out must not be written again)
+        null_terms = [] if (plan is not None and plan[1]) else None
 
         # ---- to_logits
         ops.wgrad(dlogits, sv["hf"], z("to_logits.1.weight", p["wl"]), z("to_logits.1.bias", p["bl"]))
@@ -309,6 +383,8 @@ class D3PMTrainer:
                                      z(pre + "attn2.key.bias", lay["bk2"]), want_dx=False)
                 ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
                                      z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+                if null_terms is not None:
+                    null_terms.append((dk2, dv2, lay["wk2"], lay["wv2"]))
                 ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
             else:
                 # ---- attention output projection + the broadcast cross-attention vector
@@ -318,6 +394,8 @@ class D3PMTrainer:
                                            z(pre + "attn2.proj.bias", lay["bproj2"]))
                 ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
                                      z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+                if null_terms is not None:          # one condition token: the softmax over a single key has no key term
+                    null_terms.append((None, dv2, None, lay["wv2"]))
                 for nm, ref in (("attn2.key.weight", lay["wk2"]), ("attn2.key.bias", lay["bk2"]),
                                 ("attn2.query.weight", lay["wq2"]), ("attn2.query.bias", lay["bq2"]),
                                 ("ln1_1.emb.weight", blk.ln1_1.emb.weight), ("ln1_1.linear.weight", blk.ln1_1.linear.weight),
@@ -352,12 +430,20 @@ class D3PMTrainer:
         dw_ = self._arena.zeros((Ws * D,))
         ops.colsum(dpos.view(Hs, Ws * D), dw_)
         g["content_emb.width_emb.weight"] = dw_.view(Ws, D)
+        gnull = None
+        if null_terms is not None:
+            # (77, 512) f32, one gsdd_cond_null_grad call per block onto rows [:Te] in the backward's block order (a fixed order: the
+            # same bits every run); rows >= Te keep the arena's zero fill
+            gnull = z(self.NULL_NAME, self._null32)
+            for dk2, dv2, wk2, wv2 in null_terms:
+                ops.cond_null_grad(dk2, dv2, self.last_drop, wk2, wv2, B, Te, gnull[:Te])
         if red is not None:
             bucket()
             a = self._arena
             lo = a.buf.data_ptr() if a.buf is not None else 0
             done = lambda t: lo and lo <= t.data_ptr() < lo + 4 * mark[0]         # inside a bucket that has been issued
-            rest = [n for n, _ in tr.named_parameters() if not done(g[n])]
+            names = [n for n, _ in tr.named_parameters()] + ([self.NULL_NAME] if gnull is not None else [])
+            rest = [n for n in names if not done(g[n])]
             if rest:                              # the first step (arena not sized yet): whatever lives outside goes in one bucket
                 flat = torch.cat([g[n].reshape(-1) for n in rest])
                 red.add(flat)
@@ -377,57 +463,76 @@ class D3PMTrainer:
         return (os.environ.get("GSDD_TRAIN_GRAPH", "1") != "0" and not getattr(self, "_graph_failed", False) and x0.is_cuda
                 and not self.reducer.active() and world_size() == 1 and x0.shape[1] % 32 == 0)
 
-    def _capture(self, x0, cond):
+    def _capture(self, x0, cond, null_cond=None, drop=None):
         """Everything of a step that runs on the device -- re-pack of the weight images and AdaLN tables, q_sample, forward, loss +
         gradient, backward, Adam -- recorded once into a hipGraph and replayed: ~1000 small dependent launches leave ~2 ms of gaps per
         step when they are enqueued one by one.  Nothing step-dependent is baked in: x_0, condition, t, p(t) live in static buffers,
         the Philox stream id and Adam's step count are device words the host sets before each replay; the timesteps are drawn
         by DiffusionTransformer.sample_time before each replay, exactly as the eager step draws them.  torch's graph-private
         allocator pool keeps every activation of the captured step at its address (torch.cuda.graph is the plumbing; every node of
-        the graph is a libgsdd kernel or a fill / copy)."""
+        the graph is a libgsdd kernel or a fill / copy).
+        Condition dropout: the f32 copy of the learned null embedding, the dropout kernel (its draw reads the stream id's device word),
+        the null gradient and the copy of the updated rows back into the fp64 parameter are nodes too; an explicit mask and a caller's
+        null condition live in static buffers like x_0."""
         dm, dev = self.dm, x0.device
         B = x0.shape[0]
         st = {"shape": (tuple(x0.shape), tuple(cond.shape)), "lr": self.lr,
               "x0": x0.clone().long().contiguous(), "cond": cond.clone().float().contiguous(),
               "t": torch.zeros((B,), dtype=torch.int64, device=dev), "pt": torch.full((B,), 1.0 / dm.num_timesteps, dtype=torch.float32, device=dev),
               "sid": torch.tensor([dm.noise_stream], dtype=torch.int64, device=dev),
-              "adam_step": torch.tensor([self._adam.step_count + 1], dtype=torch.int64, device=dev)}
+              "adam_step": torch.tensor([self._adam.step_count + 1], dtype=torch.int64, device=dev),
+              "drop": None if drop is None else drop.to(dev).to(torch.uint8).contiguous().clone(),
+              "null": None if null_cond is None else null_cond.to(dev).float().contiguous().clone()}
         tr = dm.transformer
         keep = (dm.noise_stream, self._adam.step_count)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             tr._packed = None                                    # the re-pack is part of the graph: every replay sees the current weights
-            loss, grads = self.loss_and_grads(st["x0"], st["cond"], st["t"], st["pt"], reduce=False, sid=st["sid"])
+            loss, grads = self.loss_and_grads(st["x0"], st["cond"], st["t"], st["pt"], reduce=False, sid=st["sid"], null_cond=st["null"],
+                                              drop=st["drop"])
             self._adam.lr = self.lr
             self._adam.step(grads, step_dev=st["adam_step"])
+            self._write_back_null(grads, cond.shape[1])
         dm.noise_stream, self._adam.step_count = keep             # capture executed nothing
         st["graph"], st["loss"], st["packed"] = graph, loss, tr._packed
         tr._packed = None
         return st
 
     @torch.no_grad()
-    def step(self, x0, cond, t=None, pt=None):
+    def step(self, x0, cond, t=None, pt=None, null_cond=None, drop=None):
+        """One optimiser step.  null_cond / drop: the null condition and the explicit drop mask of condition dropout (loss_and_grads).
+        With dm.learnable_cf the learned null embedding is updated with the transformer's parameters: its f32 copy and its gradient go
+        through the same Adam launch, and rows [:Te] of the updated copy are written back into the fp64 parameter."""
         self._sync_start()
         if self._graph_usable(x0, cond):
-            return self._step_graphed(x0, cond, t, pt)
-        return self._step_eager(x0, cond, t, pt)
+            return self._step_graphed(x0, cond, t, pt, null_cond, drop)
+        return self._step_eager(x0, cond, t, pt, null_cond, drop)
 
-    def _step_graphed(self, x0, cond, t, pt):
+    def _write_back_null(self, grads, Te):
+        """After Adam: rows [:Te] of the updated f32 copy go back into dm.empty_text_embed (f32 -> fp64, one copy node).  The rows
+        beyond Te have an exactly zero gradient and keep their fp64 values."""
+        if self.NULL_NAME in grads:
+            self.dm.empty_text_embed.data[:Te].copy_(self._null32[:Te])
+
+    def _step_graphed(self, x0, cond, t, pt, null_cond=None, drop=None):
         """Two eager steps first (arenas, images and tables reach their final addresses), then capture, then replays."""
         self._eager_steps = getattr(self, "_eager_steps", 0)
         # one captured graph per (batch shape, learning rate), the two most recent kept: an epoch's short last batch must not make
         # every epoch capture twice (each graph owns its activations' pool: ~7 GB at bs 16, L = 4096)
         graphs = self.__dict__.setdefault("_graphs", {})
-        key = (tuple(x0.shape), tuple(cond.shape), float(self.lr))
+        # ... and per condition-dropout setting: the probability is a launch constant of the dropout kernel, and the learned null
+        # embedding, a mask and a caller's null condition each change the graph's nodes
+        key = (tuple(x0.shape), tuple(cond.shape), float(self.lr), float(getattr(self.dm, "cond_drop_prob", 0.0) or 0.0),
+               bool(self.dm.learnable_cf), drop is not None, null_cond is not None, self.deterministic)
         st = self._graph = graphs.get(key)
         if st is None and self._eager_steps < 2:
             self._eager_steps += 1
-            return self._step_eager(x0, cond, t, pt)
+            return self._step_eager(x0, cond, t, pt, null_cond, drop)
         dm = self.dm
         if st is None:
             keep = (dm.noise_stream, self._adam.step_count)
             try:
-                st = self._graph = self._capture(x0, cond)
+                st = self._graph = self._capture(x0, cond, null_cond, drop)
                 while len(graphs) >= 2:
                     graphs.pop(next(iter(graphs)))
                 graphs[key] = st
@@ -438,7 +543,7 @@ class D3PMTrainer:
                 self._graph_failed = True
                 dm.transformer._packed = None
                 torch.cuda.synchronize()
-                return self._step_eager(x0, cond, t, pt)
+                return self._step_eager(x0, cond, t, pt, null_cond, drop)
         if t is None:
             # the reference's own timestep sampler (importance sampling once every Lt_count exceeds 10: its check reads device memory,
             # i.e. waits for the previous step -- one host round trip per step, ~0.1 ms beside a 54 ms replay)
@@ -447,6 +552,10 @@ class D3PMTrainer:
         st["cond"].copy_(cond, non_blocking=True)
         st["t"].copy_(t, non_blocking=True)
         st["pt"].copy_(pt, non_blocking=True)
+        if drop is not None:
+            st["drop"].copy_(drop, non_blocking=True)
+        if null_cond is not None:
+            st["null"].copy_(null_cond.reshape(st["null"].shape), non_blocking=True)
         # the two device words are set from the host's counts before every replay (two fills): whoever else draws from the noise stream
         # between steps -- the validation loop's _train_loss, set_noise, a resumed checkpoint -- moves dm.noise_stream, and the replay
         # must use the stream id the eager step would
@@ -460,17 +569,26 @@ class D3PMTrainer:
         self.last_fwd = None
         return st["loss"].clone()
 
-    def _step_eager(self, x0, cond, t=None, pt=None):
-        loss, grads = self.loss_and_grads(x0, cond, t, pt, reduce=True)
+    def _step_eager(self, x0, cond, t=None, pt=None, null_cond=None, drop=None):
+        loss, grads = self.loss_and_grads(x0, cond, t, pt, reduce=True, null_cond=null_cond, drop=drop)
         tr = self.dm.transformer
         params = dict(tr.named_parameters())
         self.step_count += 1
+        learned = self.NULL_NAME in grads
         if getattr(self, "_adam", None) is None:
-            self._adam = MultiAdam(list(params.items()), self.lr, self.betas, self.eps)
+            # the learned null embedding joins the parameter list (last) as its f32 copy: one Adam launch updates everything, and
+            # optimizer_state() / load_optimizer_state() carry its moments with the rest
+            plist = list(params.items()) + ([(self.NULL_NAME, self._null32)] if learned else [])
+            self._adam = MultiAdam(plist, self.lr, self.betas, self.eps)
             self._adam.load_state(getattr(self, "_pending_adam", None))
             self._pending_adam = None
+        if learned != (self._adam.params[-1][0] == self.NULL_NAME):
+            raise GsddError("this trainer's optimiser state was laid out " + ("without" if learned else "with") + " the learned null "
+                            "embedding: condition dropout with learnable_cf must be on for every step of a trainer or for none "
+                            "(make a new D3PMTrainer to change it)")
         self._adam.lr = self.lr
         self._adam.step(grads)                  # all parameters in one launch
+        self._write_back_null(grads, cond.shape[1])
         tr._packed = None                       # parameters changed in place through raw pointers
         return loss
 
@@ -497,24 +615,31 @@ class _TrainForward(torch.autograd.Function):
     incoming d(loss)."""
 
     @staticmethod
-    def forward(ctx, trainer, x0, cond, want_probs, *params):
-        loss, grads = trainer.loss_and_grads(x0, cond, want_probs=want_probs, reduce=True)    # DDP semantics: .grad = group mean
+    def forward(ctx, trainer, x0, cond, want_probs, null_cond, drop, *params):
+        loss, grads = trainer.loss_and_grads(x0, cond, want_probs=want_probs, reduce=True, null_cond=null_cond, drop=drop)    # DDP semantics: .grad = group mean
         names = [n for n, _ in trainer.dm.transformer.named_parameters()]
         ctx.grads = [grads[n].clone() for n in names]          # the arena is re-used by the next forward
+        if len(params) > len(names):                           # dm.empty_text_embed, the last input: its gradient widened to the parameter's fp64
+            ctx.grads.append(grads[trainer.NULL_NAME].double())
         return loss[0].clone()
 
     @staticmethod
     def backward(ctx, g_loss):
         out = tuple(g * g_loss for g in ctx.grads)
         ctx.grads = None
-        return (None, None, None, None) + out
+        return (None, None, None, None, None, None) + out
 
 
-def train_forward(dm, x0, cond, want_probs=False):
-    """DiffusionTransformer.forward in train mode with autograd enabled -> (loss with grad_fn, forward dict)."""
+def train_forward(dm, x0, cond, want_probs=False, null_cond=None, drop=None):
+    """DiffusionTransformer.forward in train mode with autograd enabled -> (loss with grad_fn, forward dict).  With condition dropout
+    and dm.learnable_cf, dm.empty_text_embed is an input of the autograd node too: backward leaves its (77, 512) fp64 gradient in .grad,
+    and the caller's optimiser over generator.parameters() updates it like any other parameter."""
     tr = getattr(dm, "_hip_trainer", None)
     if tr is None:
         tr = D3PMTrainer(dm)
         object.__setattr__(dm, "_hip_trainer", tr)
-    loss = _TrainForward.apply(tr, x0, cond, want_probs, *[p for _, p in dm.transformer.named_parameters()])
+    params = [p for _, p in dm.transformer.named_parameters()]
+    if dm.learnable_cf and tr._dropout_plan(cond, null_cond, drop) is not None:
+        params.append(dm.empty_text_embed)
+    loss = _TrainForward.apply(tr, x0, cond, want_probs, null_cond, drop, *params)
     return loss, tr.last_fwd

@@ -709,6 +709,50 @@ def adam(p, g, m, v, lr, beta1, beta2, eps, step, stream=None):
     check(lib().gsdd_adam(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, stream_ptr(stream)))
 
 
+def set_deterministic(on):
+    """Switches the training step's gradient reductions to their reproducible form (gsdd_set_deterministic; process-wide) -> the
+    previous setting.  D3PMTrainer(deterministic=True) brackets its calls with it."""
+    return bool(lib().gsdd_set_deterministic(1 if on else 0))
+
+
+# ----------------------------------------------------------------------------- classifier-free training: condition dropout
+def cond_dropout(cond, null_rows, p, *, seed, sid, row0=0, drop=None, out=None, drop_out=None, stream=None):
+    """-> (out, drop_out): out[b] = the null rows where sample b is dropped, else cond[b] (gsdd_cond_dropout).  cond (B, Te, C) f32,
+    null_rows (Te, C) f32; the decision is the Philox draw keyed by (seed, row0 + b, sid[0]) against p, or `drop` (B,) bool / uint8
+    when given; sid: int64[1] device tensor (the stream id of the step's q_sample draw)."""
+    if cond.dim() != 3 or cond.dtype != torch.float32 or null_rows.dtype != torch.float32:
+        raise GsddError(f"cond_dropout: cond must be a float32 (B, Te, C) tensor and null_rows float32, got {tuple(cond.shape)} {cond.dtype}")
+    B, Te, Cd = cond.shape
+    if null_rows.numel() != Te * Cd:
+        raise GsddError(f"cond_dropout: null_rows must hold (Te, C) = {(Te, Cd)} values, got {tuple(null_rows.shape)}")
+    if drop is not None:
+        if drop.dtype not in (torch.uint8, torch.bool) or tuple(drop.shape) != (B,):
+            raise GsddError(f"cond_dropout: drop must be a bool / uint8 {(B,)} tensor, got {tuple(drop.shape)} {drop.dtype}")
+    elif sid is None or sid.dtype != torch.int64:
+        raise GsddError("cond_dropout: the draw needs sid, an int64[1] device tensor")
+    out = torch.empty_like(cond) if out is None else out
+    drop_out = torch.empty((B,), dtype=torch.uint8, device=cond.device) if drop_out is None else drop_out
+    if out.dtype != torch.float32 or out.shape != cond.shape or drop_out.dtype != torch.uint8 or drop_out.numel() != B:
+        raise GsddError("cond_dropout: out must be float32 of cond's shape and drop_out uint8 (B,)")
+    check(lib().gsdd_cond_dropout(ptr(cond), ptr(null_rows), B, Te, Cd, float(p), int(seed), ptr(sid), int(row0), ptr(drop), ptr(out),
+                                  ptr(drop_out), stream_ptr(stream)))
+    return out, drop_out
+
+
+def cond_null_grad(dk, dv, drop, wk, wv, B, Te, dnull, stream=None):
+    """dnull (Te, C) += sum over the dropped samples of dk[b] Wk + dv[b] Wv (gsdd_cond_null_grad); dk / dv hold (B, Te, D) values,
+    wk / wv are (D, C); dk and wk are both None on the one-token path.  drop: uint8 (B,), what cond_dropout wrote."""
+    D, Cd = wv.shape
+    if dv.numel() != B * Te * D or (dk is not None and dk.numel() != B * Te * D) or dnull.numel() != Te * Cd:
+        raise GsddError(f"cond_null_grad: dk / dv must hold (B, Te, D) = {(B, Te, D)} values and dnull (Te, C) = {(Te, Cd)}")
+    if drop.dtype not in (torch.uint8, torch.bool) or drop.numel() != B or (wk is not None and wk.shape != wv.shape):
+        raise GsddError("cond_null_grad: drop must be bool / uint8 (B,) and wk of wv's shape")
+    if any(x is not None and x.dtype != torch.float32 for x in (dk, dv, wk, wv, dnull)):
+        raise GsddError("cond_null_grad: float32 tensors only")
+    check(lib().gsdd_cond_null_grad(ptr(dk), ptr(dv), ptr(drop), ptr(wk), ptr(wv), B, Te, D, Cd, ptr(dnull), stream_ptr(stream)))
+    return dnull
+
+
 # ----------------------------------------------------------------------------- VQ-VAE training-step building blocks
 def conv_wgrad(x, dY, dW, *, in_dims, out_grid, stride=(1, 1, 1), taps=None, ntaps=1, cin, cout, in_pitch=None, pro=None,
                out_dims=None, out_step=(1, 1, 1), out_off=(0, 0, 0), exact_f32=None, stream=None):

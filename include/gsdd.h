@@ -498,6 +498,13 @@ int gsdd_ln_fwd(const float* x, int64_t M, int C, float eps, const float* gamma,
 int gsdd_ln_bwd(const float* dh, const float* x, const float* stats, const float* gamma, const int64_t* sel, int gstride,
                 int rows_per_batch, int64_t M, int C, const float* dx_in, float* dx_out, float* dgamma, float* dbeta,
                 int gacc_stride, int acc_by_batch, void* stream);
+/* Process-wide switch of the reductions below (gsdd_ln_bwd's dgamma / dbeta, gsdd_wgrad, gsdd_colsum, gsdd_batch_rowsum,
+ * gsdd_d3pm_embed_bwd, gsdd_adaln_bwd's demb): by default workgroups add their partial sums with float atomics, fast, and the last
+ * bits of a gradient depend on the order the hardware retires them in.  on != 0: every output address receives the sum of ONE
+ * workgroup (or thread) formed in a fixed order -- the same inputs give the same bits -- at the cost of the parallelism over the rows
+ * (gsdd_d3pm_embed_bwd walks all rows per table row: for tests and reproducibility runs, not the production shape).  Returns the
+ * previous setting.  Read by the host code at launch time: a captured graph keeps the form it was captured with. */
+int gsdd_set_deterministic(int on);
 /* dW[N][K] += dY^T X (contraction over the M rows), db[N] += column sums of dY (optional) */
 int gsdd_wgrad(const float* dY, int ldy, const float* X, int ldx, int64_t M, int N, int K, float* dW, float* db, void* stream);
 /* out[n] += sum_m Y[m][n] */
@@ -548,6 +555,22 @@ int gsdd_adam_multi(const int64_t* table, int n_blocks, float lr, float beta1, f
  * caller sets *step_dev before each replay, or advances it with gsdd_advance inside the graph). */
 int gsdd_adam_multi_dev(const int64_t* table, int n_blocks, float lr, float beta1, float beta2, float eps, const int64_t* step_dev,
                         void* stream);
+
+/* ------------------------------------------------------------------ classifier-free training: condition dropout, learned null embedding
+ * (the reference substitutes empty_text_embed for the condition at diffusion_transformer.py:541-543) */
+/* out[b] = drop_b ? null_rows : cond[b] over (Te, C) rows, drop_out[b] = drop_b.  drop_b = drop_in[b] != 0 when drop_in is given,
+ * else u_b < p with u_b = (w >> 8) * 2^-24, w = word 0 of Philox4x32-10 with key `seed` and counter (row0 + b [64 bit], sid[0], 1):
+ * every other draw of the library has 0 in counter word 3.  cond / out: [B][Te][C]; null_rows: [Te][C]; sid: device int64[1], the
+ * stream id of the step's q_sample draw (may be NULL with drop_in); drop_in / drop_out: B bytes.  C % 4 == 0, 1 <= Te <= 77,
+ * 0 <= p <= 1, rows 16-byte aligned; out must not overlap cond or null_rows. */
+int gsdd_cond_dropout(const float* cond, const float* null_rows, int B, int Te, int C, float p, uint64_t seed, const int64_t* sid,
+                      int64_t row0, const uint8_t* drop_in, float* out, uint8_t* drop_out, void* stream);
+/* dnull[j][:] += sum_{b: drop[b]} (dk[b][j][:] Wk + dv[b][j][:] Wv) for j < Te: the gradient of the null rows through one block's
+ * attn2.key / attn2.value.  dk / dv: [B][Te][D]; wk / wv: [D][C]; dnull: [Te][C]; dk and wk may both be NULL (one condition token: no
+ * key term).  Samples in ascending b, features in ascending d, no atomics: bitwise reproducible.  With no sample dropped dnull is not
+ * written.  1 <= Te <= 77, 1 <= D <= 4096. */
+int gsdd_cond_null_grad(const float* dk, const float* dv, const uint8_t* drop, const float* wk, const float* wv, int B, int Te, int D,
+                        int C, float* dnull, void* stream);
 
 /* t[b] += dt ; stream[0] += ds   (device-side loop counters for the captured step graph) */
 int gsdd_advance(int64_t* t_dev, int B, int64_t dt, int64_t* stream_dev, int64_t ds, void* stream);

@@ -90,7 +90,8 @@ class MultistageTextMotionModel(BaseModel):
         # as the glue does on the reference-shaped path: per-rank noise rows, rank 0's importance-sampling statistics everywhere
         set_rank_noise_rows(self.generator.diffusion_model, x.shape[0])
         broadcast_buffers(self.generator.diffusion_model)
-        loss = self._native.step(tokens, text_emb)[0]
+        # (condition dropout: the null condition the reference-shaped path hands the denoiser -- None unless train_cond_drop_prob is on)
+        loss = self._native.step(tokens, text_emb, null_cond=self.generator.null_condition(tokens.device))[0]
         self.generator_losses["train"].update({"losses": loss})
         self.loss_dict["generator_loss"] = loss
         return self.loss_dict

@@ -6,6 +6,7 @@
 //   (3) null pointers, bad sizes, unknown variant / mode values: GSDD_E_ARG, nothing launched;
 //   (4) a failing hipFuncSetAttribute: reported as GSDD_E_HIP by that call and retried (successfully) by the next one.
 // Exit code 0 = all expectations met and no sanitizer report.  Test infrastructure only.
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -243,6 +244,68 @@ int main() {
             j.B = B;
             EXPECT(gsdd_d3pm_forward_jump(nullptr, st), GSDD_E_ARG, false);
             EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
+        }
+        {   // the training step's gradient reductions, in the fast form and in the reproducible one (gsdd_set_deterministic)
+            float *dh = devp(1 << 25), *xr = devp(1 << 25), *stats = devp(), *gam = devp(), *dxo = devp(1 << 25), *dg = devp(), *dbt = devp();
+            float *dW = devp(), *dbias = devp(), *osum = devp(), *dtab = devp(), *emb = devp(), *wad = devp(), *demb = devp(), *dpos = devp(1 << 21);
+            int64_t *sel = devp<int64_t>(), *tokp = devp<int64_t>();
+            EXPECT(gsdd_set_deterministic(0), 0, false);
+            for (int det = 0; det < 2; ++det) {
+                EXPECT(gsdd_set_deterministic(det), det ? 0 : 0, false);
+                EXPECT(gsdd_ln_bwd(dh, xr, stats, gam, sel, 128, L, M, 64, nullptr, dxo, dg, dbt, 128, 1, st), GSDD_OK, true);       // AdaLN: per-batch slots
+                EXPECT(gsdd_ln_bwd(dh, xr, stats, gam, sel, 128, 40, 160, 64, dh, dxo, dg, dbt, 128, 1, st), GSDD_OK, true);        // L % 16 != 0
+                EXPECT(gsdd_ln_bwd(dh, xr, stats, gam, nullptr, 0, L, M, 64, nullptr, dxo, dg, dbt, 64, 0, st), GSDD_OK, true);     // affine LN
+                EXPECT(gsdd_ln_bwd(dh, xr, stats, gam, nullptr, 0, L, M, 64, nullptr, dxo, nullptr, nullptr, 64, 0, st), GSDD_OK, true);
+                EXPECT(gsdd_wgrad(dh, 64, xr, 64, M, 64, 64, dW, dbias, st), GSDD_OK, true);
+                EXPECT(gsdd_wgrad(dh, 256, xr, 64, 160, 256, 64, dW, nullptr, st), GSDD_OK, true);
+                EXPECT(gsdd_colsum(dh, 64, M, 64, osum, st), GSDD_OK, true);
+                EXPECT(gsdd_batch_rowsum(dh, B, L, 64, osum, st), GSDD_OK, true);
+                EXPECT(gsdd_d3pm_embed_bwd(dh, tokp, B, L, 64, K + 1, demb, dpos, st), GSDD_OK, true);
+                EXPECT(gsdd_adaln_bwd(dtab, sel, B, 64, emb, wad, demb, dW, dbias, st), GSDD_OK, true);
+                EXPECT(gsdd_wgrad(dh, 64, xr, 64, 0, 64, 64, dW, dbias, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_ln_bwd(dh, xr, stats, gam, sel, 128, L, M, 64, nullptr, dxo, dg, nullptr, 128, 1, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_d3pm_embed_bwd(dh, nullptr, B, L, 64, K + 1, demb, dpos, st), GSDD_E_ARG, false);
+            }
+            EXPECT(gsdd_set_deterministic(0), 1, false);             // returns the previous setting
+            EXPECT(gsdd_set_deterministic(0), 0, false);
+        }
+        {   // classifier-free training: condition dropout (drawn and with a mask) and the null embedding's gradient; bad arguments
+            const int Te = 22, C = 512, D = 64;
+            float *cond = devp(), *null_rows = devp(), *out = devp();
+            int64_t* sid = devp<int64_t>();
+            uint8_t *din = devp<uint8_t>(), *dout = devp<uint8_t>();
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 1000, nullptr, out, dout, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.f, 21, nullptr, 0, din, out, dout, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, 5, 77, C, 1.f, 21, sid, (int64_t)1 << 33, nullptr, out, dout, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, 1, 1, 4, 0.5f, 21, sid, 0, nullptr, out, dout, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_dropout(nullptr, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, nullptr, B, Te, C, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, nullptr, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, out, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, nullptr, 0, nullptr, out, dout, st), GSDD_E_ARG, false);   // a draw without sid
+            for (int bad : {0, -1, 78}) EXPECT(gsdd_cond_dropout(cond, null_rows, B, bad, C, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            for (int bad : {0, -4, 6, 510}) EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, bad, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            for (float bad : {-0.1f, 1.5f, NAN}) EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, bad, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, 0, Te, C, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, -1, nullptr, out, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, cond, dout, st), GSDD_E_ARG, false);      // out == cond
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, cond + Te * C, dout, st), GSDD_E_ARG, false);   // overlap
+            EXPECT(gsdd_cond_dropout(cond, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, null_rows, dout, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_dropout(cond + 1, null_rows, B, Te, C, 0.1f, 21, sid, 0, nullptr, out, dout, st), GSDD_E_ARG, false);   // not 16-byte aligned
+            float *dk = devp(), *dv = devp(), *wk = devp(), *wv = devp(), *dnull = devp();
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, B, Te, D, C, dnull, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_null_grad(nullptr, dv, dout, nullptr, wv, B, 1, D, C, dnull, st), GSDD_OK, true);                        // one token: no key term
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, 3, 77, 4096, 20, dnull, st), GSDD_OK, true);
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, nullptr, wv, B, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(nullptr, dv, dout, wk, wv, B, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, nullptr, dout, wk, wv, B, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, dv, nullptr, wk, wv, B, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, nullptr, B, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, B, Te, D, C, nullptr, st), GSDD_E_ARG, false);
+            for (int bad : {0, -1, 78}) EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, B, bad, D, C, dnull, st), GSDD_E_ARG, false);
+            for (int bad : {0, -1, 4097}) EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, B, Te, bad, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, 0, Te, D, C, dnull, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_cond_null_grad(dk, dv, dout, wk, wv, B, Te, D, 0, dnull, st), GSDD_E_ARG, false);
         }
         {   // purity-prior step: scores + candidates, selection, plan counter
             gsdd_purity_desc p;
