@@ -3,8 +3,10 @@ state_dict keys, computing on gfx950 through the C ABI.
 
 Reference: src/models/motionencoder/{dalle_mask_image_embedding,transformer_utils,diffusion_transformer}.py and
 src/models/networks/discrete_diffusion.py.  The nn.Module tree only owns parameters under the
-reference's names; the sampling loop runs as one captured hipGraph per reverse
-step, replayed diffusion_step times with the timestep and the Philox stream id living in device memory.
+reference's names.  A sampling chain is a program: the tuple of op kinds a plan lists in order of
+execution ("step", "jump", "reveal", "final").  Every op of a kind is the same launch sequence driven by device counters (the
+timestep, the Philox stream id), so `issue_schedule` has each lane run a kind eagerly once, capture it into a hipGraph if it
+recurs, and replay it from then on; `DiffusionTransformer._sample_once` walks that schedule.
 """
 import collections
 import collections.abc
@@ -12,7 +14,6 @@ import contextlib
 import ctypes
 import numbers
 import os
-import types
 
 import numpy as np
 import torch
@@ -20,6 +21,10 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import GsddError
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
 
 @contextlib.contextmanager
@@ -392,7 +397,6 @@ class Text2ImageTransformer(nn.Module):
 # ----------------------------------------------------------------------------- diffusion
 def alpha_schedule(time_step, N=100, att_1=0.99999, att_T=0.000009, ctt_1=0.000009, ctt_T=0.99999):
     """Linear schedule in fp64 numpy (host, init only).  Reference: diffusion_transformer.py:56-69."""
-    import numpy as np
     att = np.arange(0, time_step) / (time_step - 1) * (att_T - att_1) + att_1
     att = np.concatenate(([1], att))
     at = att[1:] / att[:-1]
@@ -416,6 +420,10 @@ class SamplePlan(collections.namedtuple("SamplePlan", "t0 n_steps dt post_skip q
     def draws(self):
         """Noise streams a run spends: one per step, one more for the q_sample start."""
         return self.n_steps + (1 if self.q_sample else 0)
+
+    @property
+    def program(self):
+        return ("step",) * self.n_steps
 
 
 def sample_plan(T, skip_step=0, start_step=0):
@@ -441,7 +449,7 @@ def plan_timesteps(plan):
 class ResamplePlan(collections.namedtuple("ResamplePlan", "T jump times ops")):
     """A known-token chain with RePaint's resampling jumps: `ops` is the order of execution, ("step", t) -- the ordinary reverse step
     with the denoiser at t, which leaves the state at level t - 1 -- and ("jump", a) -- the whole state diffused forward from level a to
-    a + jump.  t0, n_steps, q_sample and draws read like SamplePlan's; every step is the plain one (dt 1, post_skip 0)."""
+    a + jump.  t0, n_steps, q_sample, draws and program read like SamplePlan's; every step is the plain one (dt 1, post_skip 0)."""
     __slots__ = ()
     q_sample, dt, post_skip = False, 1, 0
 
@@ -461,6 +469,10 @@ class ResamplePlan(collections.namedtuple("ResamplePlan", "T jump times ops")):
     def draws(self):
         """Noise streams a run spends: one per step and one per jump, in order of execution."""
         return len(self.ops)
+
+    @property
+    def program(self):
+        return tuple(kind for kind, _ in self.ops)
 
 
 def resample_plan(T, jump, times):
@@ -487,7 +499,6 @@ def jump_table(T, K, jump):
     cumulative arrays of alpha_schedule (index T: 1 / 0): alpha~ = abar_b / abar_a, gamma~ = (gbar_b - gbar_a) / (1 - gbar_a),
     beta~ = (1 - alpha~ - gamma~) / K, all in fp64 (beta~ is a difference of numbers of size 1e-5 at the top of the schedule).  Rows
     whose target a + jump lies above T - 1 are NaN: the chain never asks for them.  What gsdd_d3pm_forward_jump reads."""
-    import numpy as np
     _, _, _, att, _, ctt = alpha_schedule(T, N=K)
     out = np.full((T + 1, 3), np.nan, dtype=np.float64)
     for row in range(T + 1):
@@ -504,14 +515,13 @@ def jump_table(T, K, jump):
 
 def check_resample(jump, times, T, known_mask):
     """Validates sample()'s resample_jump / resample_times.  -> None (the plain chain) or (jump, times) with times >= 2."""
-    is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
-    if not is_int(times) or times < 1:
+    if not _is_int(times) or times < 1:
         raise GsddError(f"resample_times must be an int >= 1, got {times!r}")
     if jump is None:
         if times != 1:
             raise GsddError(f"resample_times = {times} needs resample_jump (how many levels every resampling jumps back up)")
         return None
-    if not is_int(jump) or not 1 <= jump <= T - 1:
+    if not _is_int(jump) or not 1 <= jump <= T - 1:
         raise GsddError(f"resample_jump must be None or an int in [1, {T - 1}] (num_timesteps - 1), got {jump!r}")
     if known_mask is None:
         raise GsddError("resample_jump needs known_mask: resampling harmonises sampled positions with given ones")
@@ -521,7 +531,7 @@ def check_resample(jump, times, T, known_mask):
 class PurityPlan(collections.namedtuple("PurityPlan", "calls final rule weight")):
     """A purity-prior chain (sample() with prior_rule 1 / 2): the (t, n) of every p_sample call at t > 0 -- denoiser at t, reveal n
     [MASK] positions per sample -- whether a plain reverse step at t = 0 closes it, the rule and the prior weight r.
-    n_steps, t0, q_sample and draws read like SamplePlan's: what the sampling loop asks of either plan."""
+    n_steps, t0, q_sample, draws and program read like SamplePlan's: what the sampling loop asks of either plan."""
     __slots__ = ()
     q_sample = False                                # from all-[MASK] only
 
@@ -537,6 +547,29 @@ class PurityPlan(collections.namedtuple("PurityPlan", "calls final rule weight")
     def draws(self):
         """Two noise streams per call (candidates, selection), one more for the closing plain step."""
         return 2 * len(self.calls) + (1 if self.final else 0)
+
+    @property
+    def program(self):
+        return ("reveal",) * len(self.calls) + (("final",) if self.final else ())
+
+
+def issue_schedule(program, lanes, graphed):
+    """-> [(lane, kind, action)] in host issue order for a plan's `program` (its op kinds in order of execution), pure.  Op-major,
+    lane-minor, so that the lanes' queues are fed alternately.  Not graphed: every op is "eager".  Graphed: a lane runs the first op
+    of a kind "eager" (arguments are validated outside capture) and, if the kind occurs again, records it right after ("capture":
+    recorded, not executed); every later op of the kind is a "replay" of that graph."""
+    left, seen, out = collections.Counter(program), set(), []
+    for kind in program:
+        left[kind] -= 1
+        for ln in range(lanes):
+            if graphed and kind in seen:
+                out.append((ln, kind, "replay"))
+                continue
+            out.append((ln, kind, "eager"))
+            if graphed and left[kind]:
+                out.append((ln, kind, "capture"))
+        seen.add(kind)
+    return out
 
 
 def reference_n_sample(T, prior_ps=1024):
@@ -643,11 +676,10 @@ def frame_mask(latent_shape, frames):
     quant.view(B, -1) flattens the encoder's codes; frames is an int k (the first k frames: clip continuation) or an iterable of frame
     indices (first + last frame: interpolation).  Negative indices count from the end."""
     shape = tuple(latent_shape)
-    is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
-    if len(shape) != 3 or not all(is_int(v) and v >= 1 for v in shape):
+    if len(shape) != 3 or not all(_is_int(v) and v >= 1 for v in shape):
         raise GsddError(f"frame_mask: latent_shape must be three positive ints (t, h, w), got {latent_shape!r}")
     nt = int(shape[0])
-    if is_int(frames):
+    if _is_int(frames):
         if not 0 <= frames <= nt:
             raise GsddError(f"frame_mask: the first {frames} frames of a latent with {nt}")
         idx = list(range(int(frames)))
@@ -656,7 +688,7 @@ def frame_mask(latent_shape, frames):
             idx = list(frames)
         except TypeError:
             raise GsddError(f"frame_mask: frames must be an int or an iterable of frame indices, got {frames!r}") from None
-        if not all(is_int(i) and -nt <= i < nt for i in idx):
+        if not all(_is_int(i) and -nt <= i < nt for i in idx):
             raise GsddError(f"frame_mask: frame indices {idx!r} outside a latent with {nt} frames")
     m = torch.zeros(shape, dtype=torch.bool)
     m[[int(i) for i in idx]] = True
@@ -710,6 +742,98 @@ SCHED_ORDER = ("log_at", "log_bt", "log_ct", "log_1_min_ct", "log_cumprod_at", "
                "log_1_min_cumprod_ct")
 
 
+class _Lane:
+    """One sub-batch of a sampling call (clips `sl` of the batch) and the ops of its chain.  Independent sub-batches run their reverse
+    chains concurrently on separate HIP streams: every clip's chain depends only on its own tokens, condition and noise rows (the noise
+    key is the global row index), so the tokens are those of the single-lane run, and workgroups of one lane fill the tail of the
+    other lane's kernels.  Holds the stream st, tokens tok, condition vectors condv (Te condition tokens, `rep` stacked guidance
+    copies), timesteps t2, workspace ws, noise-stream counter sid, M = Bs L positions from global row row0, the known-position
+    keywords, the graph of every op kind captured so far and what only some programs need: the jump's table and held positions, the
+    reveal's plan arrays, counters and candidate buffers.  Built on `st`, after st waits for the caller's stream."""
+
+    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw):
+        dev, L, K, Bs, tr = dm.device, dm.shape, dm.num_classes - 1, sl.stop - sl.start, dm.transformer
+        self.tr, self.plan, self.st, self.rep, self.guided, self.graphs = tr, plan, st, rep, dm._guided, {}
+        self.trunc_kw = trunc_kw                    # a launch constant of both step kernels: a captured graph records it
+        self.sched, self.K, self.T = dm._sched(), K, dm.num_timesteps
+        self.guidance, self.seed = float(dm.guidance_scale), dm.noise_seed
+        self.Te, self.M, self.row0 = conds.shape[1], Bs * L, (dm.row_offset + sl.start) * L
+        self.condv = tr.cond_vectors(conds.contiguous())
+        self.ws = tr.workspace(rep * Bs, L, dev, rep=rep)
+        i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+        self.t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
+        self.sid = i64([dm.noise_stream + (1 if plan.q_sample else 0)])      # the partially noised start spends one draw on q_sample
+        if x0 is None:
+            self.tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)          # all [MASK] (:613-618)
+        else:                                                                        # q_sample at t = start_step - 1 (:628-630)
+            self.tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
+            ops.d3pm_q_sample(x0[sl].contiguous(), self.tok, self.sched, self.t2[:Bs].contiguous(), i64([dm.noise_stream]), K=K,
+                              T=self.T, seed=self.seed, row0=self.row0, stream=st)
+        # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they are
+        # constants of the chain; nothing at all without a mask
+        self.known_kw = _known_kwargs(known, dev, sl)
+        if "jump" in plan.program:              # the jump's table and, in hold mode, the positions it copies through
+            self.jump_table = dm._jump_table(plan.jump, dev)
+            self.jump_hold = self.known_kw["known"] if self.known_kw["known_mode"] == KNOWN_MODES["hold"] else None
+        if "reveal" in plan.program:
+            # (t, n) of every call plus a (0, 0) sentinel: after the last reveal the counter leaves t = 0 for the final step
+            self.plan_t, self.plan_n = i64([t for t, _ in plan.calls] + [0]), i64([n for _, n in plan.calls] + [0])
+            self.step_dev, self.n_dev = i64([0]), i64([plan.calls[0][1]])
+            self.score = torch.empty((Bs, L), dtype=torch.float32, device=dev)
+            self.smax = torch.empty((Bs,), dtype=torch.float32, device=dev)
+            self.cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
+
+    def denoise(self):                          # -> the conditional and the unconditional logits of the lane's tokens at t2
+        logits = self.tr.run(self.tok, self.condv, self.Te, self.t2, self.ws, rep=self.rep, stream=self.st)
+        return logits[:self.M], (logits[self.M:] if self.rep == 2 else logits[:self.M]) if self.guided else None
+
+    def plain_step(self, post_skip):
+        ops.d3pm_step(*self.denoise(), self.tok, self.tok, self.sched, self.t2, self.sid, K=self.K, T=self.T, guidance=self.guidance,
+                      seed=self.seed, row0=self.row0, post_skip=post_skip, stream=self.st, **self.trunc_kw, **self.known_kw)
+
+    def step(self):                             # the reverse step at t2, then t2 and sid move on
+        self.plain_step(self.plan.post_skip)
+        if self.plan.dt == 1:
+            ops.advance(self.t2, -1, self.sid, 1, stream=self.st)
+        else:                                   # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
+            ops.advance_floor(self.t2, -self.plan.dt, 0, self.sid, 1, stream=self.st)
+
+    def jump(self):                             # the state at level t2 moves forward to t2 + jump; one noise stream, like a step
+        ops.d3pm_forward_jump(self.tok, self.tok, self.jump_table, self.t2, self.sid, K=self.K, T=self.T, jump=self.plan.jump,
+                              seed=self.seed, row0=self.row0, hold=self.jump_hold, stream=self.st)
+        ops.advance(self.t2, self.plan.jump, self.sid, 1, stream=self.st)
+
+    def reveal(self):                           # a purity call: candidates, the n_dev most trusted [MASK] positions, the next (t, n)
+        plan = self.plan
+        ops.d3pm_purity_step(*self.denoise(), self.score, self.smax, self.cand, self.sid, K=self.K, guidance=self.guidance,
+                             prior_rule=plan.rule, prior_weight=plan.weight, seed=self.seed, row0=self.row0, stream=self.st,
+                             **self.trunc_kw)
+        ops.d3pm_purity_select(self.tok, self.tok, self.cand, self.score, self.smax, self.n_dev, self.sid, K=self.K,
+                               prior_rule=plan.rule, seed=self.seed, stream_add=1, row0=self.row0, stream=self.st)
+        ops.advance_plan(self.step_dev, self.plan_t, self.plan_n, self.t2, self.n_dev, self.sid, 2, stream=self.st)
+
+    def final(self):                            # the purity chain's ordinary reverse step at t = 0
+        self.plain_step(0)
+
+    OPS = {"step": step, "jump": jump, "reveal": reveal, "final": final}
+
+    def issue(self, kind, action, trace=None):
+        """One entry of `issue_schedule`; an eager op of a traced call appends the lane's tokens to `trace`."""
+        if action == "replay":
+            self.graphs[kind].launch(self.st)
+            return
+        with torch.cuda.stream(self.st):
+            if action == "capture":
+                g = self.graphs[kind] = ops.Graph()
+                g.begin(self.st)
+                self.OPS[kind](self)            # recorded, not executed
+                g.end(self.st)
+            else:
+                self.OPS[kind](self)
+                if trace is not None:
+                    trace.append(self.tok.clone())
+
+
 class DiffusionTransformer(nn.Module):
     """Drop-in for diffusion_transformer.py:71-645 (sample, forward/_train_loss surface)."""
 
@@ -759,11 +883,15 @@ class DiffusionTransformer(nn.Module):
         self.row_offset = 0          # global row of this rank's first sample (multi-GPU batch sharding)
         self.sample_lanes = None     # concurrent sub-batches of sample() (see there): None = two when the batch allows it;
                                      # `bench.py --lanes N` / GSDD_SAMPLE_LANES override it
-        self._graph_cache = {}
 
     @property
     def device(self):
         return self.transformer.to_logits[-1].weight.device
+
+    @property
+    def _guided(self):
+        """Whether a reverse step mixes conditional and unconditional logits (guidance_scale != 1)."""
+        return abs(self.guidance_scale - 1) >= 1e-3
 
     def set_noise(self, seed, stream=0, row_offset=0):
         self.noise_seed, self.noise_stream, self.row_offset = int(seed), int(stream), int(row_offset)
@@ -797,8 +925,7 @@ class DiffusionTransformer(nn.Module):
     def _cf_embed(self, condition_embed, cf_condition_embed):
         """The unconditional condition of a guided sampling call: the caller's, else (learnable_cf) the learned null rows repeated over
         the batch."""
-        guided = abs(self.guidance_scale - 1) >= 1e-3
-        if cf_condition_embed is not None or not guided:
+        if cf_condition_embed is not None or not self._guided:
             return cf_condition_embed
         if not self.learnable_cf:
             raise GsddError("guided sampling (guidance_scale != 1) needs cf_condition_embed")
@@ -823,11 +950,10 @@ class DiffusionTransformer(nn.Module):
     def _purity_plan(self, start_step):
         """Validates the prior attributes and returns the PurityPlan sample() runs (prior_rule 1 / 2)."""
         T, L = self.num_timesteps, self.shape
-        is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
         if start_step != 0:
             raise GsddError("prior_rule > 0 samples from all-[MASK] only: filter_ratio must give start_step 0 (the reference's "
                             "filter_ratio > 0 loop raises with any prior_rule, diffusion_transformer.py:636)")
-        if not is_int(self.prior_ps) or self.prior_ps < 1:
+        if not _is_int(self.prior_ps) or self.prior_ps < 1:
             raise GsddError(f"prior_ps must be an int >= 1, got {self.prior_ps!r}")
         if isinstance(self.prior_weight, bool) or not isinstance(self.prior_weight, numbers.Real) or not self.prior_weight >= 0:
             raise GsddError(f"prior_weight must be a number >= 0, got {self.prior_weight!r}")
@@ -835,7 +961,7 @@ class DiffusionTransformer(nn.Module):
         if ns is None or len(ns) != T:
             raise GsddError(f"n_sample must list one reveal count per timestep: len(n_sample) = {None if ns is None else len(ns)}, "
                             f"num_timesteps = {T}")
-        if not all(is_int(v) for v in ns):
+        if not all(_is_int(v) for v in ns):
             raise GsddError("n_sample entries must be ints")
         if min(ns) < 0:
             raise GsddError(f"negative entry in n_sample: {min(ns)}")
@@ -860,8 +986,11 @@ class DiffusionTransformer(nn.Module):
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", resample_jump=None,
                resample_times=1, **kwargs):
-        """diffusion_transformer.py:568-644.  The loop itself is `_sample_once`, driven by `sample_plan`; `_sample_checked` repeats it
-        on the bf16x3 layer kernel if an activation left the f16 operand range.
+        """diffusion_transformer.py:568-644.  The arguments pick a plan (`sample_plan`, `resample_plan`, `_purity_plan`); `_sample_once`
+        executes the plan's program -- its op kinds in order -- as `issue_schedule` lays it out over the lanes (a lane runs a kind
+        eagerly once, captures it into a hipGraph if it recurs and replays it from then on; use_graph=False or a `trace` list: every
+        op eagerly in one lane, one trace entry per op); `_sample_checked` repeats the call on the bf16x3 layer kernel if an
+        activation left the f16 operand range.
         filter_ratio > 0: start from content_token noised to t = start_step - 1 and run start_step reverse steps
         (diffusion_transformer.py:590-592, :626-634; the reference's own loop there passes p_sample four of its six positional
         parameters and raises TypeError -- this is the behaviour that branch is written for, one p_sample per step).
@@ -921,7 +1050,7 @@ class DiffusionTransformer(nn.Module):
         if int(T * filter_ratio) != 0:
             raise GsddError(f"sample_fast starts from all-[MASK] only: int(num_timesteps * filter_ratio) = {int(T * filter_ratio)}, "
                             "must be 0 (diffusion_transformer.py:686)")
-        if isinstance(skip_step, bool) or not isinstance(skip_step, numbers.Integral) or skip_step < 0:
+        if not _is_int(skip_step) or skip_step < 0:
             raise GsddError(f"skip_step must be a non-negative int, got {skip_step!r}")
         cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
         if return_logits:
@@ -946,188 +1075,68 @@ class DiffusionTransformer(nn.Module):
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
                      use_graph=True, trace=None, truncation_rate=None, known=None, **kwargs):
+        """Runs plan.program once: resolves the guidance copies and the lane count, builds the lanes, issues `issue_schedule`'s
+        entries and joins the lanes' streams."""
         dev = self.device
-        trunc_kw = _trunc_kwargs(truncation_rate)   # a launch constant of both step kernels: the captured graph records it
         if dev.type != "cuda":
             raise GsddError("sampling runs on the HIP path only: move the module to a ROCm device")
-        B = len(condition_token) if condition_token is not None else kwargs["batch_size"]
-        L, K, T = self.shape, self.num_classes - 1, self.num_timesteps
-        guided = abs(self.guidance_scale - 1) >= 1e-3
+        B, L, K = self._batch_of(condition_token, kwargs), self.shape, self.num_classes - 1
         cond = condition_embed.to(dev).float()
-        cf = cf_condition_embed.to(dev).float().type_as(cond) if guided else None
+        cf = cf_condition_embed.to(dev).float().type_as(cond) if self._guided else None
         # Identical conditional and unconditional embeddings -- the reference's shipped inference path: DiscreteDiffusion.forward zeroes
         # both (discrete_diffusion.py:25, :49) -- make the two guidance copies the same computation on the same inputs, bit for bit.
         # Then one copy runs and the step kernel reads its logits on both sides of log p_u + s (log p_c - log p_u): the same values
         # through the same arithmetic as the stacked pass, at half the denoiser work.  (One host comparison per sample() call;
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
-        same_cond = (guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape and bool(torch.equal(cond, cf)))
-        resample = isinstance(plan, ResamplePlan)   # RePaint's jumps: the host issues plan.ops in order, steps and forward jumps
-        purity = isinstance(plan, PurityPlan)       # prior_rule 1 / 2: the calls at t > 0 come from device plan arrays; the rest is shared
-        n_steps = plan.n_steps
-        stream0 = self.noise_stream + (1 if plan.q_sample else 0)      # the partially noised start spends one draw on q_sample
+        same_cond = (self._guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape
+                     and bool(torch.equal(cond, cf)))
+        rep = 2 if (self._guided and not same_cond) else 1
+        x0 = None
         if plan.q_sample:
-            x0_start = content_token.to(dev).long().reshape(B, L).contiguous()
-            if int(x0_start.min()) < 0 or int(x0_start.max()) > K:
+            x0 = content_token.to(dev).long().reshape(B, L).contiguous()
+            if int(x0.min()) < 0 or int(x0.max()) > K:
                 raise GsddError("content_token outside [0, num_embed]")
-        rep = 2 if (guided and not same_cond) else 1
-        self._last_cfg_dedupe = same_cond
-        tr = self.transformer
-        # Independent sub-batches ("lanes") run their reverse chains concurrently on separate HIP streams: every clip's chain
-        # depends only on its own tokens, condition and noise rows (the noise key is the global row index), so the tokens are
-        # those of the single-lane run, and workgroups of one lane fill the tail of the other lane's kernels.
-        # Two lanes by default (measured +8.5 % at bs 16: BENCH_r02 extra.two_lanes); a lane keeps at least 4 clips.
+        # Two lanes by default (measured +8.5 % at bs 16: BENCH_r02 extra.two_lanes); a lane keeps at least 4 clips.  An eager or
+        # traced call runs in one.
+        graphed = use_graph and trace is None
         lanes = kwargs.get("lanes", os.environ.get("GSDD_SAMPLE_LANES", self.sample_lanes))
         lanes = 2 if lanes is None else int(lanes)
-        lanes = lanes if (use_graph and trace is None and lanes > 1 and B % lanes == 0 and B // lanes >= 4) else 1
-        # hipGraph capture is not allowed on the legacy default stream: the loop runs on side streams
+        lanes = lanes if (graphed and lanes > 1 and B % lanes == 0 and B // lanes >= 4) else 1
+        # hipGraph capture is not allowed on the legacy default stream: the lanes run on side streams
         if getattr(self, "_streams", None) is None or len(self._streams) < lanes:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(lanes)]
-        self._stream = self._streams[0]
-        Bs = B // lanes
-        toks, graphs, finals, redo_counters, range_flags = [], [], [], [], []
-        sched = self._sched()
-
-        # The steps of a lane's chain.  `lane` holds what belongs to one sub-batch: its stream st, tokens tok, condition vectors condv
-        # (Te condition tokens), timesteps t2, workspace ws, noise-stream counter sid, M = Bs L positions from global row row0, its
-        # known-position keywords and, for a purity chain, the plan arrays, counters and candidate buffers.
-        def denoise(lane):                      # -> the conditional and the unconditional logits of the lane's tokens at t2
-            logits = tr.run(lane.tok, lane.condv, lane.Te, lane.t2, lane.ws, rep=rep, stream=lane.st)
-            return logits[:lane.M], (logits[lane.M:] if rep == 2 else logits[:lane.M]) if guided else None
-
-        def plain_step(lane, post_skip):
-            ops.d3pm_step(*denoise(lane), lane.tok, lane.tok, sched, lane.t2, lane.sid, K=K, T=T, guidance=float(self.guidance_scale),
-                          seed=self.noise_seed, row0=lane.row0, post_skip=post_skip, stream=lane.st, **trunc_kw, **lane.known_kw)
-
-        def chain_step(lane):
-            plain_step(lane, plan.post_skip)
-            if plan.dt == 1:
-                ops.advance(lane.t2, -1, lane.sid, 1, stream=lane.st)
-            else:                               # skip-step chain: t moves by -(1 + s) and stops at 0 (the appended last step)
-                ops.advance_floor(lane.t2, -plan.dt, 0, lane.sid, 1, stream=lane.st)
-
-        def purity_step(lane):
-            ops.d3pm_purity_step(*denoise(lane), lane.score, lane.smax, lane.cand, lane.sid, K=K, guidance=float(self.guidance_scale),
-                                 prior_rule=plan.rule, prior_weight=plan.weight, seed=self.noise_seed, row0=lane.row0, stream=lane.st,
-                                 **trunc_kw)
-            ops.d3pm_purity_select(lane.tok, lane.tok, lane.cand, lane.score, lane.smax, lane.n_dev, lane.sid, K=K, prior_rule=plan.rule,
-                                   seed=self.noise_seed, stream_add=1, row0=lane.row0, stream=lane.st)
-            ops.advance_plan(lane.step_dev, lane.plan_t, lane.plan_n, lane.t2, lane.n_dev, lane.sid, 2, stream=lane.st)
-
-        def jump_op(lane):                      # the state at level t2 moves forward to t2 + jump; one noise stream, like a step
-            ops.d3pm_forward_jump(lane.tok, lane.tok, lane.jump_table, lane.t2, lane.sid, K=K, T=T, jump=plan.jump, seed=self.noise_seed,
-                                  row0=lane.row0, hold=lane.jump_hold, stream=lane.st)
-            ops.advance(lane.t2, plan.jump, lane.sid, 1, stream=lane.st)
-
-        one_step = purity_step if purity else chain_step
-        lane_list = []
         cur = torch.cuda.current_stream()
-        tr.packed()                                 # packed weights, AdaLN tables and the fragment images are (re)built HERE, on the
-        tr.fragment_images()                        # caller's stream: each lane's wait_stream(cur) below then orders its reads after them
-        for ln in range(lanes):
-            st = self._streams[ln]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                sl = slice(ln * Bs, (ln + 1) * Bs)
-                conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
-                lane = types.SimpleNamespace(st=st, Te=conds.shape[1], M=Bs * L, row0=(self.row_offset + ln * Bs) * L)
-                lane.condv = tr.cond_vectors(conds.contiguous())
-                lane.ws = tr.workspace(rep * Bs, L, dev, rep=rep)
-                redo_counters.append(lane.ws["redo"])
-                range_flags.append(lane.ws["range"])
-                lane.t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
-                lane.sid = torch.tensor([stream0], dtype=torch.int64, device=dev)
-                if not plan.q_sample:
-                    lane.tok = torch.full((Bs, L), K, dtype=torch.int64, device=dev)      # all [MASK] (:613-618)
-                else:                                                                    # q_sample at t = start_step - 1 (:628-630)
-                    lane.tok = torch.empty((Bs, L), dtype=torch.int64, device=dev)
-                    ops.d3pm_q_sample(x0_start[sl].contiguous(), lane.tok, sched, lane.t2[:Bs].contiguous(),
-                                      torch.tensor([self.noise_stream], dtype=torch.int64, device=dev), K=K, T=T,
-                                      seed=self.noise_seed, row0=lane.row0, stream=st)
-                # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they
-                # are constants of the chain, so the captured graph is still one step; nothing at all without a mask
-                lane.known_kw = _known_kwargs(known, dev, sl)
-                if resample:                    # the jump's table and, in hold mode, the positions it copies through
-                    lane.jump_table = self._jump_table(plan.jump, dev)
-                    lane.jump_hold = lane.known_kw["known"] if lane.known_kw["known_mode"] == KNOWN_MODES["hold"] else None
-                    lane.jump_graph = None
-                    lane_list.append(lane)
-                if purity:
-                    # (t, n) of every call plus a (0, 0) sentinel: after the last purity call the counter leaves t = 0 for the plain step
-                    i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
-                    lane.plan_t, lane.plan_n = i64([t for t, _ in plan.calls] + [0]), i64([n for _, n in plan.calls] + [0])
-                    lane.step_dev, lane.n_dev = i64([0]), i64([plan.calls[0][1] if plan.calls else 0])
-                    lane.score = torch.empty((Bs, L), dtype=torch.float32, device=dev)
-                    lane.smax = torch.empty((Bs,), dtype=torch.float32, device=dev)
-                    lane.cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
-                    if plan.final:
-                        finals.append(lane)
+        self.transformer.packed()                   # packed weights, AdaLN tables and the fragment images are (re)built HERE, on the
+        self.transformer.fragment_images()          # caller's stream: each lane's wait_stream(cur) below then orders its reads after them
+        lane_list = []
 
-                if n_steps == 0:                # (a purity schedule that reveals nothing at t >= 1)
-                    pass
-                elif use_graph and trace is None:
-                    one_step(lane)              # eager first step (validates arguments outside capture)
-                    g = ops.Graph()
-                    g.begin(st)
-                    one_step(lane)              # recorded, not executed
-                    g.end(st)
-                    graphs.append(g)
-                elif resample:                  # eager: every op of the plan in order (a trace gets one entry per op)
-                    for kind, _ in plan.ops:
-                        (one_step if kind == "step" else jump_op)(lane)
-                        if trace is not None:
-                            trace.append(lane.tok.clone())
-                else:
-                    for _ in range(n_steps):
-                        one_step(lane)
-                        if trace is not None:
-                            trace.append(lane.tok.clone())
-                toks.append(lane.tok)
-        if graphs and resample:
-            # the plan's ops in order, the lanes alternating per op.  Two linear graphs per lane: the step (above) and the jump kernel with
-            # its counter update; a lane's first jump runs eagerly (arguments validated outside capture) and is recorded right after
-            for kind, _ in plan.ops[1:]:
-                for ln, lane in enumerate(lane_list):
-                    if kind == "step":
-                        graphs[ln].launch(lane.st)
-                    elif lane.jump_graph is None:
-                        with torch.cuda.stream(lane.st):
-                            jump_op(lane)
-                            lane.jump_graph = ops.Graph()
-                            lane.jump_graph.begin(lane.st)
-                            jump_op(lane)       # recorded, not executed
-                            lane.jump_graph.end(lane.st)
-                    else:
-                        lane.jump_graph.launch(lane.st)
-            self._last_graph = graphs[0]
-            self._last_graphs = graphs
-            self._last_jump_graphs = [lane.jump_graph for lane in lane_list]
-        elif graphs:
-            for _ in range(n_steps - 1):        # the lanes' replays are issued alternately so that both queues stay fed
-                for ln, g in enumerate(graphs):
-                    g.launch(self._streams[ln])
-            self._last_graph = graphs[0]
-            self._last_graphs = graphs
-        for lane in finals:                     # the purity chain's ordinary reverse step at t = 0, after the lane's replays
-            with torch.cuda.stream(lane.st):
-                plain_step(lane, 0)
-                if trace is not None:           # (a trace runs in one lane)
-                    trace.append(toks[0].clone())
-        for ln in range(lanes):
-            cur.wait_stream(self._streams[ln])
-            toks[ln].record_stream(cur)
-        tok = toks[0] if lanes == 1 else torch.cat(toks, 0)
-        self._redo_counters = redo_counters     # attention chunk-redo events of this call, one device counter per lane
-        self._range_flags = range_flags
-        self._last_lanes = lanes
-        self._last_plan = plan
-        if not (graphs and resample):           # (the jump graphs belong to the call that made them)
-            self._last_jump_graphs = []
-        self._last_draws = plan.draws
-        self.noise_stream += self._last_draws
-        out = {"content_token": tok}
+        def lane(ln):
+            # Lanes are set up on first use, in order: lane 0's first op is on the GPU while the host sets up lane 1 (setting every
+            # lane up before the first op measured 0.08 % slower at the headline shape)
+            while len(lane_list) <= ln:
+                st = self._streams[len(lane_list)]
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    sl = slice(len(lane_list) * (B // lanes), (len(lane_list) + 1) * (B // lanes))
+                    conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
+                    lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate)))
+            return lane_list[ln]
+        for ln, kind, action in issue_schedule(plan.program, lanes, graphed):
+            lane(ln).issue(kind, action, trace)
+        lane(lanes - 1)                             # (an empty program: the all-[MASK] start is the result)
+        for lane in lane_list:
+            cur.wait_stream(lane.st)
+            lane.tok.record_stream(cur)
+        self._redo_counters = [lane.ws["redo"] for lane in lane_list]      # attention chunk-redo events of this call, per lane
+        self._range_flags = [lane.ws["range"] for lane in lane_list]
+        # the graphs live until the next call: their replays may still be in flight when this one returns
+        self._last_graphs = [lane.graphs for lane in lane_list]
+        self._last_jump_graphs = [lane.graphs.get("jump") for lane in lane_list] if graphed and "jump" in plan.program else []
+        self._last_lanes, self._last_plan, self._last_cfg_dedupe, self._last_draws = lanes, plan, same_cond, plan.draws
+        self.noise_stream += plan.draws
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
-        return out
+        return {"content_token": lane_list[0].tok if lanes == 1 else torch.cat([lane.tok for lane in lane_list], 0)}
 
     def attention_redo_events(self):
         """Chunk-redo events of the attention kernel during the last sample() call (synchronises: reads device counters)."""
@@ -1145,7 +1154,7 @@ class DiffusionTransformer(nn.Module):
         known_kw = _known_kwargs(known, dev)
         B, L = tok.shape
         K, T = self.num_classes - 1, self.num_timesteps
-        guided = abs(self.guidance_scale - 1) >= 1e-3
+        guided = self._guided
         rep = 2 if guided else 1
         conds = torch.cat([cond, cf_cond], 0).float().contiguous() if guided else cond.float().contiguous()
         tr = self.transformer
@@ -1334,13 +1343,12 @@ class DiscreteDiffusion(nn.Module):
                                              or sample_skip_step < 0):
             raise GsddError(f"sample_skip_step must be null or a non-negative int, got {sample_skip_step!r}")
         self.sample_skip_step = None if sample_skip_step is None else int(sample_skip_step)
-        is_int = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
-        if sample_prior_rule is not None and not (is_int(sample_prior_rule) and sample_prior_rule in (0, 1, 2)):
+        if sample_prior_rule is not None and not (_is_int(sample_prior_rule) and sample_prior_rule in (0, 1, 2)):
             raise GsddError(f"sample_prior_rule must be null, 0, 1 or 2, got {sample_prior_rule!r}")
         if sample_prior_weight is not None and (isinstance(sample_prior_weight, bool) or not isinstance(sample_prior_weight, numbers.Real)
                                                 or not sample_prior_weight >= 0):
             raise GsddError(f"sample_prior_weight must be null or a number >= 0, got {sample_prior_weight!r}")
-        if sample_prior_ps is not None and not (is_int(sample_prior_ps) and sample_prior_ps >= 1):
+        if sample_prior_ps is not None and not (_is_int(sample_prior_ps) and sample_prior_ps >= 1):
             raise GsddError(f"sample_prior_ps must be null or an int >= 1, got {sample_prior_ps!r}")
         if not isinstance(sample_prior_scale_schedule, bool):
             raise GsddError(f"sample_prior_scale_schedule must be true or false, got {sample_prior_scale_schedule!r}")
@@ -1354,7 +1362,7 @@ class DiscreteDiffusion(nn.Module):
         self.sample_truncation_rate = check_truncation_rate(sample_truncation_rate, "sample_truncation_rate")
         if sample_condition_frames is not None:
             frames = sample_condition_frames
-            if is_int(frames):
+            if _is_int(frames):
                 if frames < 1:
                     raise GsddError(f"sample_condition_frames must be null, an int >= 1 or a list of frame indices, got {frames!r}")
                 frames = int(frames)
@@ -1363,7 +1371,7 @@ class DiscreteDiffusion(nn.Module):
                     frames = [v for v in frames] if not isinstance(frames, (str, bytes)) else None
                 except TypeError:
                     frames = None
-                if not frames or not all(is_int(v) for v in frames):
+                if not frames or not all(_is_int(v) for v in frames):
                     raise GsddError("sample_condition_frames must be null, an int >= 1 or a non-empty list of frame indices, "
                                     f"got {sample_condition_frames!r}")
                 frames = [int(v) for v in frames]
@@ -1376,7 +1384,7 @@ class DiscreteDiffusion(nn.Module):
         self.sample_condition_frames = sample_condition_frames
         self.sample_known_mode = sample_known_mode
         for name, v, lo in (("sample_resample_jump", sample_resample_jump, 1), ("sample_resample_times", sample_resample_times, 1)):
-            if v is not None and not (is_int(v) and v >= lo):
+            if v is not None and not (_is_int(v) and v >= lo):
                 raise GsddError(f"{name} must be null or an int >= {lo}, got {v!r}")
         if sample_resample_times is not None and sample_resample_times > 1 and sample_resample_jump is None:
             raise GsddError(f"sample_resample_times = {sample_resample_times} needs sample_resample_jump")
