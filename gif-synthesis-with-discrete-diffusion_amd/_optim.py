@@ -40,6 +40,44 @@ class GradArena:
         return self.zeros(tuple(t.shape))
 
 
+class GradBook:
+    """One step's gradients: the name -> gradient dict `g`, the arena they are zero-filled views of, and -- with a reducer (a
+    parallel.GradReducer) -- the data-parallel buckets they leave in.  `bucket()` all-reduces (in place, async) what the arena handed
+    out since the last bucket, anonymous scratch included; a bucket that has been issued must never be written again, so a gradient
+    is requested only when its kernel is about to be enqueued.  `finish(names)` issues the remainder, sends whatever lives outside
+    the issued range (the first step, when the arena is not sized yet, or a step that outgrew it) as one concatenated bucket and
+    waits.  Without a reducer nothing is issued, `names` (any iterable) is not read and `g` is returned as handed out."""
+
+    def __init__(self, arena, reducer=None):
+        self.arena, self.red, self.g, self.mark = arena, reducer, {}, 0
+        arena.reset()                             # every gradient is a zero-filled view of one buffer: one fill per step
+
+    def zeros(self, name, like):
+        self.g[name] = self.arena.zeros_like(like)
+        return self.g[name]
+
+    def scratch(self, shape):
+        """zero-filled arena memory that is no parameter's gradient: it may ride in a bucket, it is never in `g`"""
+        return self.arena.zeros(tuple(shape))
+
+    def bucket(self):
+        a = self.arena
+        if self.red is not None and a.buf is not None and self.mark < a.off <= a.buf.numel():
+            self.red.add(a.buf[self.mark:a.off])
+            self.mark = a.off
+
+    def finish(self, names):
+        if self.red is None:
+            return self.g
+        self.bucket()
+        a = self.arena
+        lo = a.buf.data_ptr() if a.buf is not None else 0
+        issued = lambda t: lo and lo <= t.data_ptr() < lo + 4 * self.mark
+        self.red.add_concatenated(self.g, [n for n in names if not issued(self.g[n])])
+        self.red.finish()
+        return self.g
+
+
 class MultiAdam:
     """Adam state (m, v flat) for a fixed list of parameters; `step(grads)` = one gsdd_adam_multi launch."""
 

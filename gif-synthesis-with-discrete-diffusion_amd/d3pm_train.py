@@ -5,13 +5,15 @@ torch.autograd of the CPU oracle; the sampling path does not depend on anything 
 Reference: MultistageTextMotionModel.allsplit_step (src/models/multistage_text_motion_model.py:170-206: zero_grad ->
 manual_backward -> Adam(lr 1e-4, betas (0.5, 0.999))) around DiffusionTransformer._train_loss
 (src/models/motionencoder/diffusion_transformer.py:391-457); DDP gradient averaging = configs/trainer/default.yaml:8."""
+import itertools
 import os
+import warnings
 
+import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import ops
-from ._optim import GradArena, MultiAdam
+from ._optim import GradArena, GradBook, MultiAdam
 from ._lib import GsddError
 from .parallel import GradReducer, broadcast_module, world_size
 
@@ -56,7 +58,6 @@ class _LinearImages:
         return pieces
 
     def _build(self):
-        import numpy as np
         dev = self.tr.blocks[0].mlp[0].weight.device
         per_block = sum(ops.rows_linear_image_bytes(no, ni) for no, ni, _ in self._pieces(self.tr.blocks[0]).values())
         self.buf = torch.empty((len(self.tr.blocks) * per_block,), dtype=torch.uint8, device=dev)
@@ -95,7 +96,32 @@ class _LinearImages:
         return self.images
 
 
+class _RowGemm:
+    """The block's row GEMMs on the branch the step takes, decided once per step: gsdd_rows_linear on the fragment images `imgs` (one
+    dict per block, `_LinearImages.refresh`) when the block has the north-star widths, else (imgs None) the generic GEMM on the weight.
+    `lin(i, x, name, w, n_out, ...)` is block i's matrix `name`, `lin.t(i, dy, name, w, n_out)` its transpose (the data gradient)."""
+
+    def __init__(self, imgs, device):
+        self.imgs, self.f = imgs, dict(dtype=torch.float32, device=device)
+
+    def __call__(self, i, x, name, w, n_out, head_major=False, bias=None, residual=None, bvec=None, rows_per_batch=0):
+        out = torch.empty((n_out // 4, x.shape[0], 4) if head_major else (x.shape[0], n_out), **self.f)
+        if self.imgs is not None:
+            return ops.rows_linear(x, self.imgs[i][name], n_out, out, bias=bias, bvec=bvec, rows_per_batch=rows_per_batch,
+                                   residual=residual, head_major=head_major)
+        return ops.linear(x, w, out, bias=bias, rows_per_batch=rows_per_batch, residual=residual, bvec=bvec,
+                          out_mode=2 if head_major else 0)
+
+    def t(self, i, dy, name, w, n_out):
+        out = torch.empty((dy.shape[0], n_out), **self.f)
+        if self.imgs is not None:
+            return ops.rows_linear(dy, self.imgs[i][name + "_t"], n_out, out)
+        return ops.linear(dy, w.t().contiguous(), out)
+
+
 class D3PMTrainer:
+    NULL_NAME = "empty_text_embed"       # the learned null embedding in the gradient dict and the optimiser's parameter list
+
     def __init__(self, dm, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, deterministic=None):
         """deterministic: True runs the backward's reductions in their reproducible form (ops.set_deterministic: one workgroup per
         output address instead of float atomics) -- two calls on the same inputs then give the same gradient bits, at a cost in step
@@ -107,7 +133,13 @@ class D3PMTrainer:
         self.state = {}
         self.reducer = GradReducer()
         self._synced = False
-        self._images = None
+        self._images = None                 # _LinearImages, from the first step on the fragment-image branch
+        self._arena = None                  # GradArena, from the first loss_and_grads
+        self._null32 = None                 # f32 copy of dm.empty_text_embed, from the first step that drops with learnable_cf
+        self.last_fwd = self.last_drop = None
+        self._adam, self._pending_adam = None, None         # MultiAdam from the first step; a state loaded before it exists
+        self._graph, self._graphs = None, {}                # the captured step in use; the two most recent by key
+        self._eager_steps, self._graph_failed = 0, False
 
     def _sync_start(self):
         """Once, before the first data-parallel step: every rank takes rank 0's parameters and buffers (what DDP does at wrap time)."""
@@ -117,103 +149,70 @@ class D3PMTrainer:
 
     # ------------------------------------------------------------------ forward with saved activations
     def _forward(self, xt, cond, t):
-        dm, tr = self.dm, self.dm.transformer
+        tr = self.dm.transformer
         p = tr.packed()
         B, L = xt.shape
-        D, H = tr.n_embd, tr.n_head
-        M = B * L
-        dev = xt.device
-        f = dict(dtype=torch.float32, device=dev)
+        D = tr.n_embd
         cond = cond.float().contiguous()
         if cond.dim() != 3 or cond.shape[0] != B:
             raise GsddError(f"the condition must be (B, Te, cond_dim) with B = {B}, got {tuple(cond.shape)}")
         Te = cond.shape[1]
-        flat = cond.reshape(B * Te, -1).contiguous()             # the condition rows [B Te][cond_dim]
-        sv = {"xt": xt, "t": t, "cond": flat, "Te": Te, "layers": []}
-        x = torch.empty((M, D), **f)
+        sv = {"xt": xt, "t": t, "cond": cond.reshape(B * Te, -1).contiguous(), "Te": Te, "p": p, "layers": [],     # cond: rows [B Te][cond_dim]
+              "dims": (B, L, D, tr.n_head), "blocks": list(tr.blocks)}
+        x = torch.empty((B * L, D), dtype=torch.float32, device=xt.device)
         ops.d3pm_embed(xt, p["emb"], p["pos"], x)
-        aws = ops.d3pm_attention_workspace(B, L, H, dev) if L % 32 == 0 else None     # pre-split K/V images (matrix-pipe forward)
-        # the block's row GEMMs run on gsdd_rows_linear (weights as fragment images, refreshed once per step) when the block has
-        # the north-star widths; other widths take the generic GEMM
-        fast = D == 64 and p["layers"] and p["layers"][0]["w1"].shape[0] == 256 and os.environ.get("GSDD_TRAIN_LINEAR") != "gemm"
-        if fast:
+        aws = ops.d3pm_attention_workspace(B, L, tr.n_head, xt.device) if L % 32 == 0 else None     # pre-split K/V images (matrix-pipe forward)
+        # the row GEMMs run on gsdd_rows_linear (weights as fragment images, refreshed once per step) when the block has the
+        # north-star widths; other widths take the generic GEMM
+        imgs = None
+        if D == 64 and p["layers"] and p["layers"][0]["w1"].shape[0] == 256 and os.environ.get("GSDD_TRAIN_LINEAR") != "gemm":
             if self._images is None:
                 self._images = _LinearImages(tr)
             imgs = self._images.refresh(cross=Te > 1)
-        sv["imgs"] = imgs if fast else None
-        for li_, lay in enumerate(p["layers"]):
-            s = {"x_in": x}
-            if Te > 1:
-                # the general block (transformer_utils.py:266-282): x1a = x + proj(attn1); x1 = x1a + proj2(attn2(ln1_1(x1a), cond))
-                im = imgs[li_] if fast else None
-
-                def lin(x_, image, w, bias, n_out, head_major=False, residual=None):
-                    """one row GEMM of the block on the branch this step takes: fragment image, or the generic GEMM"""
-                    out = torch.empty((n_out // 4, M, 4) if head_major else (M, n_out), **f)
-                    if fast:
-                        return ops.rows_linear(x_, im[image], n_out, out, bias=bias, head_major=head_major, residual=residual)
-                    return ops.linear(x_, w, out, bias=bias, out_mode=2 if head_major else 0, residual=residual)
-
-                s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
-                                                  rows_per_batch=L)
-                s["qkv"] = lin(s["hn"], "qkv", lay["wqkv"], lay["bqkv"], 3 * D, head_major=True)
-                s["y"], s["lse"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
-                ops.d3pm_attention_train(s["qkv"][0:H], s["qkv"][H:2 * H], s["qkv"][2 * H:], B, L, H, s["y"], s["lse"], ws=aws)
-                s["x1a"] = lin(s["y"], "proj", lay["wproj"], lay["bproj"], D, residual=x)
-                ada2 = tr._ada2(li_).view(-1)
-                s["stats11"], s["hq"] = ops.ln_fwd(s["x1a"], ada2, ada2[D:], sel=t, gstride=2 * D, rows_per_batch=L)
-                s["q2"] = lin(s["hq"], "q2", lay["wq2"], lay["bq2"], D, head_major=True)
-                s["k2"] = ops.small_linear(flat, lay["wk2"], lay["bk2"])
-                s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
-                s["y2"], s["lse2"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
-                ops.d3pm_cross_attention_train(s["q2"], s["k2"], s["v2"], B, L, Te, H, s["y2"], s["lse2"])
-                s["x1"] = lin(s["y2"], "proj2", lay["wproj2"], lay["bproj2"], D, residual=s["x1a"])
-                s["stats2"], s["h2"] = ops.ln_fwd(s["x1"], lay["g2"], lay["b2"])
-                s["a"] = lin(s["h2"], "w1", lay["w1"], lay["bb1"], lay["w1"].shape[0])
-                s["u"] = ops.gelu2(s["a"])
-                x = lin(s["u"], "w2", lay["w2"], lay["bb2"], D, residual=s["x1"])
-                sv["layers"].append(s)
-                continue
-            if fast:
-                im = imgs[li_]
-                s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
-                                                  rows_per_batch=L)
-                s["qkv"] = ops.rows_linear(s["hn"], im["qkv"], 3 * D, torch.empty((3 * H, M, 4), **f), bias=lay["bqkv"], head_major=True)
-                s["y"], s["lse"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
-                ops.d3pm_attention_train(s["qkv"][0:H], s["qkv"][H:2 * H], s["qkv"][2 * H:], B, L, H, s["y"], s["lse"], ws=aws)
-                s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
-                cvec = ops.small_linear(s["v2"], lay["wproj2"], lay["bproj2"])
-                s["x1"] = ops.rows_linear(s["y"], im["proj"], D, torch.empty((M, D), **f), bias=lay["bproj"], bvec=cvec,
-                                          rows_per_batch=L, residual=x)
-                s["stats2"], s["h2"] = ops.ln_fwd(s["x1"], lay["g2"], lay["b2"])
-                s["a"] = ops.rows_linear(s["h2"], im["w1"], 4 * D, torch.empty((M, 4 * D), **f), bias=lay["bb1"])
-                s["u"] = ops.gelu2(s["a"])
-                x = ops.rows_linear(s["u"], im["w2"], D, torch.empty((M, D), **f), bias=lay["bb2"], residual=s["x1"])
-                sv["layers"].append(s)
-                continue
-            s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
-                                              rows_per_batch=L)          # AdaLayerNorm: statistics + normalised rows in one pass
-            s["qkv"] = ops.linear(s["hn"], lay["wqkv"], torch.empty((3 * H, M, 4), **f), bias=lay["bqkv"], out_mode=2)
-            s["y"], s["lse"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
-            ops.d3pm_attention_train(s["qkv"][0:H], s["qkv"][H:2 * H], s["qkv"][2 * H:], B, L, H, s["y"], s["lse"], ws=aws)
-            s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
-            cvec = ops.small_linear(s["v2"], lay["wproj2"], lay["bproj2"])
-            s["x1"] = ops.linear(s["y"], lay["wproj"], torch.empty((M, D), **f), bias=lay["bproj"], bvec=cvec, rows_per_batch=L,
-                                 residual=x)
-            s["stats2"], s["h2"] = ops.ln_fwd(s["x1"], lay["g2"], lay["b2"])
-            s["a"] = ops.linear(s["h2"], lay["w1"], torch.empty((M, lay["w1"].shape[0]), **f), bias=lay["bb1"])
-            s["u"] = ops.gelu2(s["a"])
-            x = ops.linear(s["u"], lay["w2"], torch.empty((M, D), **f), bias=lay["bb2"], residual=s["x1"])
+        sv["lin"] = _RowGemm(imgs, xt.device)
+        for i in range(len(p["layers"])):
+            s, x = self._block_forward(i, x, sv, aws)
             sv["layers"].append(s)
         sv["x_out"] = x
         sv["statsf"], sv["hf"] = ops.ln_fwd(x, p["gf"], p["bf"])
-        sv["logits"] = ops.linear(sv["hf"], p["wl"], torch.empty((M, p["wl"].shape[0]), **f), bias=p["bl"])
+        sv["logits"] = ops.linear(sv["hf"], p["wl"], torch.empty((B * L, p["wl"].shape[0]), dtype=torch.float32, device=xt.device),
+                                  bias=p["bl"])
         return sv
 
-    # ------------------------------------------------------------------ loss + gradients
-    # ------------------------------------------------------------------ classifier-free training: condition dropout
-    NULL_NAME = "empty_text_embed"       # the learned null embedding in the gradient dict and the optimiser's parameter list
+    def _block_forward(self, i, x, sv, aws):
+        """-> (the activations block i's backward reads, the block's output).  With more than one condition token the middle is the
+        general block (transformer_utils.py:266-282): x1a = x + proj(attn1); x1 = x1a + proj2(attn2(ln1_1(x1a), cond)).  With one
+        token the cross-attention softmax runs over a single key and the block adds the vector proj2(value(cond)) to every position:
+        it is folded into attn1's projection (bvec), and x1a, ln1_1, q2 and k2 are neither computed nor kept."""
+        lay, lin, t, flat, Te = sv["p"]["layers"][i], sv["lin"], sv["t"], sv["cond"], sv["Te"]
+        (B, L, D, H), M = sv["dims"], x.shape[0]
+        f = dict(dtype=torch.float32, device=x.device)
+        s = {"x_in": x}
+        s["stats1"], s["hn"] = ops.ln_fwd(x, lay["ada1"].view(-1), lay["ada1"].view(-1)[D:], sel=t, gstride=2 * D,
+                                          rows_per_batch=L)          # AdaLayerNorm: statistics + normalised rows in one pass
+        s["qkv"] = lin(i, s["hn"], "qkv", lay["wqkv"], 3 * D, head_major=True, bias=lay["bqkv"])
+        s["y"], s["lse"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
+        ops.d3pm_attention_train(s["qkv"][0:H], s["qkv"][H:2 * H], s["qkv"][2 * H:], B, L, H, s["y"], s["lse"], ws=aws)
+        if Te > 1:
+            s["x1a"] = lin(i, s["y"], "proj", lay["wproj"], D, bias=lay["bproj"], residual=x)
+            ada2 = self.dm.transformer._ada2(i).view(-1)
+            s["stats11"], s["hq"] = ops.ln_fwd(s["x1a"], ada2, ada2[D:], sel=t, gstride=2 * D, rows_per_batch=L)
+            s["q2"] = lin(i, s["hq"], "q2", lay["wq2"], D, head_major=True, bias=lay["bq2"])
+            s["k2"] = ops.small_linear(flat, lay["wk2"], lay["bk2"])
+            s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
+            s["y2"], s["lse2"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
+            ops.d3pm_cross_attention_train(s["q2"], s["k2"], s["v2"], B, L, Te, H, s["y2"], s["lse2"])
+            s["x1"] = lin(i, s["y2"], "proj2", lay["wproj2"], D, bias=lay["bproj2"], residual=s["x1a"])
+        else:
+            s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
+            cvec = ops.small_linear(s["v2"], lay["wproj2"], lay["bproj2"])
+            s["x1"] = lin(i, s["y"], "proj", lay["wproj"], D, bias=lay["bproj"], bvec=cvec, rows_per_batch=L, residual=x)
+        s["stats2"], s["h2"] = ops.ln_fwd(s["x1"], lay["g2"], lay["b2"])
+        s["a"] = lin(i, s["h2"], "w1", lay["w1"], lay["w1"].shape[0], bias=lay["bb1"])
+        s["u"] = ops.gelu2(s["a"])
+        return s, lin(i, s["u"], "w2", lay["w2"], D, bias=lay["bb2"], residual=s["x1"])
 
+    # ------------------------------------------------------------------ classifier-free training: condition dropout
     def _dropout_plan(self, cond, null_cond, drop):
         """Validates the step's condition dropout on the host (no device call) -> None when the step drops nothing (cond_drop_prob == 0
         and no mask: the step then launches exactly what it launches without the feature), else (p, learnable)."""
@@ -245,7 +244,7 @@ class D3PMTrainer:
         B, Te, cd = cond.shape
         dev = cond.device
         if learnable:
-            if getattr(self, "_null32", None) is None or self._null32.device != dev:
+            if self._null32 is None or self._null32.device != dev:
                 self._null32 = torch.empty(tuple(dm.empty_text_embed.shape), dtype=torch.float32, device=dev)
             self._null32.copy_(dm.empty_text_embed.detach())                   # fp64 -> f32, one copy node
             rows = self._null32[:Te]
@@ -256,6 +255,7 @@ class D3PMTrainer:
             drop = (drop if drop.dtype == torch.uint8 else drop.to(torch.uint8)).contiguous()
         return ops.cond_dropout(cond, rows, p, seed=dm.noise_seed, sid=sid, row0=dm.row_offset, drop=drop)
 
+    # ------------------------------------------------------------------ loss + gradients
     def loss_and_grads(self, *args, **kwargs):
         """`_loss_and_grads` (see there), bracketed by the reproducible-reductions switch when the trainer is `deterministic`."""
         if not self.deterministic:
@@ -282,30 +282,65 @@ class D3PMTrainer:
         (Te, cond_dim) or (1, Te, cond_dim).  `self.last_drop` keeps the uint8 (B,) decisions (None: no dropout in this step)."""
         plan = self._dropout_plan(cond, null_cond, drop)
         self._sync_start()
-        dm, tr = self.dm, self.dm.transformer
         if not x0.is_cuda:
             raise GsddError("the HIP path needs tensors on a ROCm device (no CPU fallback)")
-        p = tr.packed()
+        tr = self.dm.transformer
+        x0, xt, cond, t, pt = self._prepare(x0, cond, t, pt, sid, plan, null_cond, drop)
+        sv = self._forward(xt, cond, t)
+        fwd, dlogits = self._loss(sv, x0, pt, want_probs)
+        if self._arena is None:
+            self._arena = GradArena(x0.device)
+        book = GradBook(self._arena, self.reducer if (reduce and self.reducer.active()) else None)
+        dx = self._head_backward(sv, dlogits, book)
+        del dlogits
         B, L = x0.shape
-        D, H = tr.n_embd, tr.n_head
+        bws = ops.d3pm_attention_bwd_workspace(B, L, tr.n_head, dx.device) if L % 32 == 0 else None     # operand images (matrix-pipe backward)
+        cws = ops.d3pm_cross_attention_bwd_workspace(B, L, sv["Te"], tr.n_head, dx.device) if sv["Te"] > 1 else None  # delta + the dK / dV partials
+        # the learned null embedding's gradient: every block leaves its (dk2, dv2, Wk2, Wv2) here; the sums over the dropped samples
+        # are formed after the last block, into the arena's last gradient (a bucket that is already out must not be written again)
+        null_terms = [] if (plan is not None and plan[1]) else None
+        n = len(sv["layers"])
+        for i in reversed(range(n)):
+            dx = self._block_backward(i, sv, dx, book, bws, cws, null_terms)
+            if (n - i) % BUCKET_LAYERS == 0:
+                book.bucket()
+        self._embed_backward(sv, dx, book)
+        names = (nm for nm, _ in tr.named_parameters())           # (a generator: the walk over the parameters is paid only with a reducer)
+        if null_terms is not None:
+            # (77, 512) f32, one gsdd_cond_null_grad call per block onto rows [:Te] in the backward's block order (a fixed order: the
+            # same bits every run); rows >= Te keep the arena's zero fill
+            gnull = book.zeros(self.NULL_NAME, self._null32)
+            for dk2, dv2, wk2, wv2 in null_terms:
+                ops.cond_null_grad(dk2, dv2, self.last_drop, wk2, wv2, B, sv["Te"], gnull[:sv["Te"]])
+            names = itertools.chain(names, [self.NULL_NAME])
+        return fwd["loss"], book.finish(names)
+
+    def _prepare(self, x0, cond, t, pt, sid, plan, null_cond, drop):
+        """-> (x0, x_t, condition, t, p(t)) on the device: the weights re-packed if they changed, timesteps drawn if none were given,
+        x_t drawn by q_sample on this step's Philox stream, the condition with its dropped samples substituted."""
+        dm = self.dm
+        dm.transformer.packed()
+        B, L = x0.shape
         K, T = dm.num_classes - 1, dm.num_timesteps
         dev = x0.device
-        f = dict(dtype=torch.float32, device=dev)
         if t is None:
             t, pt = dm.sample_time(B, dev, "importance")
         t, pt = t.to(dev).long().contiguous(), pt.to(dev).float().contiguous()
         if sid is None:
             sid = torch.tensor([dm.noise_stream], dtype=torch.int64, device=dev)
         dm.noise_stream += 1
-        sched = dm._sched()
         x0 = x0.contiguous().long()
         xt = torch.empty_like(x0)
-        ops.d3pm_q_sample(x0, xt, sched, t, sid, K=K, T=T, seed=dm.noise_seed, row0=dm.row_offset * L)
+        ops.d3pm_q_sample(x0, xt, dm._sched(), t, sid, K=K, T=T, seed=dm.noise_seed, row0=dm.row_offset * L)
         self.last_drop = None
         if plan is not None:          # the substituted condition is what the forward, every saved activation and every gradient see
             cond, self.last_drop = self._drop_condition(cond.to(dev).float().contiguous(), plan, null_cond, drop, sid)
-        sv = self._forward(xt, cond, t)
-        kw = dict(K=K, T=T, mask_weight=dm.mask_weight, aux_weight=dm.auxiliary_loss_weight,
+        return x0, xt, cond, t, pt
+
+    def _loss(self, sv, x0, pt, want_probs):
+        """-> (the forward's dict, kept as `self.last_fwd`; d loss / d logits)"""
+        dm, xt, t, sched = self.dm, sv["xt"], sv["t"], self.dm._sched()
+        kw = dict(K=dm.num_classes - 1, T=dm.num_timesteps, mask_weight=dm.mask_weight, aux_weight=dm.auxiliary_loss_weight,
                   adaptive_aux=dm.adaptive_auxiliary_loss)
         if want_probs or os.environ.get("GSDD_TRAIN_LOSS_SPLIT"):      # (the switch: A/B and the equality test of the two paths)
             fwd = ops.d3pm_train_loss(sv["logits"], x0, xt, t, pt, sched, dm.Lt_history, dm.Lt_count, want_probs=want_probs, **kw)
@@ -314,153 +349,121 @@ class D3PMTrainer:
             fwd, dlogits = ops.d3pm_train_loss_grad(sv["logits"], x0, xt, t, pt, sched, dm.Lt_history, dm.Lt_count, **kw)
         fwd["t"], fwd["xt"] = t, xt
         self.last_fwd = fwd
+        return fwd, dlogits
 
-        g = {}
-        if getattr(self, "_arena", None) is None:
-            self._arena = GradArena(dev)
-        self._arena.reset()                       # every gradient below is a zero-filled view of one buffer: one fill per step
-        red = self.reducer if (reduce and self.reducer.active()) else None
-        mark = [0]
-
-        def bucket():                             # all-reduce what the arena handed out since the last bucket (in place, async)
-            a = self._arena
-            if red is not None and a.buf is not None and mark[0] < a.off <= a.buf.numel():
-                red.add(a.buf[mark[0]:a.off])
-                mark[0] = a.off
-
-        def z(name, like):
-            g[name] = self._arena.zeros_like(like)
-            return g[name]
-
-        def tw(w):                              # transposed copy for the data-gradient GEMMs
-            return w.t().contiguous()
-
-        # the learned null embedding's gradient: every block leaves its (dk2, dv2, Wk2, Wv2) here; the sums over the dropped samples
-        # are formed after the last block, into the arena's last gradient (a bucket that is already out must not be written again)
-        null_terms = [] if (plan is not None and plan[1]) else None
-
-        # ---- to_logits
+    def _head_backward(self, sv, dlogits, book):
+        """to_logits (final LayerNorm + the class projection) -> d loss / d (the last block's output); the head's gradients are the
+        first bucket"""
+        p, z = sv["p"], book.zeros
+        D = self.dm.transformer.n_embd
         ops.wgrad(dlogits, sv["hf"], z("to_logits.1.weight", p["wl"]), z("to_logits.1.bias", p["bl"]))
-        dhf = ops.linear(dlogits, tw(p["wl"]), torch.empty((B * L, D), **f))
+        dhf = ops.linear(dlogits, p["wl"].t().contiguous(), torch.empty((dlogits.shape[0], D), dtype=torch.float32, device=dlogits.device))
         dx = ops.ln_bwd(dhf, sv["x_out"], sv["statsf"], p["gf"], dgamma=z("to_logits.0.weight", p["gf"]),
                         dbeta=z("to_logits.0.bias", p["bf"]), gacc_stride=D)
-        del dlogits
-        bucket()
-        bws = ops.d3pm_attention_bwd_workspace(B, L, H, dx.device) if L % 32 == 0 else None     # operand images (matrix-pipe backward)
-        Te = sv["Te"]
-        cws = ops.d3pm_cross_attention_bwd_workspace(B, L, Te, H, dx.device) if Te > 1 else None  # delta + the dK / dV partials
-        for i in reversed(range(len(p["layers"]))):
-            lay, s = p["layers"][i], sv["layers"][i]
-            pre = f"blocks.{i}."
-            blk = tr.blocks[i]
-            # ---- MLP
-            im = sv["imgs"][i] if sv.get("imgs") is not None else None
-            lin_t = (lambda dy_, name, w_, n_out: ops.rows_linear(dy_, im[name], n_out, torch.empty((B * L, n_out), **f))) if im is not None \
-                else (lambda dy_, name, w_, n_out: ops.linear(dy_, tw(w_), torch.empty((B * L, n_out), **f)))
-            ops.wgrad(dx, s["u"], z(pre + "mlp.2.weight", lay["w2"]), z(pre + "mlp.2.bias", lay["bb2"]))
-            du = lin_t(dx, "w2_t", lay["w2"], s["u"].shape[1])
-            da = ops.gelu2(s["a"], du)
-            ops.wgrad(da, s["h2"], z(pre + "mlp.0.weight", lay["w1"]), z(pre + "mlp.0.bias", lay["bb1"]))
-            dh2 = lin_t(da, "w1_t", lay["w1"], D)
-            dx1 = ops.ln_bwd(dh2, s["x1"], s["stats2"], lay["g2"], dx_in=dx, dgamma=z(pre + "ln2.weight", lay["g2"]),
-                             dbeta=z(pre + "ln2.bias", lay["b2"]), gacc_stride=D)
-            if Te > 1:
-                # ---- cross-attention over the condition tokens: proj, attention, query, ln1_1; keys / values against the condition rows
-                ops.wgrad(dx1, s["y2"], z(pre + "attn2.proj.weight", lay["wproj2"]), z(pre + "attn2.proj.bias", lay["bproj2"]))
-                dy2 = lin_t(dx1, "proj2_t", lay["wproj2"], D)
-                dq2, dk2, dv2 = ops.d3pm_cross_attention_bwd(s["q2"], s["k2"], s["v2"], s["y2"], dy2, s["lse2"], B, L, Te, H, cws)
-                dq2 = dq2.permute(1, 0, 2).reshape(B * L, D).contiguous()          # head-major -> rows, the layout wgrad and the row GEMMs take
-                ops.wgrad(dq2, s["hq"], z(pre + "attn2.query.weight", lay["wq2"]), z(pre + "attn2.query.bias", lay["bq2"]))
-                dhq = lin_t(dq2, "q2_t", lay["wq2"], D)
-                ada2 = tr._ada2(i).view(-1)
-                dtab2 = torch.zeros((B, 2 * D), **f)
-                dx1 = ops.ln_bwd(dhq, s["x1a"], s["stats11"], ada2, sel=t, gstride=2 * D, rows_per_batch=L, dx_in=dx1, dgamma=dtab2,
-                                 dbeta=dtab2.view(-1)[D:], gacc_stride=2 * D, acc_by_batch=True)
-                ops.adaln_bwd(dtab2, t, blk.ln1_1.emb.weight.contiguous(), blk.ln1_1.linear.weight.contiguous(),
-                              z(pre + "ln1_1.emb.weight", blk.ln1_1.emb.weight), z(pre + "ln1_1.linear.weight", blk.ln1_1.linear.weight),
-                              z(pre + "ln1_1.linear.bias", blk.ln1_1.linear.bias))
-                ops.small_linear_bwd(dk2, sv["cond"], lay["wk2"], z(pre + "attn2.key.weight", lay["wk2"]),
-                                     z(pre + "attn2.key.bias", lay["bk2"]), want_dx=False)
-                ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
-                                     z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
-                if null_terms is not None:
-                    null_terms.append((dk2, dv2, lay["wk2"], lay["wv2"]))
-                ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
-            else:
-                # ---- attention output projection + the broadcast cross-attention vector
-                ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
-                dcvec = ops.batch_rowsum(dx1, B, L)
-                dv2 = ops.small_linear_bwd(dcvec, s["v2"], lay["wproj2"], z(pre + "attn2.proj.weight", lay["wproj2"]),
-                                           z(pre + "attn2.proj.bias", lay["bproj2"]))
-                ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
-                                     z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
-                if null_terms is not None:          # one condition token: the softmax over a single key has no key term
-                    null_terms.append((None, dv2, None, lay["wv2"]))
-                for nm, ref in (("attn2.key.weight", lay["wk2"]), ("attn2.key.bias", lay["bk2"]),
-                                ("attn2.query.weight", lay["wq2"]), ("attn2.query.bias", lay["bq2"]),
-                                ("ln1_1.emb.weight", blk.ln1_1.emb.weight), ("ln1_1.linear.weight", blk.ln1_1.linear.weight),
-                                ("ln1_1.linear.bias", blk.ln1_1.linear.bias)):
-                    z(pre + nm, ref)                # softmax over a single key: exactly zero gradient
-            dy = lin_t(dx1, "proj_t", lay["wproj"], D)
-            # ---- self-attention
-            qkv = s["qkv"]
-            dqkv = ops.d3pm_attention_bwd(qkv[0:H], qkv[H:2 * H], qkv[2 * H:], s["y"], dy, s["lse"], B, L, H, ws=bws)
-            wq = z(pre + "_wqkv", lay["wqkv"])
-            bq = z(pre + "_bqkv", lay["bqkv"])
-            ops.wgrad(dqkv, s["hn"], wq, bq)
-            for j, nm in enumerate(("query", "key", "value")):        # row blocks of the fused gradient: views, already contiguous
-                g[pre + f"attn1.{nm}.weight"] = wq[j * D:(j + 1) * D]
-                g[pre + f"attn1.{nm}.bias"] = bq[j * D:(j + 1) * D]
-            del g[pre + "_wqkv"], g[pre + "_bqkv"]
-            dhn = lin_t(dqkv, "qkv_t", lay["wqkv"], D)
-            dtab = torch.zeros((B, 2 * D), **f)           # (not in the arena: the arena's size must not depend on the batch size)
-            dx = ops.ln_bwd(dhn, s["x_in"], s["stats1"], lay["ada1"].view(-1), sel=t, gstride=2 * D, rows_per_batch=L,
-                            dx_in=dx1, dgamma=dtab, dbeta=dtab.view(-1)[D:], gacc_stride=2 * D, acc_by_batch=True)
-            ops.adaln_bwd(dtab, t, blk.ln1.emb.weight.contiguous(), blk.ln1.linear.weight.contiguous(),
-                          z(pre + "ln1.emb.weight", blk.ln1.emb.weight), z(pre + "ln1.linear.weight", blk.ln1.linear.weight),
-                          z(pre + "ln1.linear.bias", blk.ln1.linear.bias))
-            if (len(p["layers"]) - i) % BUCKET_LAYERS == 0:
-                bucket()
-        # ---- embeddings
-        ce = tr.content_emb
-        Hs, Ws = ce.spatial_size
-        dpos = self._arena.zeros((Hs * Ws, D))
-        ops.d3pm_embed_bwd(dx, xt, z("content_emb.emb.weight", ce.emb.weight), dpos)
-        ops.batch_rowsum(dpos, Hs, Ws, out=z("content_emb.height_emb.weight", ce.height_emb.weight))
-        dw_ = self._arena.zeros((Ws * D,))
-        ops.colsum(dpos.view(Hs, Ws * D), dw_)
-        g["content_emb.width_emb.weight"] = dw_.view(Ws, D)
-        gnull = None
-        if null_terms is not None:
-            # (77, 512) f32, one gsdd_cond_null_grad call per block onto rows [:Te] in the backward's block order (a fixed order: the
-            # same bits every run); rows >= Te keep the arena's zero fill
-            gnull = z(self.NULL_NAME, self._null32)
-            for dk2, dv2, wk2, wv2 in null_terms:
-                ops.cond_null_grad(dk2, dv2, self.last_drop, wk2, wv2, B, Te, gnull[:Te])
-        if red is not None:
-            bucket()
-            a = self._arena
-            lo = a.buf.data_ptr() if a.buf is not None else 0
-            done = lambda t: lo and lo <= t.data_ptr() < lo + 4 * mark[0]         # inside a bucket that has been issued
-            names = [n for n, _ in tr.named_parameters()] + ([self.NULL_NAME] if gnull is not None else [])
-            rest = [n for n in names if not done(g[n])]
-            if rest:                              # the first step (arena not sized yet): whatever lives outside goes in one bucket
-                flat = torch.cat([g[n].reshape(-1) for n in rest])
-                red.add(flat)
-                off = 0
-                for n in rest:
-                    k = g[n].numel()
-                    g[n] = flat[off:off + k].view(g[n].shape)
-                    off += k
-            red.finish()
-        return fwd["loss"], g
+        book.bucket()
+        return dx
 
-    # ------------------------------------------------------------------ optimiser step (Adam) with DP averaging
+    def _block_backward(self, i, sv, dx, book, bws, cws, null_terms):
+        """d loss / d (block i's output) -> d loss / d (its input); the block's gradients go into the book"""
+        lay, s, blk, lin, t = sv["p"]["layers"][i], sv["layers"][i], sv["blocks"][i], sv["lin"], sv["t"]
+        B, L, D, H = sv["dims"]
+        pre, z = f"blocks.{i}.", book.zeros
+        # ---- MLP
+        ops.wgrad(dx, s["u"], z(pre + "mlp.2.weight", lay["w2"]), z(pre + "mlp.2.bias", lay["bb2"]))
+        du = lin.t(i, dx, "w2", lay["w2"], s["u"].shape[1])
+        da = ops.gelu2(s["a"], du)
+        ops.wgrad(da, s["h2"], z(pre + "mlp.0.weight", lay["w1"]), z(pre + "mlp.0.bias", lay["bb1"]))
+        dh2 = lin.t(i, da, "w1", lay["w1"], D)
+        dx1 = ops.ln_bwd(dh2, s["x1"], s["stats2"], lay["g2"], dx_in=dx, dgamma=z(pre + "ln2.weight", lay["g2"]),
+                         dbeta=z(pre + "ln2.bias", lay["b2"]), gacc_stride=D)
+        # ---- the condition: cross-attention over its tokens, or the broadcast vector; attn1's output projection
+        if sv["Te"] > 1:
+            dx1 = self._cross_attention_backward(i, sv, dx1, book, cws, null_terms)
+        else:
+            self._condition_vector_backward(i, sv, dx1, book, null_terms)
+        dy = lin.t(i, dx1, "proj", lay["wproj"], D)
+        # ---- self-attention
+        qkv = s["qkv"]
+        dqkv = ops.d3pm_attention_bwd(qkv[0:H], qkv[H:2 * H], qkv[2 * H:], s["y"], dy, s["lse"], B, L, H, ws=bws)
+        wq, bq = book.scratch(lay["wqkv"].shape), book.scratch(lay["bqkv"].shape)
+        ops.wgrad(dqkv, s["hn"], wq, bq)
+        for j, nm in enumerate(("query", "key", "value")):        # row blocks of the fused gradient: views, already contiguous
+            book.g[pre + f"attn1.{nm}.weight"] = wq[j * D:(j + 1) * D]
+            book.g[pre + f"attn1.{nm}.bias"] = bq[j * D:(j + 1) * D]
+        dhn = lin.t(i, dqkv, "qkv", lay["wqkv"], D)
+        dtab = torch.zeros((B, 2 * D), dtype=torch.float32, device=dx.device)      # (not in the arena: the arena's size must not depend on the batch size)
+        dx = ops.ln_bwd(dhn, s["x_in"], s["stats1"], lay["ada1"].view(-1), sel=t, gstride=2 * D, rows_per_batch=L,
+                        dx_in=dx1, dgamma=dtab, dbeta=dtab.view(-1)[D:], gacc_stride=2 * D, acc_by_batch=True)
+        ops.adaln_bwd(dtab, t, blk.ln1.emb.weight.contiguous(), blk.ln1.linear.weight.contiguous(),
+                      z(pre + "ln1.emb.weight", blk.ln1.emb.weight), z(pre + "ln1.linear.weight", blk.ln1.linear.weight),
+                      z(pre + "ln1.linear.bias", blk.ln1.linear.bias))
+        return dx
+
+    def _cross_attention_backward(self, i, sv, dx1, book, cws, null_terms):
+        """More than one condition token: attn2's projection, the attention, its query, ln1_1; keys / values against the condition
+        rows; attn1.proj's weight gradient -> d loss / d x1a"""
+        lay, s, blk, lin, t = sv["p"]["layers"][i], sv["layers"][i], sv["blocks"][i], sv["lin"], sv["t"]
+        (B, L, D, H), Te = sv["dims"], sv["Te"]
+        pre, z = f"blocks.{i}.", book.zeros
+        ops.wgrad(dx1, s["y2"], z(pre + "attn2.proj.weight", lay["wproj2"]), z(pre + "attn2.proj.bias", lay["bproj2"]))
+        dy2 = lin.t(i, dx1, "proj2", lay["wproj2"], D)
+        dq2, dk2, dv2 = ops.d3pm_cross_attention_bwd(s["q2"], s["k2"], s["v2"], s["y2"], dy2, s["lse2"], B, L, Te, H, cws)
+        dq2 = dq2.permute(1, 0, 2).reshape(B * L, D).contiguous()          # head-major -> rows, the layout wgrad and the row GEMMs take
+        ops.wgrad(dq2, s["hq"], z(pre + "attn2.query.weight", lay["wq2"]), z(pre + "attn2.query.bias", lay["bq2"]))
+        dhq = lin.t(i, dq2, "q2", lay["wq2"], D)
+        ada2 = self.dm.transformer._ada2(i).view(-1)
+        dtab2 = torch.zeros((B, 2 * D), dtype=torch.float32, device=dx1.device)
+        dx1 = ops.ln_bwd(dhq, s["x1a"], s["stats11"], ada2, sel=t, gstride=2 * D, rows_per_batch=L, dx_in=dx1, dgamma=dtab2,
+                         dbeta=dtab2.view(-1)[D:], gacc_stride=2 * D, acc_by_batch=True)
+        ops.adaln_bwd(dtab2, t, blk.ln1_1.emb.weight.contiguous(), blk.ln1_1.linear.weight.contiguous(),
+                      z(pre + "ln1_1.emb.weight", blk.ln1_1.emb.weight), z(pre + "ln1_1.linear.weight", blk.ln1_1.linear.weight),
+                      z(pre + "ln1_1.linear.bias", blk.ln1_1.linear.bias))
+        ops.small_linear_bwd(dk2, sv["cond"], lay["wk2"], z(pre + "attn2.key.weight", lay["wk2"]),
+                             z(pre + "attn2.key.bias", lay["bk2"]), want_dx=False)
+        ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
+                             z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+        if null_terms is not None:
+            null_terms.append((dk2, dv2, lay["wk2"], lay["wv2"]))
+        ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
+        return dx1
+
+    def _condition_vector_backward(self, i, sv, dx1, book, null_terms):
+        """One condition token: attn1.proj's weight gradient, then the broadcast vector proj2(value(cond)) -- the sum of dx1 over a
+        sample's rows through attn2.proj and attn2.value.  The softmax over a single key gives attn2.query, attn2.key and ln1_1
+        exactly zero gradient: they are requested and left at the arena's fill."""
+        lay, s, blk = sv["p"]["layers"][i], sv["layers"][i], sv["blocks"][i]
+        pre, z = f"blocks.{i}.", book.zeros
+        ops.wgrad(dx1, s["y"], z(pre + "attn1.proj.weight", lay["wproj"]), z(pre + "attn1.proj.bias", lay["bproj"]))
+        dcvec = ops.batch_rowsum(dx1, *sv["dims"][:2])
+        dv2 = ops.small_linear_bwd(dcvec, s["v2"], lay["wproj2"], z(pre + "attn2.proj.weight", lay["wproj2"]),
+                                   z(pre + "attn2.proj.bias", lay["bproj2"]))
+        ops.small_linear_bwd(dv2, sv["cond"], lay["wv2"], z(pre + "attn2.value.weight", lay["wv2"]),
+                             z(pre + "attn2.value.bias", lay["bv2"]), want_dx=False)
+        if null_terms is not None:          # no key term
+            null_terms.append((None, dv2, None, lay["wv2"]))
+        for nm, ref in (("attn2.key.weight", lay["wk2"]), ("attn2.key.bias", lay["bk2"]),
+                        ("attn2.query.weight", lay["wq2"]), ("attn2.query.bias", lay["bq2"]),
+                        ("ln1_1.emb.weight", blk.ln1_1.emb.weight), ("ln1_1.linear.weight", blk.ln1_1.linear.weight),
+                        ("ln1_1.linear.bias", blk.ln1_1.linear.bias)):
+            z(pre + nm, ref)
+
+    def _embed_backward(self, sv, dx, book):
+        """token and position embeddings; the (Hs Ws, D) position gradient and the width sum are arena scratch"""
+        ce = self.dm.transformer.content_emb
+        Hs, Ws = ce.spatial_size
+        D = dx.shape[1]
+        dpos = book.scratch((Hs * Ws, D))
+        ops.d3pm_embed_bwd(dx, sv["xt"], book.zeros("content_emb.emb.weight", ce.emb.weight), dpos)
+        ops.batch_rowsum(dpos, Hs, Ws, out=book.zeros("content_emb.height_emb.weight", ce.height_emb.weight))
+        dw_ = book.scratch((Ws * D,))
+        ops.colsum(dpos.view(Hs, Ws * D), dw_)
+        book.g["content_emb.width_emb.weight"] = dw_.view(Ws, D)
+
     # ------------------------------------------------------------------ the step as one captured graph
     def _graph_usable(self, x0, cond):
         """Single-process steps only: with a data-parallel group the bucketed all-reduces run between the backward's launches through
         torch.distributed, outside any capture (the eager path; its launch gaps are covered by the collectives' own latency)."""
-        return (os.environ.get("GSDD_TRAIN_GRAPH", "1") != "0" and not getattr(self, "_graph_failed", False) and x0.is_cuda
+        return (os.environ.get("GSDD_TRAIN_GRAPH", "1") != "0" and not self._graph_failed and x0.is_cuda
                 and not self.reducer.active() and world_size() == 1 and x0.shape[1] % 32 == 0)
 
     def _capture(self, x0, cond, null_cond=None, drop=None):
@@ -516,10 +519,9 @@ class D3PMTrainer:
 
     def _step_graphed(self, x0, cond, t, pt, null_cond=None, drop=None):
         """Two eager steps first (arenas, images and tables reach their final addresses), then capture, then replays."""
-        self._eager_steps = getattr(self, "_eager_steps", 0)
         # one captured graph per (batch shape, learning rate), the two most recent kept: an epoch's short last batch must not make
         # every epoch capture twice (each graph owns its activations' pool: ~7 GB at bs 16, L = 4096)
-        graphs = self.__dict__.setdefault("_graphs", {})
+        graphs = self._graphs
         # ... and per condition-dropout setting: the probability is a launch constant of the dropout kernel, and the learned null
         # embedding, a mask and a caller's null condition each change the graph's nodes
         key = (tuple(x0.shape), tuple(cond.shape), float(self.lr), float(getattr(self.dm, "cond_drop_prob", 0.0) or 0.0),
@@ -537,7 +539,6 @@ class D3PMTrainer:
                     graphs.pop(next(iter(graphs)))
                 graphs[key] = st
             except Exception as e:                                # noqa: BLE001  (a capture that cannot be made must not cost the step)
-                import warnings
                 warnings.warn(f"D3PMTrainer: the training step could not be captured as a graph ({type(e).__name__}: {e}); running launch by launch")
                 dm.noise_stream, self._adam.step_count = keep
                 self._graph_failed = True
@@ -575,12 +576,12 @@ class D3PMTrainer:
         params = dict(tr.named_parameters())
         self.step_count += 1
         learned = self.NULL_NAME in grads
-        if getattr(self, "_adam", None) is None:
+        if self._adam is None:
             # the learned null embedding joins the parameter list (last) as its f32 copy: one Adam launch updates everything, and
             # optimizer_state() / load_optimizer_state() carry its moments with the rest
             plist = list(params.items()) + ([(self.NULL_NAME, self._null32)] if learned else [])
             self._adam = MultiAdam(plist, self.lr, self.betas, self.eps)
-            self._adam.load_state(getattr(self, "_pending_adam", None))
+            self._adam.load_state(self._pending_adam)
             self._pending_adam = None
         if learned != (self._adam.params[-1][0] == self.NULL_NAME):
             raise GsddError("this trainer's optimiser state was laid out " + ("without" if learned else "with") + " the learned null "
@@ -592,17 +593,15 @@ class D3PMTrainer:
         tr._packed = None                       # parameters changed in place through raw pointers
         return loss
 
-
     # ------------------------------------------------------------------ optimiser state for checkpoints (exact resume)
     def optimizer_state(self):
-        a = getattr(self, "_adam", None)
-        return a.state() if a is not None else getattr(self, "_pending_adam", None)
+        return self._adam.state() if self._adam is not None else self._pending_adam
 
     def load_optimizer_state(self, state):
         self._graph, self._graphs = None, {}                    # (captured steps bake the addresses of the Adam state they were made with)
         if state is None:
             return
-        if getattr(self, "_adam", None) is not None:
+        if self._adam is not None:
             self._adam.load_state(state)
         else:
             self._pending_adam = state

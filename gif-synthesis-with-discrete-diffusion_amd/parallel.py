@@ -127,6 +127,19 @@ class GradReducer:
         self.tensors.append(t)
         self.handles.append(dist.all_reduce(t, async_op=True))
 
+    def add_concatenated(self, g, names):
+        """Gradients that do not lie side by side (g: name -> tensor) leave as one bucket: their concatenation is queued, and the
+        dict is re-bound to views of it, so that what the caller reads afterwards is what the all-reduce wrote."""
+        if not names:
+            return
+        flat = torch.cat([g[n].reshape(-1) for n in names])
+        self.add(flat)
+        off = 0
+        for n in names:
+            k = g[n].numel()
+            g[n] = flat[off:off + k].view(g[n].shape)
+            off += k
+
     def finish(self):
         if not self.handles:
             return

@@ -234,13 +234,7 @@ class VQVAETrainer:
             names = [n for n in g if n not in flushed]
             if red is None or not names:
                 return
-            flat = torch.cat([g[n].reshape(-1) for n in names])
-            red.add(flat)
-            off = 0
-            for n in names:
-                k = g[n].numel()
-                g[n] = flat[off:off + k].view(g[n].shape)
-                off += k
+            red.add_concatenated(g, names)
             flushed.update(names)
         C_, E = vq.n_hiddens, vq.embedding_dim
         dims = sv["dims"]

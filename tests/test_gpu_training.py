@@ -38,17 +38,22 @@ def oracle_grads(sd, a, cfg, t):
                          for k, v in leaf.items() if k.startswith("transformer.") and v.dtype.is_floating_point}
 
 
+@pytest.mark.parametrize("linear", ["images", "gemm"])
 @pytest.mark.parametrize("tvals", [[0, 61], [37, 99]])
-def test_loss_gradients_match_autograd_of_oracle(G, golden, tvals):
+def test_loss_gradients_match_autograd_of_oracle(G, golden, monkeypatch, tvals, linear):
+    """linear: the block's row GEMMs on the fragment images, or (GSDD_TRAIN_LINEAR=gemm) on the generic GEMM"""
     from gsdd_amd.d3pm_train import D3PMTrainer
     sd, a, cfg = golden("d3pm_L64")
     t = torch.tensor(tvals, dtype=torch.long)
     want_loss, want = oracle_grads(sd, a, cfg, t)
+    if linear == "gemm":
+        monkeypatch.setenv("GSDD_TRAIN_LINEAR", "gemm")
     dm = build(G, sd, cfg)
     dm.set_noise(cfg["noise_seed"], stream=int(a["train_stream"]))
     tr = D3PMTrainer(dm)
     loss, got = tr.loss_and_grads(torch.from_numpy(a["train_x0"]).cuda(), torch.from_numpy(a["step_cond"]).cuda(), t=t.cuda(),
                                   pt=(torch.ones(cfg["B"]) / cfg["T"]).cuda())
+    assert (tr._images is not None) == (linear == "images")
     np.testing.assert_allclose(loss.item(), want_loss, rtol=2e-5)
     assert set(got) == set(want), set(got) ^ set(want)
     worst = ("", 0.0)
