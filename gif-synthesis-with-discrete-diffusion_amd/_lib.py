@@ -21,6 +21,7 @@ EXPORTS = [
     "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan", "gsdd_d3pm_forward_jump",
     "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
     "gsdd_ln_apply", "gsdd_d3pm_cross_attention_train", "gsdd_d3pm_cross_attention_bwd", "gsdd_d3pm_cross_attention_bwd_workspace_bytes",
+    "gsdd_d3pm_cross_attention_len", "gsdd_d3pm_cross_attention_train_len", "gsdd_d3pm_cross_attention_bwd_len",
     "gsdd_cond_dropout", "gsdd_cond_null_grad", "gsdd_set_deterministic",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
@@ -173,6 +174,10 @@ def lib():
         L.gsdd_d3pm_cross_attention_bwd_workspace_bytes.argtypes = [_i, _i, _i, _i]
         L.gsdd_d3pm_cross_attention_bwd_workspace_bytes.restype = _i64
         L.gsdd_d3pm_cross_attention_bwd.argtypes = [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]
+        # (..., cond_len device int32 [B], cond_len_host host int32 [B] or NULL, B, L, Te, H, ...)
+        L.gsdd_d3pm_cross_attention_len.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]
+        L.gsdd_d3pm_cross_attention_train_len.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]
+        L.gsdd_d3pm_cross_attention_bwd_len.argtypes = [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]
         L.gsdd_d3pm_step.argtypes = [C.POINTER(StepDesc), _p]
         L.gsdd_d3pm_q_sample.argtypes = [_p, _p, _i, _i, _i, _i, C.POINTER(_p), _p, C.c_uint64, _p, _i64, _p]
         L.gsdd_d3pm_train_loss.argtypes = [C.POINTER(TrainDesc), _p]

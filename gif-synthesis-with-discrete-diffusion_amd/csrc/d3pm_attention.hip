@@ -910,8 +910,10 @@ __global__ __launch_bounds__(256) void d3pm_attention_v4_kernel(const float* __r
 }
 
 // General cross-attention with Te condition tokens (tiny: Te <= 77), one thread per (row, head).
-__global__ void d3pm_cross_attention_kernel(const float* q, const float* kc, const float* vc, int B, int L, int Te, int H,
-                                            float* out) {
+// cond_len (int32 [B], or NULL: all Te keys): batch element b attends to its keys 0 .. cond_len[b] - 1 only (clamped into [1, Te]);
+// keys behind the length are never read.
+__global__ void d3pm_cross_attention_kernel(const float* q, const float* kc, const float* vc, const int32_t* cond_len, int B, int L,
+                                            int Te, int H, float* out) {
     const int64_t M = (int64_t)B * L;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * H) return;
@@ -919,14 +921,15 @@ __global__ void d3pm_cross_attention_kernel(const float* q, const float* kc, con
     const int64_t m = i % M;
     const int b = (int)(m / L);
     const float4 qv = *reinterpret_cast<const float4*>(q + ((int64_t)h * M + m) * 4);
+    const int ne = cond_len != nullptr ? min(max(cond_len[b], 1), Te) : Te;
     float mx = -INFINITY;
-    for (int e = 0; e < Te; ++e) {
+    for (int e = 0; e < ne; ++e) {
         const float4 kv = *reinterpret_cast<const float4*>(kc + ((int64_t)b * Te + e) * (H * 4) + h * 4);
         const float s = (qv.x * kv.x + qv.y * kv.y + qv.z * kv.z + qv.w * kv.w) * 0.5f;
         mx = fmaxf(mx, s);
     }
     float l = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    for (int e = 0; e < Te; ++e) {
+    for (int e = 0; e < ne; ++e) {
         const float4 kv = *reinterpret_cast<const float4*>(kc + ((int64_t)b * Te + e) * (H * 4) + h * 4);
         const float4 vv = *reinterpret_cast<const float4*>(vc + ((int64_t)b * Te + e) * (H * 4) + h * 4);
         const float s = (qv.x * kv.x + qv.y * kv.y + qv.z * kv.z + qv.w * kv.w) * 0.5f;
@@ -1054,13 +1057,37 @@ int gsdd_attention_v4_with_lse(const float* q, const float* k, const float* v, i
     return GSDD_OK;
 }
 
+// cond_len == nullptr: every batch element attends to all Te keys
+static int cross_launch(const float* q, const float* kc, const float* vc, const int32_t* cond_len, int B, int L, int Te, int H,
+                        float* out, void* stream) {
+    const int64_t n = (int64_t)B * L * H;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(d3pm_cross_attention_kernel, grid, dim3(256), 0, (hipStream_t)stream, q, kc, vc, cond_len, B, L, Te, H, out);
+    GSDD_CHECK_LAUNCH();
+    return GSDD_OK;
+}
+
 extern "C" int gsdd_d3pm_cross_attention(const float* q, const float* kc, const float* vc, int B, int L, int Te, int H,
                                          float* out, void* stream) {
     GSDD_CHECK_ARG(q && kc && vc && out, "null pointer");
     GSDD_CHECK_ARG(B > 0 && L > 0 && Te > 0 && H > 0, "bad sizes");
-    const int64_t n = (int64_t)B * L * H;
-    hipLaunchKernelGGL(d3pm_cross_attention_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       q, kc, vc, B, L, Te, H, out);
-    GSDD_CHECK_LAUNCH();
-    return GSDD_OK;
+    return cross_launch(q, kc, vc, nullptr, B, L, Te, H, out, stream);
+}
+
+extern "C" int gsdd_d3pm_cross_attention_len(const float* q, const float* kc, const float* vc, const int32_t* cond_len,
+                                             const int32_t* cond_len_host, int B, int L, int Te, int H, float* out, void* stream) {
+    GSDD_CHECK_ARG(q && kc && vc && cond_len && out, "null pointer");
+    GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
+    GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
+    GSDD_CHECK_ARG(((int64_t)B * L * H + 255) / 256 < (1ll << 31), "grid too large");
+    if (cond_len_host != nullptr) {
+        for (int b = 0; b < B; ++b) {
+            if (cond_len_host[b] < 1 || cond_len_host[b] > Te) {
+                set_error(std::string(__func__) + ": cond_len[" + std::to_string(b) + "] = " + std::to_string(cond_len_host[b]) +
+                          " is outside [1, " + std::to_string(Te) + "]");
+                return GSDD_E_ARG;
+            }
+        }
+    }
+    return cross_launch(q, kc, vc, cond_len, B, L, Te, H, out, stream);
 }

@@ -15,6 +15,12 @@
 // element's results do not depend on which other elements share the launch.
 // Workspace (gsdd_d3pm_cross_attention_bwd_workspace_bytes): delta f32 [H][M], padded to 256 B | partials f32 [B][chunks][H][Te][8]
 // ({dk x 4 (before the 1/2), dv x 4}).
+//
+// Condition lengths (the _len entry points): cond_len, int32 [B], is a kernel argument, NULL in the entry points without lengths.  With
+// it, batch element b attends to its keys 0 .. len[b] - 1 only (a prefix; len[b] clamped into [1, Te] on the device), keys behind it
+// are never read, and the dK / dV lane of such a key skips its rows and writes a zero partial, so that the reduce kernel, which knows
+// nothing of lengths, writes exact zeros into those dkc / dvc rows.  The loops run the same arithmetic in the same order over len[b]
+// keys as over Te: without lengths, and with every length equal to Te, the bits are the ones they always were.
 #include "common.hpp"
 
 namespace gsdd {
@@ -25,10 +31,14 @@ constexpr float CR_C = 0.5f * 1.4426950408889634f;     // 1/2 (the score scale) 
 
 __host__ __device__ __forceinline__ int64_t cross_delta_bytes(int64_t M, int H) { return (M * H * 4 + 255) & ~(int64_t)255; }
 __host__ __device__ __forceinline__ int cross_chunks(int L) { return (L + CR_ROWS - 1) / CR_ROWS; }
+// keys of batch element b: its length clamped into [1, Te] (never an empty softmax, never a row outside kc / vc); no lengths: all Te
+__device__ __forceinline__ int cross_keys(const int32_t* cond_len, int b, int Te) {
+    return cond_len != nullptr ? min(max(cond_len[b], 1), Te) : Te;
+}
 
 // forward: one lane per (row, head), online softmax over the keys (one pass over kc / vc)
-__global__ __launch_bounds__(256) void cross_train_fwd_kernel(const float* q, const float* kc, const float* vc, int B, int L, int Te,
-                                                              int H, float* out, float* lse) {
+__global__ __launch_bounds__(256) void cross_train_fwd_kernel(const float* q, const float* kc, const float* vc, const int32_t* cond_len,
+                                                              int B, int L, int Te, int H, float* out, float* lse) {
     const int64_t M = (int64_t)B * L;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= M * H) return;
@@ -39,8 +49,9 @@ __global__ __launch_bounds__(256) void cross_train_fwd_kernel(const float* q, co
     qv.x *= CR_C; qv.y *= CR_C; qv.z *= CR_C; qv.w *= CR_C;
     const float* kp = kc + (int64_t)b * Te * (H * 4) + h * 4;
     const float* vp = vc + (int64_t)b * Te * (H * 4) + h * 4;
+    const int ne = cross_keys(cond_len, b, Te);
     float mx = -INFINITY, l = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
-    for (int e = 0; e < Te; ++e) {
+    for (int e = 0; e < ne; ++e) {
         const float4 kk = *reinterpret_cast<const float4*>(kp + (int64_t)e * (H * 4));
         const float4 vv = *reinterpret_cast<const float4*>(vp + (int64_t)e * (H * 4));
         const float s = fmaf(qv.x, kk.x, fmaf(qv.y, kk.y, fmaf(qv.z, kk.z, qv.w * kk.w)));
@@ -60,8 +71,8 @@ __global__ __launch_bounds__(256) void cross_train_fwd_kernel(const float* q, co
 
 // dQ (head-major) and delta = dO . o: one lane per (row, head)
 __global__ __launch_bounds__(256) void cross_bwd_dq_kernel(const float* q, const float* kc, const float* vc, const float* o,
-                                                           const float* dO, const float* lse, int B, int L, int Te, int H, float* dq,
-                                                           float* delta) {
+                                                           const float* dO, const float* lse, const int32_t* cond_len, int B, int L,
+                                                           int Te, int H, float* dq, float* delta) {
     const int64_t M = (int64_t)B * L;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= M * H) return;
@@ -76,8 +87,9 @@ __global__ __launch_bounds__(256) void cross_bwd_dq_kernel(const float* q, const
     const float ls = lse[i];
     const float* kp = kc + (int64_t)b * Te * (H * 4) + h * 4;
     const float* vp = vc + (int64_t)b * Te * (H * 4) + h * 4;
+    const int ne = cross_keys(cond_len, b, Te);
     float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
-    for (int e = 0; e < Te; ++e) {
+    for (int e = 0; e < ne; ++e) {
         const float4 kk = *reinterpret_cast<const float4*>(kp + (int64_t)e * (H * 4));
         const float4 vv = *reinterpret_cast<const float4*>(vp + (int64_t)e * (H * 4));
         const float s = fmaf(qv.x, kk.x, fmaf(qv.y, kk.y, fmaf(qv.z, kk.z, qv.w * kk.w)));
@@ -91,16 +103,22 @@ __global__ __launch_bounds__(256) void cross_bwd_dq_kernel(const float* q, const
 }
 
 // dK / dV partials of one chunk of rows of one batch element: one lane per (head, key) pair, rows in ascending order.
-// grid: x = b * chunks + c, y = group of CR_PAIRS pairs
+// grid: x = b * chunks + c, y = group of CR_PAIRS pairs.  The lane of a key at or behind the length reads nothing and writes zeros.
 __global__ __launch_bounds__(CR_PAIRS) void cross_bwd_dkv_kernel(const float* q, const float* kc, const float* vc, const float* dO,
-                                                                 const float* lse, const float* delta, int B, int L, int Te, int H,
-                                                                 float* part) {
+                                                                 const float* lse, const float* delta, const int32_t* cond_len, int B,
+                                                                 int L, int Te, int H, float* part) {
     const int chunks = cross_chunks(L);
     const int b = (int)(blockIdx.x / (unsigned)chunks), c = (int)(blockIdx.x % (unsigned)chunks);
     const int pr = (int)blockIdx.y * CR_PAIRS + (int)threadIdx.x;           // pair = h * Te + e
     if (pr >= H * Te) return;
     const int h = pr / Te, e = pr - h * Te;
     const int64_t M = (int64_t)B * L;
+    float4* dst = reinterpret_cast<float4*>(part + ((int64_t)blockIdx.x * (H * Te) + pr) * 8);
+    if (e >= cross_keys(cond_len, b, Te)) {
+        dst[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+        dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
     const float4 kk = *reinterpret_cast<const float4*>(kc + ((int64_t)b * Te + e) * (H * 4) + h * 4);
     const float4 vv = *reinterpret_cast<const float4*>(vc + ((int64_t)b * Te + e) * (H * 4) + h * 4);
     const int r0 = c * CR_ROWS, r1 = min(L, r0 + CR_ROWS);
@@ -116,7 +134,6 @@ __global__ __launch_bounds__(CR_PAIRS) void cross_bwd_dkv_kernel(const float* q,
         const float ds = p * (dp - delta[hm + r]);
         dk0 = fmaf(ds, qq.x, dk0); dk1 = fmaf(ds, qq.y, dk1); dk2 = fmaf(ds, qq.z, dk2); dk3 = fmaf(ds, qq.w, dk3);
     }
-    float4* dst = reinterpret_cast<float4*>(part + ((int64_t)blockIdx.x * (H * Te) + pr) * 8);
     dst[0] = make_float4(dk0, dk1, dk2, dk3);
     dst[1] = make_float4(dv0, dv1, dv2, dv3);
 }
@@ -149,17 +166,46 @@ static bool cross_sizes_ok(int B, int L, int Te, int H) {
     return B > 0 && L > 0 && H > 0 && H <= 4096 && Te >= 1 && Te <= 77;
 }
 
+// host copy of the lengths, when the caller has one: every entry in [1, Te] (the kernels clamp what no host has seen)
+static int cross_len_check(const char* fn, const int32_t* cond_len_host, int B, int Te) {
+    if (cond_len_host == nullptr) return GSDD_OK;
+    for (int b = 0; b < B; ++b) {
+        if (cond_len_host[b] < 1 || cond_len_host[b] > Te) {
+            set_error(std::string(fn) + ": cond_len[" + std::to_string(b) + "] = " + std::to_string(cond_len_host[b]) + " is outside [1, " +
+                      std::to_string(Te) + "]");
+            return GSDD_E_ARG;
+        }
+    }
+    return GSDD_OK;
+}
+
+// cond_len == nullptr: every batch element attends to all Te keys
+static int cross_train_launch(const float* q, const float* kc, const float* vc, const int32_t* cond_len, int B, int L, int Te, int H,
+                              float* out, float* lse, void* stream) {
+    const int64_t n = (int64_t)B * L * H;
+    GSDD_CHECK_ARG((n + 255) / 256 < (1ll << 31), "grid too large");
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(cross_train_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, q, kc, vc, cond_len, B, L, Te, H, out, lse);
+    GSDD_CHECK_LAUNCH();
+    return GSDD_OK;
+}
+
 extern "C" int gsdd_d3pm_cross_attention_train(const float* q, const float* kc, const float* vc, int B, int L, int Te, int H,
                                                float* out, float* lse, void* stream) {
     GSDD_CHECK_ARG(q && kc && vc && out && lse, "null pointer");
     GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
     GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
-    const int64_t n = (int64_t)B * L * H;
-    GSDD_CHECK_ARG((n + 255) / 256 < (1ll << 31), "grid too large");
-    hipLaunchKernelGGL(cross_train_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, kc, vc, B, L,
-                       Te, H, out, lse);
-    GSDD_CHECK_LAUNCH();
-    return GSDD_OK;
+    return cross_train_launch(q, kc, vc, nullptr, B, L, Te, H, out, lse, stream);
+}
+
+extern "C" int gsdd_d3pm_cross_attention_train_len(const float* q, const float* kc, const float* vc, const int32_t* cond_len,
+                                                   const int32_t* cond_len_host, int B, int L, int Te, int H, float* out, float* lse,
+                                                   void* stream) {
+    GSDD_CHECK_ARG(q && kc && vc && cond_len && out && lse, "null pointer");
+    GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
+    GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
+    if (cross_len_check(__func__, cond_len_host, B, Te) != GSDD_OK) return GSDD_E_ARG;
+    return cross_train_launch(q, kc, vc, cond_len, B, L, Te, H, out, lse, stream);
 }
 
 extern "C" int64_t gsdd_d3pm_cross_attention_bwd_workspace_bytes(int B, int L, int Te, int H) {
@@ -167,12 +213,9 @@ extern "C" int64_t gsdd_d3pm_cross_attention_bwd_workspace_bytes(int B, int L, i
     return cross_delta_bytes((int64_t)B * L, H) + (int64_t)B * cross_chunks(L) * H * Te * 8 * 4;
 }
 
-extern "C" int gsdd_d3pm_cross_attention_bwd(const float* q, const float* kc, const float* vc, const float* o, const float* dO,
-                                             const float* lse, int B, int L, int Te, int H, float* dq, float* dkc, float* dvc,
-                                             void* workspace, int64_t workspace_bytes, void* stream) {
-    GSDD_CHECK_ARG(q && kc && vc && o && dO && lse && dq && dkc && dvc && workspace, "null pointer");
-    GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
-    GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
+static int cross_bwd_launch(const float* q, const float* kc, const float* vc, const float* o, const float* dO, const float* lse,
+                            const int32_t* cond_len, int B, int L, int Te, int H, float* dq, float* dkc, float* dvc, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
     GSDD_CHECK_ARG(workspace_bytes >= gsdd_d3pm_cross_attention_bwd_workspace_bytes(B, L, Te, H), "workspace too small");
     const int64_t n = (int64_t)B * L * H;
     const int64_t bc = (int64_t)B * cross_chunks(L);
@@ -181,13 +224,32 @@ extern "C" int gsdd_d3pm_cross_attention_bwd(const float* q, const float* kc, co
     hipStream_t st = (hipStream_t)stream;
     float* delta = reinterpret_cast<float*>(workspace);
     float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + cross_delta_bytes((int64_t)B * L, H));
-    hipLaunchKernelGGL(cross_bwd_dq_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, kc, vc, o, dO, lse, B, L, Te, H, dq,
-                       delta);
+    const dim3 gq((unsigned)((n + 255) / 256)), gkv((unsigned)bc, (unsigned)((H * Te + CR_PAIRS - 1) / CR_PAIRS));
+    hipLaunchKernelGGL(cross_bwd_dq_kernel, gq, dim3(256), 0, st, q, kc, vc, o, dO, lse, cond_len, B, L, Te, H, dq, delta);
     GSDD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cross_bwd_dkv_kernel, dim3((unsigned)bc, (unsigned)((H * Te + CR_PAIRS - 1) / CR_PAIRS)), dim3(CR_PAIRS), 0, st,
-                       q, kc, vc, dO, lse, delta, B, L, Te, H, part);
+    hipLaunchKernelGGL(cross_bwd_dkv_kernel, gkv, dim3(CR_PAIRS), 0, st, q, kc, vc, dO, lse, delta, cond_len, B, L, Te, H, part);
     GSDD_CHECK_LAUNCH();
     hipLaunchKernelGGL(cross_bwd_reduce_kernel, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, part, B, L, Te, H, dkc, dvc);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
+}
+
+extern "C" int gsdd_d3pm_cross_attention_bwd(const float* q, const float* kc, const float* vc, const float* o, const float* dO,
+                                             const float* lse, int B, int L, int Te, int H, float* dq, float* dkc, float* dvc,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+    GSDD_CHECK_ARG(q && kc && vc && o && dO && lse && dq && dkc && dvc && workspace, "null pointer");
+    GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
+    GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
+    return cross_bwd_launch(q, kc, vc, o, dO, lse, nullptr, B, L, Te, H, dq, dkc, dvc, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gsdd_d3pm_cross_attention_bwd_len(const float* q, const float* kc, const float* vc, const float* o, const float* dO,
+                                                 const float* lse, const int32_t* cond_len, const int32_t* cond_len_host, int B, int L,
+                                                 int Te, int H, float* dq, float* dkc, float* dvc, void* workspace,
+                                                 int64_t workspace_bytes, void* stream) {
+    GSDD_CHECK_ARG(q && kc && vc && o && dO && lse && cond_len && dq && dkc && dvc && workspace, "null pointer");
+    GSDD_CHECK_ARG(B > 0 && L > 0 && H > 0 && H <= 4096, "bad sizes");
+    GSDD_CHECK_ARG(Te >= 1 && Te <= 77, "Te must be in [1, 77]");
+    if (cross_len_check(__func__, cond_len_host, B, Te) != GSDD_OK) return GSDD_E_ARG;
+    return cross_bwd_launch(q, kc, vc, o, dO, lse, cond_len, B, L, Te, H, dq, dkc, dvc, workspace, workspace_bytes, stream);
 }

@@ -242,17 +242,17 @@ class Text2ImageTransformer(nn.Module):
         self.range_demotions = getattr(self, "range_demotions", 0) + 1
         return True
 
-    def run_checked(self, tok, condv, Te, t2, ws, rep=1, stream=None):
+    def run_checked(self, tok, condv, Te, t2, ws, rep=1, stream=None, cond_len=None):
         """run() + the range screen of the f16 hi + lo layer kernel (one 4-byte read back: eager callers only -- forward(),
         p_sample_tokens, the no-grad objective; sample() checks once per call, after its captured loop, and the gradient path
         (d3pm_train.py) does not use the fused layer kernel at all).  The read is a host synchronisation, kept because the caller
         gets these logits: a demoted model (see demote_to_x3p) pays it without ever re-running."""
-        logits = self.run(tok, condv, Te, t2, ws, rep=rep, stream=stream)
+        logits = self.run(tok, condv, Te, t2, ws, rep=rep, stream=stream, cond_len=cond_len)
         if int(ws["range"].item()) != 0:
             ws["range"].zero_()
             if not self.demote_to_x3p(stream):
                 raise GsddError("non-finite activations in the denoiser (inf / NaN in the inputs or weights?)")
-            logits = self.run(tok, condv, Te, t2, ws, rep=rep, stream=stream)
+            logits = self.run(tok, condv, Te, t2, ws, rep=rep, stream=stream, cond_len=cond_len)
         return logits
 
     # ------------------------------------------------------------------ one denoiser pass on the HIP path
@@ -272,12 +272,20 @@ class Text2ImageTransformer(nn.Module):
                 out.append((ops.small_linear(flat, lay["wk2"], lay["bk2"]), v))
         return out
 
-    def run(self, tok, condv, Te, t2, ws, rep=1, stream=None):
+    def run(self, tok, condv, Te, t2, ws, rep=1, stream=None, cond_len=None):
         """tok (B,L) int64; the pass runs on `rep` stacked copies of the batch (B2 = rep*B rows of cond).
-        t2: int64 [B2] timesteps on device.  ws: workspace dict from `workspace()`.  -> logits [B2*L][K]."""
+        t2: int64 [B2] timesteps on device.  ws: workspace dict from `workspace()`.  -> logits [B2*L][K].
+        cond_len: None, or int32 [B2] on the device with Te > 1 -- row b's cross-attention runs over its first cond_len[b] condition
+        tokens only and never reads the others (the kernels clamp a value outside [1, Te]; callers with a host copy check it first,
+        see check_condition_len)."""
         p = self.packed()
         B, L = tok.shape
         B2, D, H = rep * B, self.n_embd, self.n_head
+        if cond_len is not None:
+            if Te == 1:
+                raise GsddError("cond_len needs more than one condition token: with Te = 1 pass None (forward() checks it is all ones)")
+            if cond_len.dtype != torch.int32 or tuple(cond_len.shape) != (B2,) or not cond_len.is_cuda:
+                raise GsddError(f"cond_len must be an int32 device tensor of shape ({B2},), got {cond_len.dtype} {tuple(cond_len.shape)}")
         M = B2 * L
         x, stats, qkv, y, hbuf, logits = ws["x"], ws["stats"], ws["qkv"], ws["y"], ws["h"], ws["logits"]
         ops.d3pm_embed(tok, p["emb"], p["pos"], x, rep=rep, stream=stream)
@@ -325,7 +333,7 @@ class Text2ImageTransformer(nn.Module):
                     ops.d3pm_layer(y, x, L, lay, cvec=condv[li], nxt=nxt, t2=t2, qkv=qkv, kv_img=attn_ws if img else None,
                                    range_flag=ws.get("range"), stream=stream)
         else:
-            self._run_blocks_unfused(layers, condv, Te, t2, ws, B2, L, stream)
+            self._run_blocks_unfused(layers, condv, Te, t2, ws, B2, L, stream, cond_len)
         if D == 64 and p["wl"].shape[0] % 4 == 0:
             with _timed(ws, "logits", stream):
                 ops.d3pm_logits(x, p["gf"], p["bf"], p["wl"], p["bl"], logits, stream=stream)
@@ -334,7 +342,7 @@ class Text2ImageTransformer(nn.Module):
             ops.linear(x, p["wl"], logits, bias=p["bl"], ln=(stats, p["gf"], p["bf"], None, 0), stream=stream)
         return logits
 
-    def _run_blocks_unfused(self, layers, condv, Te, t2, ws, B2, L, stream):
+    def _run_blocks_unfused(self, layers, condv, Te, t2, ws, B2, L, stream, cond_len=None):
         """General path (any T_E): one launch per operator (transformer_utils.py:266-282 in order)."""
         D, H = self.n_embd, self.n_head
         x, stats, qkv, y, hbuf = ws["x"], ws["stats"], ws["qkv"], ws["y"], ws["h"]
@@ -356,7 +364,7 @@ class Text2ImageTransformer(nn.Module):
                 ops.linear(x, lay["wq2"], q2, bias=lay["bq2"],
                            ln=(stats, ada2.view(-1), ada2.view(-1)[D:], t2, 2 * D),
                            rows_per_batch=L, out_mode=2, stream=stream)
-                ops.d3pm_cross_attention(q2, condv[li][0], condv[li][1], B2, L, Te, H, y, stream=stream)
+                ops.d3pm_cross_attention(q2, condv[li][0], condv[li][1], B2, L, Te, H, y, stream=stream, cond_len=cond_len)
                 ops.linear(y, lay["wproj2"], x, bias=lay["bproj2"], residual=x, stream=stream)
             ops.row_stats(x, stats, stream=stream)
             ops.linear(x, lay["w1"], hbuf, bias=lay["bb1"], ln=(stats, lay["g2"], lay["b2"], None, 0),
@@ -381,16 +389,22 @@ class Text2ImageTransformer(nn.Module):
         return ws
 
     @torch.no_grad()
-    def forward(self, input, cond_emb, t):
+    def forward(self, input, cond_emb, t, cond_len=None):
         """(B,L) int64 tokens, (B,Te,cond_dim), (B,) int64 -> logits (B, K, L) (view of [B][L][K] rows,
-        like the reference's rearrange 'b l c -> b c l', transformer_utils.py:442-443)."""
+        like the reference's rearrange 'b l c -> b c l', transformer_utils.py:442-443).
+        cond_len: None, or (B,) integers in [1, Te] -- sample b is conditioned on its first cond_len[b] tokens only; the rows of
+        cond_emb behind them are never read (Te = 1: must be all ones)."""
         if not input.is_cuda:
             raise GsddError("the denoiser runs on the HIP path only: move module and inputs to a ROCm device")
         B, L = input.shape
         ws = self.workspace(B, L, input.device)
         cond_emb = cond_emb.float()
         condv = self.cond_vectors(cond_emb)
-        logits = self.run_checked(input.contiguous(), condv, cond_emb.shape[1], t.to(input.device).long().contiguous(), ws)
+        Te = cond_emb.shape[1]
+        if cond_len is not None:
+            cond_len = check_condition_len(cond_len, B, Te, "cond_len")
+            cond_len = cond_len.to(input.device) if Te > 1 else None          # (one token: the whole length, nothing to mask)
+        logits = self.run_checked(input.contiguous(), condv, Te, t.to(input.device).long().contiguous(), ws, cond_len=cond_len)
         return logits.view(B, L, -1).transpose(1, 2)
 
 
@@ -729,6 +743,43 @@ def check_known(known_mask, content_token, known_mode, *, B, L, K, start_step=0,
     return mask.contiguous(), tok.contiguous(), KNOWN_MODES[known_mode]
 
 
+def check_condition_len(condition_len, B, Te, what="condition_len"):
+    """Validates per-sample condition lengths: (B,) integers in [1, Te] -- sample b is conditioned on its first condition_len[b] tokens
+    (a tokenizer's eot + 1); the condition rows behind them are caption padding the cross-attention never reads.  -> a contiguous int32
+    CPU tensor (one host read per call if the lengths came on a device; a list or a numpy array will do)."""
+    n = torch.as_tensor(condition_len)
+    if n.is_floating_point() or n.is_complex() or n.dtype == torch.bool:
+        raise GsddError(f"{what} must hold integers, got {n.dtype}")
+    if tuple(n.shape) != (B,):
+        raise GsddError(f"{what} must have shape ({B},), one length per sample, got {tuple(n.shape)}")
+    n = n.detach().cpu().to(torch.int64)
+    bad = ((n < 1) | (n > Te)).nonzero()
+    if bad.numel():
+        b = int(bad[0])
+        raise GsddError(f"{what}[{b}] = {int(n[b])} is outside [1, {Te}] (Te condition tokens)")
+    return n.to(torch.int32).contiguous()
+
+
+def _guidance_lens(condition_len, cf_condition_len, B, Te, guided):
+    """The lengths of a sampling call's conditional and unconditional copies -> None (no lengths: the plain call) or
+    (len, cf_len or None), int32 CPU (B,).  cf_condition_len defaults to Te: the null embedding is full length."""
+    if condition_len is None and (cf_condition_len is None or not guided):
+        return None
+    full = torch.full((B,), Te, dtype=torch.int32)
+    len_c = full if condition_len is None else check_condition_len(condition_len, B, Te)
+    if not guided:
+        return (len_c, None) if Te > 1 else None
+    len_u = full if cf_condition_len is None else check_condition_len(cf_condition_len, B, Te, "cf_condition_len")
+    return (len_c, len_u) if Te > 1 else None          # (one token, checked to be all ones: nothing to mask)
+
+
+def _len_kwargs(condition_len, cf_condition_len):
+    """sample()'s length keywords as `_sample_once` takes them; nothing at all without lengths."""
+    if condition_len is None and cf_condition_len is None:
+        return {}
+    return {"condition_len": condition_len, "cf_condition_len": cf_condition_len}
+
+
 def _known_kwargs(known, dev, sl=slice(None)):
     """check_known's result -> the known / x_known / known_mode keywords of ops.d3pm_step for the clips `sl` of the batch, on `dev`;
     nothing at all without a mask."""
@@ -751,7 +802,7 @@ class _Lane:
     keywords, the graph of every op kind captured so far and what only some programs need: the jump's table and held positions, the
     reveal's plan arrays, counters and candidate buffers.  Built on `st`, after st waits for the caller's stream."""
 
-    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw):
+    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw, cond_len=None):
         dev, L, K, Bs, tr = dm.device, dm.shape, dm.num_classes - 1, sl.stop - sl.start, dm.transformer
         self.tr, self.plan, self.st, self.rep, self.guided, self.graphs = tr, plan, st, rep, dm._guided, {}
         self.trunc_kw = trunc_kw                    # a launch constant of both step kernels: a captured graph records it
@@ -759,6 +810,8 @@ class _Lane:
         self.guidance, self.seed = float(dm.guidance_scale), dm.noise_seed
         self.Te, self.M, self.row0 = conds.shape[1], Bs * L, (dm.row_offset + sl.start) * L
         self.condv = tr.cond_vectors(conds.contiguous())
+        # condition lengths of the lane's rep * Bs rows ([len | cf_len]), or None: lane set-up, a device buffer every captured op reads
+        self.cond_len = None if cond_len is None else cond_len.to(dev).contiguous()
         self.ws = tr.workspace(rep * Bs, L, dev, rep=rep)
         i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
         self.t2 = torch.full((rep * Bs,), plan.t0, dtype=torch.int64, device=dev)
@@ -784,7 +837,7 @@ class _Lane:
             self.cand = torch.empty((Bs, L), dtype=torch.int64, device=dev)
 
     def denoise(self):                          # -> the conditional and the unconditional logits of the lane's tokens at t2
-        logits = self.tr.run(self.tok, self.condv, self.Te, self.t2, self.ws, rep=self.rep, stream=self.st)
+        logits = self.tr.run(self.tok, self.condv, self.Te, self.t2, self.ws, rep=self.rep, stream=self.st, cond_len=self.cond_len)
         return logits[:self.M], (logits[self.M:] if self.rep == 2 else logits[:self.M]) if self.guided else None
 
     def plain_step(self, post_skip):
@@ -985,7 +1038,7 @@ class DiffusionTransformer(nn.Module):
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", resample_jump=None,
-               resample_times=1, **kwargs):
+               resample_times=1, condition_len=None, cf_condition_len=None, **kwargs):
         """diffusion_transformer.py:568-644.  The arguments pick a plan (`sample_plan`, `resample_plan`, `_purity_plan`); `_sample_once`
         executes the plan's program -- its op kinds in order -- as `issue_schedule` lays it out over the lanes (a lane runs a kind
         eagerly once, captures it into a hipGraph if it recurs and replays it from then on; use_graph=False or a `trace` list: every
@@ -1006,7 +1059,13 @@ class DiffusionTransformer(nn.Module):
         steps the whole state is diffused forward by that many levels (gsdd_d3pm_forward_jump; "hold" copies the known positions
         through, "renoise" moves them like every other position) and denoised again, `resample_times` times over, so that the sampled
         positions see the known content more than once per level.  Every step and every jump spends one noise stream.  None or
-        resample_times = 1: the call without them, launch for launch."""
+        resample_times = 1: the call without them, launch for launch.
+        condition_len / cf_condition_len ((B,) integers in [1, Te], `check_condition_len`; more than one condition token): clip b is
+        conditioned on the first condition_len[b] rows of condition_embed[b] only -- the rows behind them are caption padding, which
+        the cross-attention never reads -- and its unconditional copy on the first cf_condition_len[b] rows of cf_condition_embed[b]
+        (default Te: the null embedding is full length).  They work with every plan.  The positional condition_mask stays ignored.
+        None: the call without them, launch for launch."""
+        kwargs = dict(kwargs, **_len_kwargs(condition_len, cf_condition_len))
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
         cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
@@ -1034,13 +1093,15 @@ class DiffusionTransformer(nn.Module):
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None, print_log=True,
                     skip_step=1, *, cf_condition_embed=None, use_graph=True, trace=None, known_mask=None, known_mode="renoise",
-                    **kwargs):
+                    condition_len=None, cf_condition_len=None, **kwargs):
         """VQ-Diffusion's skip-step sampler (diffusion_transformer.py:648-713): the denoiser runs at t = T-1, T-1-(1+s), ..., then 0
         (`sample_plan`), and each step's posterior jumps to t - s (for t > s) across the skipped levels.  From all-[MASK] only, as the
         reference asserts.  The reference passes cf_predict_start three of its four arguments; the
         unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit.
-        known_mask / known_mode: as in sample(); a known position is re-noised to the level the step's posterior jumps to."""
+        known_mask / known_mode: as in sample(); a known position is re-noised to the level the step's posterior jumps to.
+        condition_len / cf_condition_len: as in sample()."""
         T = self.num_timesteps
+        kwargs = dict(kwargs, **_len_kwargs(condition_len, cf_condition_len))
         if "resample_jump" in kwargs or "resample_times" in kwargs:
             raise GsddError("sample_fast takes no resample_jump / resample_times: the skip-step chain has no resampling jumps (use sample)")
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
@@ -1074,7 +1135,8 @@ class DiffusionTransformer(nn.Module):
         return out
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
-                     use_graph=True, trace=None, truncation_rate=None, known=None, **kwargs):
+                     use_graph=True, trace=None, truncation_rate=None, known=None, condition_len=None, cf_condition_len=None,
+                     **kwargs):
         """Runs plan.program once: resolves the guidance copies and the lane count, builds the lanes, issues `issue_schedule`'s
         entries and joins the lanes' streams."""
         dev = self.device
@@ -1088,8 +1150,14 @@ class DiffusionTransformer(nn.Module):
         # Then one copy runs and the step kernel reads its logits on both sides of log p_u + s (log p_c - log p_u): the same values
         # through the same arithmetic as the stacked pass, at half the denoiser work.  (One host comparison per sample() call;
         # GSDD_CFG_DEDUPE=0 keeps the two copies.)
+        # (With condition lengths the copies must also attend to the same rows: equal lengths.)
+        lens = None
+        if condition_len is not None or cf_condition_len is not None:
+            if cond.dim() != 3:
+                raise GsddError(f"condition_len needs condition_embed (B, Te, cond_dim), got {tuple(cond.shape)}")
+            lens = _guidance_lens(condition_len, cf_condition_len, B, cond.shape[1], self._guided)
         same_cond = (self._guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape
-                     and bool(torch.equal(cond, cf)))
+                     and bool(torch.equal(cond, cf)) and (lens is None or bool(torch.equal(lens[0], lens[1]))))
         rep = 2 if (self._guided and not same_cond) else 1
         x0 = None
         if plan.q_sample:
@@ -1119,7 +1187,8 @@ class DiffusionTransformer(nn.Module):
                 with torch.cuda.stream(st):
                     sl = slice(len(lane_list) * (B // lanes), (len(lane_list) + 1) * (B // lanes))
                     conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
-                    lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate)))
+                    lane_len = None if lens is None else (torch.cat([lens[0][sl], lens[1][sl]]) if rep == 2 else lens[0][sl])
+                    lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate), lane_len))
             return lane_list[ln]
         for ln, kind, action in issue_schedule(plan.program, lanes, graphed):
             lane(ln).issue(kind, action, trace)
@@ -1145,10 +1214,11 @@ class DiffusionTransformer(nn.Module):
     # ------------------------------------------------------------------ single-step pieces (parity tests, training glue)
     @torch.no_grad()
     def p_sample_tokens(self, tok, cond, cf_cond, t, stream_id, post_dbg=None, x0_dbg=None, post_skip=0, truncation_rate=None,
-                        known=None):
+                        known=None, condition_len=None, cf_condition_len=None):
         """One reverse step on tokens (p_sample, diffusion_transformer.py:304-352, prior_rule 0); post_skip > 0: the posterior at
         t - post_skip for t > post_skip (a sample_fast step, :700-704); truncation_rate: top-r truncation of the guided row;
-        known: what `check_known` returns (mask, clean tokens, mode) -- those positions skip the learned step as in sample()."""
+        known: what `check_known` returns (mask, clean tokens, mode) -- those positions skip the learned step as in sample();
+        condition_len / cf_condition_len: as in sample()."""
         trunc_kw = _trunc_kwargs(check_truncation_rate(truncation_rate))
         dev = tok.device
         known_kw = _known_kwargs(known, dev)
@@ -1161,7 +1231,11 @@ class DiffusionTransformer(nn.Module):
         ws = tr.workspace(rep * B, L, dev, rep=rep)
         condv = tr.cond_vectors(conds)
         t2 = torch.cat([t, t]).contiguous() if guided else t.contiguous()
-        logits = tr.run_checked(tok.contiguous(), condv, conds.shape[1], t2.long(), ws, rep=rep)
+        lens = None
+        if condition_len is not None or cf_condition_len is not None:
+            lens = _guidance_lens(condition_len, cf_condition_len, B, conds.shape[1], guided)
+        cond_len = None if lens is None else (torch.cat(lens) if guided else lens[0]).to(dev)
+        logits = tr.run_checked(tok.contiguous(), condv, conds.shape[1], t2.long(), ws, rep=rep, cond_len=cond_len)
         sid = torch.tensor([stream_id], dtype=torch.int64, device=dev)
         out = torch.empty_like(tok)
         M = B * L
@@ -1187,7 +1261,7 @@ class DiffusionTransformer(nn.Module):
         raise ValueError(method)
 
     @torch.no_grad()
-    def _train_loss(self, x, cond_emb, is_train=True, want_probs=True):
+    def _train_loss(self, x, cond_emb, is_train=True, want_probs=True, cond_len=None):
         """_train_loss (diffusion_transformer.py:391-457) as HIP kernels: q_sample -> denoiser -> fused KL/NLL/aux
         reduction (forward value; the gradient path is d3pm_train.py, reached through forward() when autograd is enabled)."""
         dev = x.device
@@ -1205,7 +1279,10 @@ class DiffusionTransformer(nn.Module):
         tr = self.transformer
         ws = tr.workspace(B, L, dev)
         cond = cond_emb.float().contiguous()
-        logits = tr.run_checked(xt, tr.cond_vectors(cond), cond.shape[1], t, ws)
+        if cond_len is not None:      # (B,) condition lengths: validated on the host; one token -> nothing to mask
+            cond_len = check_condition_len(cond_len, B, cond.shape[1], "condition_len")
+            cond_len = cond_len.to(dev) if cond.shape[1] > 1 else None
+        logits = tr.run_checked(xt, tr.cond_vectors(cond), cond.shape[1], t, ws, cond_len=cond_len)
         aux_w = self.auxiliary_loss_weight if is_train else 0.0
         out = ops.d3pm_train_loss(logits, x0, xt, t, pt, sched, self.Lt_history, self.Lt_count, K=K, T=T,
                                   mask_weight=self.mask_weight, aux_weight=aux_w,
@@ -1214,7 +1291,9 @@ class DiffusionTransformer(nn.Module):
         return out
 
     def forward(self, input, return_loss=False, return_logits=True, return_att_weight=False, is_train=True, **kwargs):
-        """diffusion_transformer.py:520-565 -> {'logits': exp(log_model_prob) (B,K+1,L), 'loss', 'pred_data' (B,L)}."""
+        """diffusion_transformer.py:520-565 -> {'logits': exp(log_model_prob) (B,K+1,L), 'loss', 'pred_data' (B,L)}.
+        input["condition_len"] (optional, (B,) integers in [1, Te]): sample b is conditioned on the first condition_len[b] rows of
+        condition_embed_token[b] only (caption padding behind them; the rows must still be finite when training)."""
         tok = input["content_token"]
         if not tok.is_cuda:
             raise GsddError("the HIP path needs tensors on a ROCm device (no CPU fallback)")
@@ -1227,7 +1306,7 @@ class DiffusionTransformer(nn.Module):
             # no-grad objective below and the sampler never drop a condition)
             from .d3pm_train import train_forward
             loss, r = train_forward(self, tok, cond.float(), want_probs=return_logits, null_cond=input.get("null_condition_embed_token"),
-                                    drop=input.get("condition_drop"))
+                                    drop=input.get("condition_drop"), cond_len=input.get("condition_len"))
             out = {"pred_data": r["x0_recon"]}
             if return_logits:
                 out["logits"] = r["probs"]
@@ -1237,7 +1316,7 @@ class DiffusionTransformer(nn.Module):
             return out
         out = {}
         if is_train:
-            r = self._train_loss(tok, cond.float(), is_train=True, want_probs=return_logits)
+            r = self._train_loss(tok, cond.float(), is_train=True, want_probs=return_logits, cond_len=input.get("condition_len"))
             if return_logits:
                 out["logits"] = r["probs"]
             if return_loss:
@@ -1321,13 +1400,20 @@ class DiscreteDiffusion(nn.Module):
     train_cond_drop_prob: null, or the probability in [0, 1] with which a training sample's text condition is replaced by the null
     condition (classifier-free training; sets the diffusion model's cond_drop_prob).  The null condition is the learned
     empty_text_embed when the diffusion model has learnable_cf, else the provider's embedding of "" -- the unconditional branch the
-    sampler guides with."""
+    sampler guides with.
+    mask_text_padding: true asks a per-token provider for each caption's length (end-of-text position + 1) and hands it to the training
+    objective and the sampler as condition lengths: the cross-attention then runs over a caption's own tokens and never reads the
+    padding behind them, so a sample does not depend on how wide the batch was padded.  The unconditional copy and a dropped training
+    sample stay full length.  Dropped with zero_text_emb (condition and null condition are the same zeros there)."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
                  sample_condition_frames=None, sample_known_mode="renoise", sample_resample_jump=None, sample_resample_times=None,
-                 train_cond_drop_prob=None, **kwargs):
+                 train_cond_drop_prob=None, mask_text_padding=False, **kwargs):
         super().__init__()
+        if not isinstance(mask_text_padding, bool):
+            raise GsddError(f"mask_text_padding must be true or false, got {mask_text_padding!r}")
+        self.mask_text_padding = mask_text_padding
         p_drop = None if train_cond_drop_prob is None else check_cond_drop_prob(train_cond_drop_prob, "train_cond_drop_prob")
         if not isinstance(textencoder, nn.Module) and not callable(textencoder):
             textencoder = _instantiate(textencoder)
@@ -1403,10 +1489,14 @@ class DiscreteDiffusion(nn.Module):
                             "frames and at least one must be left to sample")
         return frame_mask(latent_shape, frames)
 
-    def _text(self, texts, dev):
-        emb = self.textencoder(texts)                                  # (B, C) pooled, or (B, Te, C) from a per-token provider
-        emb = (emb.unsqueeze(1) if emb.dim() == 2 else emb).to(dev)
-        return torch.zeros_like(emb) if self.zero_text_emb else emb.float()
+    def _text(self, texts, dev, return_lengths=False):
+        """-> the (B, Te, C) condition of `texts`; return_lengths: (condition, the captions' int32 (B,) host lengths, or None when
+        mask_text_padding is off or the embedding is zeroed)."""
+        want = return_lengths and self.mask_text_padding and not self.zero_text_emb
+        emb, lens = self.textencoder(texts, return_lengths=True) if want else (self.textencoder(texts), None)
+        emb = (emb.unsqueeze(1) if emb.dim() == 2 else emb).to(dev)   # (B, C) pooled, or (B, Te, C) from a per-token provider
+        emb = torch.zeros_like(emb) if self.zero_text_emb else emb.float()
+        return (emb, lens) if return_lengths else emb
 
     def null_condition(self, dev):
         """The null condition a training step with condition dropout needs from the caller: None when nothing is dropped or the
@@ -1434,9 +1524,9 @@ class DiscreteDiffusion(nn.Module):
             quant = autoencoder.encode(x)
         quant_flat = quant.view(x.shape[0], -1)
         with torch.no_grad():
-            text_emb = self._text(batch["text"], dev)
+            text_emb, text_len = self._text(batch["text"], dev, return_lengths=True)
         diffusion_out = self.diffusion_model({"condition_embed_token": text_emb, "content_token": quant_flat,
-                                              "null_condition_embed_token": self.null_condition(dev)},
+                                              "null_condition_embed_token": self.null_condition(dev), "condition_len": text_len},
                                              return_loss=True, return_logits=False)   # (`logits` = exp(log_model_prob), a (B, K+1, L)
         # tensor the reference computes here and never reads (discrete_diffusion.py:38-41, :66-81): not asked for, so the loss and its gradient take the one-pass kernel)
         # arg-max over K+1 classes can only return [MASK] when every code row sits at the -70 clamp; the reference would
@@ -1465,7 +1555,8 @@ class DiscreteDiffusion(nn.Module):
                 shape = tuple(quant.shape[1:])
                 mask = self.condition_frame_mask(shape)     # the conditioned latent frames keep the input clip's own codes
                 known_kw = {} if mask is None else {"known_tokens": quant_flat, "known_mask": mask}
-                inference_out = self.sample_videos(batch["text"], autoencoder, latent_shape=shape, text_emb=text_emb, **known_kw)
+                inference_out = self.sample_videos(batch["text"], autoencoder, latent_shape=shape, text_emb=text_emb, text_len=text_len,
+                                                   **known_kw)
         if do_inference:
             out = LazyOutputs(pred_data=inference_out, pred_single_step=single_step_out, gt_data=x, losses=diffusion_out["loss"], test=test)
         else:
@@ -1476,14 +1567,18 @@ class DiscreteDiffusion(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None):
+    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None, text_len=None):
         """The inference branch of forward (discrete_diffusion.py:44-62): text -> tokens -> decoded clips.
         known_tokens (B, L) / known_mask ((B, L) or (L,) bool): clean tokens to keep at the mask's positions (the sampler's
-        content_token / known_mask, with sample_known_mode); without a mask the call is the plain one."""
+        content_token / known_mask, with sample_known_mode); without a mask the call is the plain one.
+        text_len goes with text_emb: the captions' (B,) condition lengths (the sampler's condition_len), None for none; without
+        text_emb both come from the provider."""
         dev = autoencoder.device
         B = len(texts)
         if text_emb is None:
-            text_emb = self._text(texts, dev)
+            text_emb, text_len = self._text(texts, dev, return_lengths=True)
+        if self.zero_text_emb:
+            text_len = None
         dm = self.diffusion_model
         if dm.learnable_cf:                     # the learned null embedding is the unconditional condition (diffusion_transformer.py:541-543)
             cf_emb = dm._cf_embed(text_emb, None)
@@ -1510,6 +1605,8 @@ class DiscreteDiffusion(nn.Module):
             if self.sample_resample_jump is not None:
                 known_kw.update(resample_jump=self.sample_resample_jump,
                                 resample_times=1 if self.sample_resample_times is None else self.sample_resample_times)
+        if text_len is not None:
+            known_kw = dict(known_kw, condition_len=text_len)          # (the unconditional copy stays full length)
         if self.sample_skip_step is None:
             out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=content, filter_ratio=0, **known_kw)
         else:

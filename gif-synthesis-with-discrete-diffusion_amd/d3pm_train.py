@@ -148,7 +148,7 @@ class D3PMTrainer:
         self._synced = True
 
     # ------------------------------------------------------------------ forward with saved activations
-    def _forward(self, xt, cond, t):
+    def _forward(self, xt, cond, t, cond_len=None):
         tr = self.dm.transformer
         p = tr.packed()
         B, L = xt.shape
@@ -158,6 +158,7 @@ class D3PMTrainer:
             raise GsddError(f"the condition must be (B, Te, cond_dim) with B = {B}, got {tuple(cond.shape)}")
         Te = cond.shape[1]
         sv = {"xt": xt, "t": t, "cond": cond.reshape(B * Te, -1).contiguous(), "Te": Te, "p": p, "layers": [],     # cond: rows [B Te][cond_dim]
+              "cond_len": cond_len,              # None, or int32 [B] on the device: the condition tokens each sample attends to
               "dims": (B, L, D, tr.n_head), "blocks": list(tr.blocks)}
         x = torch.empty((B * L, D), dtype=torch.float32, device=xt.device)
         ops.d3pm_embed(xt, p["emb"], p["pos"], x)
@@ -201,7 +202,7 @@ class D3PMTrainer:
             s["k2"] = ops.small_linear(flat, lay["wk2"], lay["bk2"])
             s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
             s["y2"], s["lse2"] = torch.empty((M, D), **f), torch.empty((H * M,), **f)
-            ops.d3pm_cross_attention_train(s["q2"], s["k2"], s["v2"], B, L, Te, H, s["y2"], s["lse2"])
+            ops.d3pm_cross_attention_train(s["q2"], s["k2"], s["v2"], B, L, Te, H, s["y2"], s["lse2"], cond_len=sv["cond_len"])
             s["x1"] = lin(i, s["y2"], "proj2", lay["wproj2"], D, bias=lay["bproj2"], residual=s["x1a"])
         else:
             s["v2"] = ops.small_linear(flat, lay["wv2"], lay["bv2"])
@@ -267,7 +268,8 @@ class D3PMTrainer:
             ops.set_deterministic(prev)
 
     @torch.no_grad()
-    def _loss_and_grads(self, x0, cond, t=None, pt=None, want_probs=False, reduce=False, sid=None, null_cond=None, drop=None):
+    def _loss_and_grads(self, x0, cond, t=None, pt=None, want_probs=False, reduce=False, sid=None, null_cond=None, drop=None,
+                        cond_len=None):
         """-> (loss tensor [1], {state_dict name: gradient}) for the transformer's parameters.  The gradients are views of one
         arena that the next call re-uses; `self.last_fwd` keeps the forward's dict (x0_recon, per_sample, probs if asked).
         reduce=True: the gradients come back averaged over the data-parallel group; the all-reduce runs in buckets of
@@ -279,14 +281,21 @@ class D3PMTrainer:
         -- `cond_drop_rows` restates it; the draw shares no counter with q_sample's, so x_t is that of the step without dropout.
         `drop`, a (B,) bool mask, overrides the draw.  The null condition is dm.empty_text_embed[:Te] with dm.learnable_cf -- the
         gradient dict then carries its gradient under "empty_text_embed", (77, 512) with rows >= Te exactly zero -- else `null_cond`,
-        (Te, cond_dim) or (1, Te, cond_dim).  `self.last_drop` keeps the uint8 (B,) decisions (None: no dropout in this step)."""
+        (Te, cond_dim) or (1, Te, cond_dim).  `self.last_drop` keeps the uint8 (B,) decisions (None: no dropout in this step).
+        cond_len ((B,) integers in [1, Te]; more than one condition token): sample b's cross-attention runs over its first cond_len[b]
+        condition tokens only; the rows behind them are caption padding, never read by the attention, and the attention's key / value
+        gradients there are exact zeros.  Those zeros are multiplied by the padding rows in the key / value weight gradients, so the
+        condition rows must be FINITE in training, padding included (a condition that comes on the host is checked).  Lengths on the
+        host (a CPU tensor, a list) are validated here; an int32 tensor on the device is taken as it is, without a read back -- the
+        kernels clamp it into [1, Te].  A dropped sample takes the null rows and length Te: the null condition is full length."""
+        cond_len = self._check_lengths(cond, cond_len)
         plan = self._dropout_plan(cond, null_cond, drop)
         self._sync_start()
         if not x0.is_cuda:
             raise GsddError("the HIP path needs tensors on a ROCm device (no CPU fallback)")
         tr = self.dm.transformer
-        x0, xt, cond, t, pt = self._prepare(x0, cond, t, pt, sid, plan, null_cond, drop)
-        sv = self._forward(xt, cond, t)
+        x0, xt, cond, t, pt, cond_len = self._prepare(x0, cond, t, pt, sid, plan, null_cond, drop, cond_len)
+        sv = self._forward(xt, cond, t, cond_len)
         fwd, dlogits = self._loss(sv, x0, pt, want_probs)
         if self._arena is None:
             self._arena = GradArena(x0.device)
@@ -315,9 +324,27 @@ class D3PMTrainer:
             names = itertools.chain(names, [self.NULL_NAME])
         return fwd["loss"], book.finish(names)
 
-    def _prepare(self, x0, cond, t, pt, sid, plan, null_cond, drop):
-        """-> (x0, x_t, condition, t, p(t)) on the device: the weights re-packed if they changed, timesteps drawn if none were given,
-        x_t drawn by q_sample on this step's Philox stream, the condition with its dropped samples substituted."""
+    def _check_lengths(self, cond, cond_len):
+        """The step's condition lengths -> None (no lengths, or one condition token: nothing to mask) or an int32 (B,) tensor, on the
+        device as given or validated on the host (`check_condition_len`)."""
+        if cond_len is None:
+            return None
+        if cond.dim() != 3:
+            raise GsddError(f"the condition must be (B, Te, cond_dim), got {tuple(cond.shape)}")
+        B, Te = cond.shape[:2]
+        if not cond.is_cuda and not bool(torch.isfinite(cond).all()):
+            raise GsddError("cond_len: the condition holds inf / NaN; in training every condition row must be finite, padding included "
+                            "(the zero key / value gradients of the padding are multiplied by those rows)")
+        if torch.is_tensor(cond_len) and cond_len.is_cuda and cond_len.dtype == torch.int32 and tuple(cond_len.shape) == (B,) and Te > 1:
+            return cond_len.contiguous()
+        from .d3pm import check_condition_len
+        cond_len = check_condition_len(cond_len, B, Te, "cond_len")
+        return cond_len if Te > 1 else None
+
+    def _prepare(self, x0, cond, t, pt, sid, plan, null_cond, drop, cond_len=None):
+        """-> (x0, x_t, condition, t, p(t), condition lengths) on the device: the weights re-packed if they changed, timesteps drawn if
+        none were given, x_t drawn by q_sample on this step's Philox stream, the condition with its dropped samples substituted (and
+        their lengths set to Te)."""
         dm = self.dm
         dm.transformer.packed()
         B, L = x0.shape
@@ -335,7 +362,11 @@ class D3PMTrainer:
         self.last_drop = None
         if plan is not None:          # the substituted condition is what the forward, every saved activation and every gradient see
             cond, self.last_drop = self._drop_condition(cond.to(dev).float().contiguous(), plan, null_cond, drop, sid)
-        return x0, xt, cond, t, pt
+        if cond_len is not None:
+            cond_len = cond_len.to(dev)
+            if plan is not None:      # a dropped sample attends to all Te null rows (formed on the device: the decisions live there)
+                cond_len = torch.where(self.last_drop != 0, torch.full_like(cond_len, cond.shape[1]), cond_len)
+        return x0, xt, cond, t, pt, cond_len
 
     def _loss(self, sv, x0, pt, want_probs):
         """-> (the forward's dict, kept as `self.last_fwd`; d loss / d logits)"""
@@ -407,7 +438,10 @@ class D3PMTrainer:
         pre, z = f"blocks.{i}.", book.zeros
         ops.wgrad(dx1, s["y2"], z(pre + "attn2.proj.weight", lay["wproj2"]), z(pre + "attn2.proj.bias", lay["bproj2"]))
         dy2 = lin.t(i, dx1, "proj2", lay["wproj2"], D)
-        dq2, dk2, dv2 = ops.d3pm_cross_attention_bwd(s["q2"], s["k2"], s["v2"], s["y2"], dy2, s["lse2"], B, L, Te, H, cws)
+        # (with condition lengths the dk2 / dv2 rows of the padding are exact zeros: they add nothing to the key / value weight gradients
+        # below as long as the condition rows there are finite)
+        dq2, dk2, dv2 = ops.d3pm_cross_attention_bwd(s["q2"], s["k2"], s["v2"], s["y2"], dy2, s["lse2"], B, L, Te, H, cws,
+                                                     cond_len=sv["cond_len"])
         dq2 = dq2.permute(1, 0, 2).reshape(B * L, D).contiguous()          # head-major -> rows, the layout wgrad and the row GEMMs take
         ops.wgrad(dq2, s["hq"], z(pre + "attn2.query.weight", lay["wq2"]), z(pre + "attn2.query.bias", lay["bq2"]))
         dhq = lin.t(i, dq2, "q2", lay["wq2"], D)
@@ -466,7 +500,7 @@ class D3PMTrainer:
         return (os.environ.get("GSDD_TRAIN_GRAPH", "1") != "0" and not self._graph_failed and x0.is_cuda
                 and not self.reducer.active() and world_size() == 1 and x0.shape[1] % 32 == 0)
 
-    def _capture(self, x0, cond, null_cond=None, drop=None):
+    def _capture(self, x0, cond, null_cond=None, drop=None, cond_len=None):
         """Everything of a step that runs on the device -- re-pack of the weight images and AdaLN tables, q_sample, forward, loss +
         gradient, backward, Adam -- recorded once into a hipGraph and replayed: ~1000 small dependent launches leave ~2 ms of gaps per
         step when they are enqueued one by one.  Nothing step-dependent is baked in: x_0, condition, t, p(t) live in static buffers,
@@ -476,7 +510,9 @@ class D3PMTrainer:
         the graph is a libgsdd kernel or a fill / copy).
         Condition dropout: the f32 copy of the learned null embedding, the dropout kernel (its draw reads the stream id's device word),
         the null gradient and the copy of the updated rows back into the fp64 parameter are nodes too; an explicit mask and a caller's
-        null condition live in static buffers like x_0."""
+        null condition live in static buffers like x_0.
+        Condition lengths live in a static int32 (B,) buffer that every replay refreshes; the dropped samples' length Te is formed
+        from the dropout decisions inside the graph."""
         dm, dev = self.dm, x0.device
         B = x0.shape[0]
         st = {"shape": (tuple(x0.shape), tuple(cond.shape)), "lr": self.lr,
@@ -485,14 +521,15 @@ class D3PMTrainer:
               "sid": torch.tensor([dm.noise_stream], dtype=torch.int64, device=dev),
               "adam_step": torch.tensor([self._adam.step_count + 1], dtype=torch.int64, device=dev),
               "drop": None if drop is None else drop.to(dev).to(torch.uint8).contiguous().clone(),
-              "null": None if null_cond is None else null_cond.to(dev).float().contiguous().clone()}
+              "null": None if null_cond is None else null_cond.to(dev).float().contiguous().clone(),
+              "len": None if cond_len is None else cond_len.to(dev).to(torch.int32).contiguous().clone()}
         tr = dm.transformer
         keep = (dm.noise_stream, self._adam.step_count)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             tr._packed = None                                    # the re-pack is part of the graph: every replay sees the current weights
             loss, grads = self.loss_and_grads(st["x0"], st["cond"], st["t"], st["pt"], reduce=False, sid=st["sid"], null_cond=st["null"],
-                                              drop=st["drop"])
+                                              drop=st["drop"], cond_len=st["len"])
             self._adam.lr = self.lr
             self._adam.step(grads, step_dev=st["adam_step"])
             self._write_back_null(grads, cond.shape[1])
@@ -502,14 +539,16 @@ class D3PMTrainer:
         return st
 
     @torch.no_grad()
-    def step(self, x0, cond, t=None, pt=None, null_cond=None, drop=None):
-        """One optimiser step.  null_cond / drop: the null condition and the explicit drop mask of condition dropout (loss_and_grads).
+    def step(self, x0, cond, t=None, pt=None, null_cond=None, drop=None, cond_len=None):
+        """One optimiser step.  null_cond / drop: the null condition and the explicit drop mask of condition dropout (loss_and_grads);
+        cond_len: the per-sample condition lengths (loss_and_grads).
         With dm.learnable_cf the learned null embedding is updated with the transformer's parameters: its f32 copy and its gradient go
         through the same Adam launch, and rows [:Te] of the updated copy are written back into the fp64 parameter."""
         self._sync_start()
+        cond_len = self._check_lengths(cond, cond_len)
         if self._graph_usable(x0, cond):
-            return self._step_graphed(x0, cond, t, pt, null_cond, drop)
-        return self._step_eager(x0, cond, t, pt, null_cond, drop)
+            return self._step_graphed(x0, cond, t, pt, null_cond, drop, cond_len)
+        return self._step_eager(x0, cond, t, pt, null_cond, drop, cond_len)
 
     def _write_back_null(self, grads, Te):
         """After Adam: rows [:Te] of the updated f32 copy go back into dm.empty_text_embed (f32 -> fp64, one copy node).  The rows
@@ -517,7 +556,7 @@ class D3PMTrainer:
         if self.NULL_NAME in grads:
             self.dm.empty_text_embed.data[:Te].copy_(self._null32[:Te])
 
-    def _step_graphed(self, x0, cond, t, pt, null_cond=None, drop=None):
+    def _step_graphed(self, x0, cond, t, pt, null_cond=None, drop=None, cond_len=None):
         """Two eager steps first (arenas, images and tables reach their final addresses), then capture, then replays."""
         # one captured graph per (batch shape, learning rate), the two most recent kept: an epoch's short last batch must not make
         # every epoch capture twice (each graph owns its activations' pool: ~7 GB at bs 16, L = 4096)
@@ -525,16 +564,16 @@ class D3PMTrainer:
         # ... and per condition-dropout setting: the probability is a launch constant of the dropout kernel, and the learned null
         # embedding, a mask and a caller's null condition each change the graph's nodes
         key = (tuple(x0.shape), tuple(cond.shape), float(self.lr), float(getattr(self.dm, "cond_drop_prob", 0.0) or 0.0),
-               bool(self.dm.learnable_cf), drop is not None, null_cond is not None, self.deterministic)
+               bool(self.dm.learnable_cf), drop is not None, null_cond is not None, self.deterministic, cond_len is not None)
         st = self._graph = graphs.get(key)
         if st is None and self._eager_steps < 2:
             self._eager_steps += 1
-            return self._step_eager(x0, cond, t, pt, null_cond, drop)
+            return self._step_eager(x0, cond, t, pt, null_cond, drop, cond_len)
         dm = self.dm
         if st is None:
             keep = (dm.noise_stream, self._adam.step_count)
             try:
-                st = self._graph = self._capture(x0, cond, null_cond, drop)
+                st = self._graph = self._capture(x0, cond, null_cond, drop, cond_len)
                 while len(graphs) >= 2:
                     graphs.pop(next(iter(graphs)))
                 graphs[key] = st
@@ -544,7 +583,7 @@ class D3PMTrainer:
                 self._graph_failed = True
                 dm.transformer._packed = None
                 torch.cuda.synchronize()
-                return self._step_eager(x0, cond, t, pt, null_cond, drop)
+                return self._step_eager(x0, cond, t, pt, null_cond, drop, cond_len)
         if t is None:
             # the reference's own timestep sampler (importance sampling once every Lt_count exceeds 10: its check reads device memory,
             # i.e. waits for the previous step -- one host round trip per step, ~0.1 ms beside a 54 ms replay)
@@ -557,6 +596,8 @@ class D3PMTrainer:
             st["drop"].copy_(drop, non_blocking=True)
         if null_cond is not None:
             st["null"].copy_(null_cond.reshape(st["null"].shape), non_blocking=True)
+        if cond_len is not None:
+            st["len"].copy_(cond_len, non_blocking=True)
         # the two device words are set from the host's counts before every replay (two fills): whoever else draws from the noise stream
         # between steps -- the validation loop's _train_loss, set_noise, a resumed checkpoint -- moves dm.noise_stream, and the replay
         # must use the stream id the eager step would
@@ -570,8 +611,8 @@ class D3PMTrainer:
         self.last_fwd = None
         return st["loss"].clone()
 
-    def _step_eager(self, x0, cond, t=None, pt=None, null_cond=None, drop=None):
-        loss, grads = self.loss_and_grads(x0, cond, t, pt, reduce=True, null_cond=null_cond, drop=drop)
+    def _step_eager(self, x0, cond, t=None, pt=None, null_cond=None, drop=None, cond_len=None):
+        loss, grads = self.loss_and_grads(x0, cond, t, pt, reduce=True, null_cond=null_cond, drop=drop, cond_len=cond_len)
         tr = self.dm.transformer
         params = dict(tr.named_parameters())
         self.step_count += 1
@@ -614,8 +655,9 @@ class _TrainForward(torch.autograd.Function):
     incoming d(loss)."""
 
     @staticmethod
-    def forward(ctx, trainer, x0, cond, want_probs, null_cond, drop, *params):
-        loss, grads = trainer.loss_and_grads(x0, cond, want_probs=want_probs, reduce=True, null_cond=null_cond, drop=drop)    # DDP semantics: .grad = group mean
+    def forward(ctx, trainer, x0, cond, want_probs, null_cond, drop, cond_len, *params):
+        loss, grads = trainer.loss_and_grads(x0, cond, want_probs=want_probs, reduce=True, null_cond=null_cond, drop=drop,
+                                             cond_len=cond_len)    # DDP semantics: .grad = group mean
         names = [n for n, _ in trainer.dm.transformer.named_parameters()]
         ctx.grads = [grads[n].clone() for n in names]          # the arena is re-used by the next forward
         if len(params) > len(names):                           # dm.empty_text_embed, the last input: its gradient widened to the parameter's fp64
@@ -626,13 +668,14 @@ class _TrainForward(torch.autograd.Function):
     def backward(ctx, g_loss):
         out = tuple(g * g_loss for g in ctx.grads)
         ctx.grads = None
-        return (None, None, None, None, None, None) + out
+        return (None, None, None, None, None, None, None) + out
 
 
-def train_forward(dm, x0, cond, want_probs=False, null_cond=None, drop=None):
+def train_forward(dm, x0, cond, want_probs=False, null_cond=None, drop=None, cond_len=None):
     """DiffusionTransformer.forward in train mode with autograd enabled -> (loss with grad_fn, forward dict).  With condition dropout
     and dm.learnable_cf, dm.empty_text_embed is an input of the autograd node too: backward leaves its (77, 512) fp64 gradient in .grad,
-    and the caller's optimiser over generator.parameters() updates it like any other parameter."""
+    and the caller's optimiser over generator.parameters() updates it like any other parameter.  cond_len: the per-sample condition
+    lengths (D3PMTrainer.loss_and_grads)."""
     tr = getattr(dm, "_hip_trainer", None)
     if tr is None:
         tr = D3PMTrainer(dm)
@@ -640,5 +683,5 @@ def train_forward(dm, x0, cond, want_probs=False, null_cond=None, drop=None):
     params = [p for _, p in dm.transformer.named_parameters()]
     if dm.learnable_cf and tr._dropout_plan(cond, null_cond, drop) is not None:
         params.append(dm.empty_text_embed)
-    loss = _TrainForward.apply(tr, x0, cond, want_probs, null_cond, drop, *params)
+    loss = _TrainForward.apply(tr, x0, cond, want_probs, null_cond, drop, cond_len, *params)
     return loss, tr.last_fwd

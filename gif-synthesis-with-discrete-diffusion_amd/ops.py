@@ -341,14 +341,38 @@ def d3pm_logits(x, g, b, w, bias, out, stream=None):
     return out
 
 
-def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None):
-    check(lib().gsdd_d3pm_cross_attention(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), stream_ptr(stream)))
+def _cond_len_args(cond_len, cond_len_host, B, what):
+    """(device pointer, host pointer or NULL) of a condition-length pair: int32 (B,) on the device, its optional host copy int32 (B,)."""
+    if not torch.is_tensor(cond_len) or cond_len.dtype != torch.int32 or tuple(cond_len.shape) != (B,) or not cond_len.is_contiguous():
+        raise GsddError(f"{what}: cond_len must be a contiguous int32 tensor of shape ({B},)")
+    if cond_len_host is None:
+        return ptr(cond_len), None
+    h = cond_len_host
+    if not torch.is_tensor(h) or h.is_cuda or h.dtype != torch.int32 or tuple(h.shape) != (B,) or not h.is_contiguous():
+        raise GsddError(f"{what}: cond_len_host must be a contiguous int32 CPU tensor of shape ({B},)")
+    return ptr(cond_len), C.c_void_p(h.data_ptr())
+
+
+def d3pm_cross_attention(q, kc, vc, B, L, Te, H, out, stream=None, cond_len=None, cond_len_host=None):
+    """cond_len: None, or int32 (B,) on the device -- batch element b attends to its first cond_len[b] keys only
+    (gsdd_d3pm_cross_attention_len); cond_len_host: its host copy, range-checked before the launch."""
+    if cond_len is None:
+        check(lib().gsdd_d3pm_cross_attention(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), stream_ptr(stream)))
+    else:
+        ln, lh = _cond_len_args(cond_len, cond_len_host, B, "d3pm_cross_attention")
+        check(lib().gsdd_d3pm_cross_attention_len(ptr(q), ptr(kc), ptr(vc), ln, lh, B, L, Te, H, ptr(out), stream_ptr(stream)))
     return out
 
 
-def d3pm_cross_attention_train(q, kc, vc, B, L, Te, H, out, lse, stream=None):
-    """Training forward of the general cross-attention: out rows [M][4 H] and lse [H][M] (log2 domain)."""
-    check(lib().gsdd_d3pm_cross_attention_train(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), ptr(lse), stream_ptr(stream)))
+def d3pm_cross_attention_train(q, kc, vc, B, L, Te, H, out, lse, stream=None, cond_len=None, cond_len_host=None):
+    """Training forward of the general cross-attention: out rows [M][4 H] and lse [H][M] (log2 domain).  cond_len / cond_len_host as
+    d3pm_cross_attention."""
+    if cond_len is None:
+        check(lib().gsdd_d3pm_cross_attention_train(ptr(q), ptr(kc), ptr(vc), B, L, Te, H, ptr(out), ptr(lse), stream_ptr(stream)))
+    else:
+        ln, lh = _cond_len_args(cond_len, cond_len_host, B, "d3pm_cross_attention_train")
+        check(lib().gsdd_d3pm_cross_attention_train_len(ptr(q), ptr(kc), ptr(vc), ln, lh, B, L, Te, H, ptr(out), ptr(lse),
+                                                        stream_ptr(stream)))
     return out
 
 
@@ -357,14 +381,22 @@ def d3pm_cross_attention_bwd_workspace(B, L, Te, H, device):
     return torch.empty(((n + 3) // 4,), dtype=torch.float32, device=device)
 
 
-def d3pm_cross_attention_bwd(q, kc, vc, o, dO, lse, B, L, Te, H, ws, dq=None, dkc=None, dvc=None, stream=None):
-    """-> (dq head-major [H][M][4], dkc, dvc rows [B Te][4 H]), all overwritten; ws from d3pm_cross_attention_bwd_workspace."""
+def d3pm_cross_attention_bwd(q, kc, vc, o, dO, lse, B, L, Te, H, ws, dq=None, dkc=None, dvc=None, stream=None, cond_len=None,
+                             cond_len_host=None):
+    """-> (dq head-major [H][M][4], dkc, dvc rows [B Te][4 H]), all overwritten; ws from d3pm_cross_attention_bwd_workspace.
+    cond_len / cond_len_host as d3pm_cross_attention: the dkc / dvc rows at and behind a batch element's length are exact zeros."""
     f = dict(dtype=torch.float32, device=q.device)
     dq = torch.empty((H, B * L, 4), **f) if dq is None else dq
     dkc = torch.empty((B * Te, 4 * H), **f) if dkc is None else dkc
     dvc = torch.empty((B * Te, 4 * H), **f) if dvc is None else dvc
-    check(lib().gsdd_d3pm_cross_attention_bwd(ptr(q), ptr(kc), ptr(vc), ptr(o), ptr(dO), ptr(lse), B, L, Te, H, ptr(dq), ptr(dkc), ptr(dvc),
-                                              ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream_ptr(stream)))
+    nws = 0 if ws is None else ws.numel() * ws.element_size()
+    if cond_len is None:
+        check(lib().gsdd_d3pm_cross_attention_bwd(ptr(q), ptr(kc), ptr(vc), ptr(o), ptr(dO), ptr(lse), B, L, Te, H, ptr(dq), ptr(dkc),
+                                                  ptr(dvc), ptr(ws), nws, stream_ptr(stream)))
+    else:
+        ln, lh = _cond_len_args(cond_len, cond_len_host, B, "d3pm_cross_attention_bwd")
+        check(lib().gsdd_d3pm_cross_attention_bwd_len(ptr(q), ptr(kc), ptr(vc), ptr(o), ptr(dO), ptr(lse), ln, lh, B, L, Te, H, ptr(dq),
+                                                      ptr(dkc), ptr(dvc), ptr(ws), nws, stream_ptr(stream)))
     return dq, dkc, dvc
 
 

@@ -324,6 +324,26 @@ int gsdd_d3pm_cross_attention_bwd(const float* q, const float* kc, const float* 
                                   const float* lse, int B, int L, int Te, int H, float* dq, float* dkc, float* dvc,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The three cross-attentions with a condition length per batch element (caption padding): batch element b attends to its keys
+ * 0 .. cond_len[b] - 1 only.  The softmax runs over those keys; kc / vc rows at e >= cond_len[b] are NOT READ (they may hold anything,
+ * NaN included), and the backward writes the dkc / dvc rows at e >= cond_len[b] as exact zeros (it still overwrites every row: no
+ * atomics, fixed summation order, a batch element's results independent of the others in the launch).  The kernels are the ones of
+ * the entry points above, which are their "every length is Te" case: cond_len[b] == Te for every b gives the same bits.
+ * `cond_len` is a device int32 [B].  `cond_len_host` is, like eot_host of gsdd_text_pool, an optional HOST copy of the same integers:
+ * when given, every entry is checked before the launch and a value outside [1, Te] is GSDD_E_ARG (gsdd_last_error names the index and
+ * the value); when NULL (a captured step has no host copy) the kernels clamp the device value into [1, Te], so they never read outside
+ * the rows and never divide by an empty sum.  1 <= Te <= 77; the workspace is the one gsdd_d3pm_cross_attention_bwd_workspace_bytes
+ * sizes.  Training: the weight gradients of the key / value projections multiply the zero dkc / dvc rows by the condition rows, so the
+ * condition rows behind a length must be FINITE there (0 x NaN is not 0). */
+int gsdd_d3pm_cross_attention_len(const float* q, const float* kc, const float* vc, const int32_t* cond_len,
+                                  const int32_t* cond_len_host, int B, int L, int Te, int H, float* out, void* stream);
+int gsdd_d3pm_cross_attention_train_len(const float* q, const float* kc, const float* vc, const int32_t* cond_len,
+                                        const int32_t* cond_len_host, int B, int L, int Te, int H, float* out, float* lse,
+                                        void* stream);
+int gsdd_d3pm_cross_attention_bwd_len(const float* q, const float* kc, const float* vc, const float* o, const float* dO,
+                                      const float* lse, const int32_t* cond_len, const int32_t* cond_len_host, int B, int L, int Te,
+                                      int H, float* dq, float* dkc, float* dvc, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* One fused reverse-diffusion step on int64 tokens:
  *   predict_start (fp log_softmax, clamp) x2 -> cf guidance mix -> q_posterior -> Gumbel arg-max.
  * Replaces diffusion_transformer.py:220-249 (predict_start/cf_predict_start tails), :251-283

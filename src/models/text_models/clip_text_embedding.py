@@ -83,7 +83,18 @@ class CLIPTextEmbedding(nn.Module):
         return self._tower
 
     @torch.no_grad()
-    def forward(self, texts, force_mask=False, native=None):
+    def forward(self, texts, force_mask=False, native=None, return_lengths=False):
+        """return_lengths=True -> (features, lengths): int32 (B,) on the host, a caption's end-of-text position + 1 with per_token (the
+        positions that are its own tokens; taken from the ids tokenized here, no device synchronisation), all ones without."""
+        out = self._embed(texts, native)
+        if not return_lengths:
+            return out
+        if not self.per_token:
+            return out, torch.ones((len(texts),), dtype=torch.int32)
+        ids = self.tokenize(texts)
+        return out, ((ids == self.tokenizer.eos_token_id).int().argmax(dim=1) + 1).to(torch.int32)
+
+    def _embed(self, texts, native=None):
         dev = self._anchor.device
         native = self.native if native is None else native
         if self.clip_model is None:
@@ -104,7 +115,8 @@ class CLIPTextEmbedding(nn.Module):
             if self.per_token:
                 # the token features of the recipe's fixed context (start + 20 + end = 22 positions, untrimmed: Te is one constant and
                 # the captured training step is not re-captured per batch); positions behind a caption's end-of-text are kept, as upstream
-                # VQ-Diffusion keeps them (its CrossAttention has no key mask)
+                # VQ-Diffusion keeps them -- forward(return_lengths=True) tells the caller where they start, and the denoiser's
+                # cross-attention skips them when given those lengths
                 ctx = self.MAX_TEXT_LEN + 2
                 return self._native_tower(dev)(ids[:, :ctx].contiguous(), eot=eot, trim=False, tokens=True)
             return self._native_tower(dev)(ids, eot=eot)

@@ -115,6 +115,46 @@ int main() {
         EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, nullptr, dvc, ws, need, st), GSDD_E_ARG, false);
         EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, L, Te, H, dq, dkc, nullptr, ws, need, st), GSDD_E_ARG, false);
         EXPECT(gsdd_d3pm_cross_attention_bwd(q, kc, vc, out, dO, lse, B, 0, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+        // the same three with a condition length per batch element: a device array plus an optional host copy that is range-checked
+        {
+            const int32_t* len = devp<int32_t>();
+            std::vector<int32_t> len_h(B);
+            for (int b = 0; b < B; ++b) len_h[b] = 1 + (b * 5) % Te;
+            len_h[1] = Te;
+            EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, len, len_h.data(), B, L, Te, H, out, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, len, nullptr, B, L, Te, H, out, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, len, len_h.data(), B, L, Te, H, out, lse, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, len, nullptr, B, L, Te, H, out, lse, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, len_h.data(), B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, nullptr, B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, len_h.data(), B, L, Te, H, dq, dkc, dvc, ws, need - 1, st), GSDD_E_ARG, false);
+            // null pointers (the host copy alone may be null)
+            EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, nullptr, len_h.data(), B, L, Te, H, out, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, len, len_h.data(), B, L, Te, H, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_len(q, nullptr, vc, len, len_h.data(), B, L, Te, H, out, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, nullptr, nullptr, B, L, Te, H, out, lse, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, len, nullptr, B, L, Te, H, out, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, nullptr, nullptr, B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, nullptr, B, L, Te, H, dq, dkc, dvc, nullptr, need, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, nullptr, B, L, Te, H, dq, nullptr, dvc, ws, need, st), GSDD_E_ARG, false);
+            // Te out of range
+            EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, len, nullptr, B, L, 0, H, out, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, len, nullptr, B, L, 78, H, out, lse, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, nullptr, B, L, 78, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+            // host lengths 0 and Te + 1: refused before the launch, the message names index and value
+            for (int32_t bad : {(int32_t)0, (int32_t)(Te + 1)}) {
+                len_h[B - 1] = bad;
+                EXPECT(gsdd_d3pm_cross_attention_len(q, kc, vc, len, len_h.data(), B, L, Te, H, out, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_d3pm_cross_attention_train_len(q, kc, vc, len, len_h.data(), B, L, Te, H, out, lse, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_d3pm_cross_attention_bwd_len(q, kc, vc, out, dO, lse, len, len_h.data(), B, L, Te, H, dq, dkc, dvc, ws, need, st), GSDD_E_ARG, false);
+                char want[64];
+                std::snprintf(want, sizeof want, "cond_len[%d] = %d", B - 1, (int)bad);
+                if (std::strstr(gsdd_last_error(), want) == nullptr) {
+                    std::fprintf(stderr, "FAIL the message does not name index and value: %s\n", gsdd_last_error());
+                    ++g_failed;
+                }
+            }
+        }
         // LayerNorm rows of any width (the text tower's per-token features)
         EXPECT(gsdd_ln_apply(q, kc, vc, dO, 16 * 22, 512, out, st), GSDD_OK, true);
         EXPECT(gsdd_ln_apply(q, kc, vc, dO, 16 * 22, 510, out, st), GSDD_E_ARG, false);
