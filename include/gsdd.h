@@ -523,7 +523,17 @@ int gsdd_ln_bwd(const float* dh, const float* x, const float* stats, const float
  * bits of a gradient depend on the order the hardware retires them in.  on != 0: every output address receives the sum of ONE
  * workgroup (or thread) formed in a fixed order -- the same inputs give the same bits -- at the cost of the parallelism over the rows
  * (gsdd_d3pm_embed_bwd walks all rows per table row: for tests and reproducibility runs, not the production shape).  Returns the
- * previous setting.  Read by the host code at launch time: a captured graph keeps the form it was captured with. */
+ * previous setting.  Read by the host code at launch time: a captured graph keeps the form it was captured with.
+ * The six entries and their reproducible forms:
+ *   gsdd_wgrad           one workgroup per 64 x 64 output tile walks all ceil(M / 128) row slabs
+ *   gsdd_colsum          one block per column group takes all M rows
+ *   gsdd_batch_rowsum    one such block per batch element (B launches), each on its own slice of out
+ *   gsdd_ln_bwd          one block for the whole call, or with acc_by_batch one single-block launch per batch element
+ *   gsdd_d3pm_embed_bwd  a kernel of its own: one thread per (table row or position, column) walks all rows in ascending order
+ *   gsdd_adaln_bwd       the first batch element of a timestep adds the shares of all batch elements with that timestep (demb)
+ * Two calls silently keep the atomic form with the switch on: gsdd_wgrad, gsdd_colsum and gsdd_ln_bwd with M >= 2^30 rows, and
+ * gsdd_ln_bwd with acc_by_batch and M % rows_per_batch != 0 (no whole number of per-batch launches).  The training step reaches
+ * neither.  Each form is held to the fast form's fp64 bars and to equal bits from two calls in tests/test_gpu_train_reproducible.py. */
 int gsdd_set_deterministic(int on);
 /* dW[N][K] += dY^T X (contraction over the M rows), db[N] += column sums of dY (optional) */
 int gsdd_wgrad(const float* dY, int ldy, const float* X, int ldx, int64_t M, int N, int K, float* dW, float* db, void* stream);

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.conftest import parity_report
+from tests.test_gpu_train_kernels import assert_forms, form_key, form_record, run_forms
 
 pytestmark = pytest.mark.gpu
 
@@ -746,62 +747,134 @@ def wgrad_slabs(M, N, K):
     return slabs
 
 
-@pytest.mark.parametrize("M,N,K,with_db,slabs", [(BIG_M, 68, 68, True, 8), (70001, 200, 12, True, 4), (40000, 12, 200, False, 2),
-                                                  (200, 68, 68, False, 1), (200, 12, 200, True, 1)])
-def test_wgrad(G, M, N, K, with_db, slabs):
-    """dW[N][K] += dY^T X and db[N] += colsum(dY) (both prefilled) at row counts that take 8, 4, 2 and 1 slabs per block."""
-    assert wgrad_slabs(M, N, K) == slabs
+# The case bodies below take form = "fast" (this file's tests: the switch is off) or "reproducible" (gsdd_set_deterministic, held on
+# by the fixture of tests/test_gpu_train_reproducible.py, which also hands in `fast_form`); reference and bounds are the same for both.
+def guarded_out(fill):
+    """-> (buffer, view): a copy of `fill` on the device with 64 sentinel floats on either side"""
+    n = fill.numel()
+    buf = torch.full((64 + n + 64,), SENTINEL, device="cuda")
+    v = buf[64:64 + n].view(fill.shape)
+    v.copy_(fill)
+    return buf, v
+
+
+def out_guards_intact(*bufs):
+    return all(bool((b[:64] == SENTINEL).all()) and bool((b[-64:] == SENTINEL).all()) for b in bufs)
+
+
+def wgrad_ref(dY, X, dW0, db0):
+    """fp64 (want, bound) of dW0 + dY^T X and of db0 + colsum(dY)"""
+    M = dY.shape[0]
+    want = dW0.double() + dY.double().t() @ X.double()
+    bound = gam(M) * (dW0.double().abs() + dY.double().abs().t() @ X.double().abs())
+    return want, bound, db0.double() + dY.double().sum(0), gam(M) * (db0.double().abs() + dY.double().abs().sum(0))
+
+
+def wgrad_case(G, name, dY, X, dW0, db0, with_db, form="fast", fast_form=None, **extra):
+    M, N, K = dY.shape[0], dY.shape[1], X.shape[1]
+    want, bound, want_db, bound_db = wgrad_ref(dY, X, dW0, db0)
+
+    def run():
+        wbuf, dW = guarded_out(dW0)
+        bbuf, db = guarded_out(db0)
+        G.ops.wgrad(dY, X, dW, db if with_db else None)
+        return {"dW": dW, "db": db, "wbuf": wbuf, "bbuf": bbuf}
+    out, again, fast = run_forms(run, form, fast_form)
+    bars = {"dW": bound, "db": bound_db} if with_db else {"dW": bound}
+    rec = form_record(out, again, fast, bars, -(-M // (128 * wgrad_slabs(M, N, K))) > 1)
+    assert out_guards_intact(out["wbuf"], out["bbuf"]), "wgrad wrote outside dW / db"
+    check_dense(f"{name}{form_key(form)}", out["dW"], want, bound, **extra, **rec)
+    if with_db:
+        db_name = name.replace("wgrad[", "wgrad_db[") if "[" in name else name + "_db"
+        check_dense(f"{db_name}{form_key(form)}", out["db"], want_db, bound_db)
+    else:
+        assert torch.equal(out["db"], db0)
+    assert_forms(rec)
+
+
+def wgrad_inputs(M, N, K):
     torch.manual_seed(M + N)
     dY = torch.randn(M, N, device="cuda")
     X = torch.randn(M, K, device="cuda")
     dW0 = torch.randn(N, K, device="cuda")
     db0 = torch.randn(N, device="cuda")
-    dW, db = dW0.clone(), db0.clone()
-    G.ops.wgrad(dY, X, dW, db if with_db else None)
-    want = dW0.double() + dY.double().t() @ X.double()
-    bound = gam(M) * (dW0.double().abs() + dY.double().abs().t() @ X.double().abs())
-    check_dense(f"wgrad[M{M}-N{N}-K{K}]", dW, want, bound, slabs=slabs)
-    if with_db:
-        check_dense(f"wgrad_db[M{M}-N{N}-K{K}]", db, db0.double() + dY.double().sum(0),
-                    gam(M) * (db0.double().abs() + dY.double().abs().sum(0)))
-    else:
-        assert torch.equal(db, db0)
+    return dY, X, dW0, db0
 
 
-def test_wgrad_cancellation(G):
-    """dY with zero column mean, X with a large positive mean: the bound against |dY|^T |X|."""
+@pytest.mark.parametrize("M,N,K,with_db,slabs", [(BIG_M, 68, 68, True, 8), (70001, 200, 12, True, 4), (40000, 12, 200, False, 2),
+                                                  (200, 68, 68, False, 1), (200, 12, 200, True, 1)])
+def test_wgrad(G, M, N, K, with_db, slabs):
+    """dW[N][K] += dY^T X and db[N] += colsum(dY) (both prefilled) at row counts that take 8, 4, 2 and 1 slabs per block."""
+    assert wgrad_slabs(M, N, K) == slabs
+    wgrad_case(G, f"wgrad[M{M}-N{N}-K{K}]", *wgrad_inputs(M, N, K), with_db, form="fast", slabs=slabs)
+
+
+def wgrad_cancellation_inputs():
     torch.manual_seed(79)
     M, N, K = 70001, 68, 200
     dY = torch.randn(M, N, device="cuda", dtype=torch.float64)
     dY = (dY - dY.mean(0, keepdim=True)).float()
     X = 40 + torch.randn(M, K, device="cuda")
-    dW0 = torch.zeros(N, K, device="cuda")
-    db0 = torch.zeros(N, device="cuda")
-    dW, db = dW0.clone(), db0.clone()
-    G.ops.wgrad(dY, X, dW, db)
-    check_dense("wgrad_cancellation", dW, dY.double().t() @ X.double(), gam(M) * (dY.double().abs().t() @ X.double().abs()))
-    check_dense("wgrad_cancellation_db", db, dY.double().sum(0), gam(M) * dY.double().abs().sum(0))
+    return dY, X, torch.zeros(N, K, device="cuda"), torch.zeros(N, device="cuda")
+
+
+def test_wgrad_cancellation(G):
+    """dY with zero column mean, X with a large positive mean: the bound against |dY|^T |X|."""
+    wgrad_case(G, "wgrad_cancellation", *wgrad_cancellation_inputs(), True, form="fast")
+
+
+def colsum_ref(Y, out0):
+    M = Y.shape[0]
+    return out0.double() + Y.double().sum(0), gam(M) * (out0.double().abs() + Y.double().abs().sum(0))
+
+
+def colsum_case(G, M, N, form="fast", fast_form=None):
+    torch.manual_seed(M + N)
+    Y = torch.randn(M, N, device="cuda")
+    out0 = torch.randn(N, device="cuda")
+    want, bound = colsum_ref(Y, out0)
+
+    def run():
+        buf, out = guarded_out(out0)
+        G.ops.colsum(Y, out)
+        return {"out": out, "buf": buf}
+    out, again, fast = run_forms(run, form, fast_form)
+    rec = form_record(out, again, fast, {"out": bound}, M > (64 if N <= 256 and M < 262144 else 256))
+    assert out_guards_intact(out["buf"]), "colsum wrote outside out"
+    check_dense(f"colsum[M{M}-N{N}]{form_key(form)}", out["out"], want, bound, **rec)
+    assert_forms(rec)
 
 
 @pytest.mark.parametrize("M,N", [(200, 1), (1000, 3), (5000, 68), (262143, 5), (262144, 4), (300000, 12), (3000, 300),
                                  (700, 257)])
 def test_colsum(G, M, N):
     """out[n] += sum_m Y[m][n] (prefilled) with 64 or 256 rows per block (M below / above 262144, N above 256)."""
-    torch.manual_seed(M + N)
-    Y = torch.randn(M, N, device="cuda")
-    out0 = torch.randn(N, device="cuda")
-    out = out0.clone()
-    G.ops.colsum(Y, out)
-    check_dense(f"colsum[M{M}-N{N}]", out, out0.double() + Y.double().sum(0), gam(M) * (out0.double().abs() + Y.double().abs().sum(0)))
+    colsum_case(G, M, N, form="fast")
+
+
+def batch_rowsum_ref(Y, B, L):
+    Yb = Y.double().view(B, L, -1)
+    return Yb.sum(1), gam(L) * Yb.abs().sum(1)
+
+
+def batch_rowsum_case(G, L, C, B=3, form="fast", fast_form=None):
+    torch.manual_seed(L + C)
+    Y = torch.randn(B * L, C, device="cuda")
+    want, bound = batch_rowsum_ref(Y, B, L)
+
+    def run():
+        buf, out = guarded_out(torch.full((B, C), SENTINEL))          # the call's own memset must clear it
+        G.ops.batch_rowsum(Y, B, L, out)
+        return {"out": out, "buf": buf}
+    out, again, fast = run_forms(run, form, fast_form)
+    rec = form_record(out, again, fast, {"out": bound}, L > 64)
+    assert out_guards_intact(out["buf"]), "batch_rowsum wrote outside out"
+    name = f"batch_rowsum[L{L}-C{C}]" if B == 3 else f"batch_rowsum[B{B}-L{L}-C{C}]"
+    check_dense(f"{name}{form_key(form)}", out["out"], want, bound, **rec)
+    assert_forms(rec)
 
 
 @pytest.mark.parametrize("L,C", [(77, 12), (200, 300), (1000, 1), (63, 68)])
 def test_batch_rowsum(G, L, C):
     """out[b][c] = sum_l Y[b L + l][c] over B = 3 batches, L not a multiple of 64."""
-    torch.manual_seed(L + C)
-    B = 3
-    Y = torch.randn(B * L, C, device="cuda")
-    out = torch.full((B, C), SENTINEL, device="cuda")
-    G.ops.batch_rowsum(Y, B, L, out)
-    Yb = Y.double().view(B, L, C)
-    check_dense(f"batch_rowsum[L{L}-C{C}]", out, Yb.sum(1), gam(L) * Yb.abs().sum(1))
+    batch_rowsum_case(G, L, C, form="fast")

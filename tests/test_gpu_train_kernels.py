@@ -51,12 +51,15 @@ and "adds twice" are errors of the size of the prefill or of the sum).
     m' carries 2 U (|b1 m| + |(1 - b1) g|), v' 3 U v'; a bias correction carries 4 U beta^step / (1 - beta^step) + U (pow in f32 or
     in double, then the subtraction).  The step dp = lr / bc1 m' / (sqrt(v' / bc2) + eps) then has
     bar (lr / bc1) e_m' / den + |dp| (e_bc1 + (e_v' / v' + e_bc2) / 2 + 8 U) and p' adds U |p'|.
-Every case records its worst error / bar ratio with tests.conftest.parity_report (train_kernels::*).
+Every case records its worst error / bar ratio with tests.conftest.parity_report (train_kernels::*).  The case bodies of ln_bwd, the
+embedding pair and adaln_bwd are plain functions with a `form` argument: the tests here run the fast form (float atomics), those of
+tests/test_gpu_train_reproducible.py the reproducible one (gsdd_set_deterministic) against the same reference, bars and guards.
 
 Memory the kernels must not write is filled with a sentinel and checked bit for bit: rows past M (ln_fwd stats and y, embedding
 rows), unused dtab slots and the gaps between accumulated outputs, demb / dW / db guard rows, the 4-float padding of Adam's m and v
 and the gaps between Adam's parameters."""
 import math
+import types
 
 import numpy as np
 import pytest
@@ -90,8 +93,8 @@ def G():
     return gsdd_amd
 
 
-def cgen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
+def cgen(seed, dev="cuda"):
+    return torch.Generator(device=dev).manual_seed(seed)
 
 
 def ratio(got, want, bar):
@@ -116,13 +119,53 @@ def guards_intact(buf, n_before, n, n_after):
     return bool((buf[:n_before] == SENT).all()) and bool((buf[n_before + n:] == SENT).all())
 
 
+# ----------------------------------------------------------------------------- the two forms of the gradient reductions
+# The case bodies of ln_bwd, embed_bwd and adaln_bwd below take form = "fast" (this file's tests: the switch is off) or "reproducible"
+# (tests/test_gpu_train_reproducible.py: its fixture holds ops.set_deterministic(True) for the test and hands in `fast_form`, a context
+# manager that turns the switch off for the one comparison run).  Reference, bars and guards are the same for both.
+def form_key(form):
+    return "" if form == "fast" else "[reproducible]"
+
+
+def run_forms(run, form, fast_form=None):
+    """run() -> dict of output tensors of one call from a fresh copy of the prefill.  -> (out, second run or None, fast-form run or
+    None): the reproducible form runs twice, and once more in the fast form for the agreement of the two"""
+    assert form in ("fast", "reproducible")
+    if form == "fast":
+        return run(), None, None
+    with fast_form():
+        fast = run()
+    return run(), run(), fast
+
+
+def same_bits(a, b):
+    """every output of two runs equal in bits (buffers with their guards included)"""
+    return all(bool(torch.equal(a[k].view(torch.int32), b[k].view(torch.int32))) for k in a)
+
+
+def form_record(out, again, fast, bars, fast_multi_wg):
+    """parity-report entries of a reproducible case: equal bits on the second run, the worst |reproducible - fast| / (bar + bar) over
+    the outputs named in `bars` (both forms are held to the same bar), and whether the fast form spreads one output address over more
+    than one workgroup (only then do equal bits say something the fast form would not)"""
+    if again is None:
+        return {}
+    agree = max(ratio(out[k], fast[k].double(), 2 * bars[k]) for k in bars)
+    return {"same_bits": same_bits(out, again), "forms_agree_ratio": agree, "fast_multi_workgroup": bool(fast_multi_wg)}
+
+
+def assert_forms(rec):
+    if rec:
+        assert rec["same_bits"], "the reproducible form gave other bits on its second run"
+        assert rec["forms_agree_ratio"] <= 1, f"fast and reproducible form differ by {rec['forms_agree_ratio']:.3g} of their two bars"
+
+
 # ----------------------------------------------------------------------------- LayerNorm forward
-def ln_rows(M, seed, wild=True):
+def ln_rows(M, seed, wild=True, dev="cuda"):
     """rows of 64 with spread ~1, and (wild) large means beside small spreads"""
-    g = cgen(seed)
-    x = torch.randn(M, D, generator=g, device="cuda")
+    g = cgen(seed, dev)
+    x = torch.randn(M, D, generator=g, device=dev)
     if wild:
-        r = torch.arange(M, device="cuda")
+        r = torch.arange(M, device=dev)
         mu = torch.where(r % 5 == 0, 1e3, torch.where(r % 5 == 1, -300.0, 0.0))
         sd = torch.where(r % 7 == 0, 1e-2, torch.where(r % 7 == 1, 30.0, 1.0))
         x = x * sd[:, None] + mu[:, None]
@@ -207,51 +250,49 @@ LN_BWD_CASES = [
 ]
 
 
-@pytest.mark.parametrize("name,M,rpb,by_batch,with_dx_in", LN_BWD_CASES, ids=[c[0] for c in LN_BWD_CASES])
-def test_ln_bwd_matches_fp64(G, name, M, rpb, by_batch, with_dx_in):
-    """dx, dgamma, dbeta of the LayerNorm backward.  AdaLN cases use the trainer's dtab layout exactly: one [B][2D] table, dgamma =
-    dtab, dbeta = dtab + D, gacc_stride = 2D (gamma and beta gradients interleaved row by row), plus two unused slots after it."""
+def ln_bwd_fast_rit(M, rpb, by_batch):
+    """16-row groups per block as gsdd_ln_bwd's fast form picks them"""
+    rit = 4
+    while rit > 1 and ((by_batch and rpb % (16 * rit) != 0) or M < 16 * rit * 512):
+        rit >>= 1
+    return rit
+
+
+def ln_bwd_setup(M, rpb, by_batch, with_dx_in, dev="cuda"):
+    """Inputs, prefill and the fp64 reference with its bars of one LayerNorm-backward case.  AdaLN cases use the trainer's dtab layout
+    exactly: one [B][2D] table, dgamma = dtab, dbeta = dtab + D, gacc_stride = 2D (gamma and beta gradients interleaved row by row),
+    plus two unused slots after it."""
     T = 100
-    g = cgen(M + rpb)
-    x = ln_rows(M, M + 3 * rpb)
+    g = cgen(M + rpb, dev)
+    x = ln_rows(M, M + 3 * rpb, dev=dev)
     xd = x.double()
     mu = xd.mean(1, keepdim=True)
     rs = ((xd - mu).square().mean(1, keepdim=True) + 1e-5).rsqrt()
     stats = torch.cat([mu, rs], 1).float().contiguous()
-    dh = torch.randn(M, D, generator=g, device="cuda")
+    dh = torch.randn(M, D, generator=g, device=dev)
     dh[::9] *= 1e3
-    dx_in = torch.randn(M, D, generator=g, device="cuda") if with_dx_in else None
+    dx_in = torch.randn(M, D, generator=g, device=dev) if with_dx_in else None
     if by_batch:
         B = M // rpb
         assert B * rpb == M
-        tab = torch.randn(T, 2 * D, generator=g, device="cuda") + 1
-        t = torch.randint(0, T, (B,), generator=g, device="cuda")
+        tab = torch.randn(T, 2 * D, generator=g, device=dev) + 1
+        t = torch.randint(0, T, (B,), generator=g, device=dev)
         t[0], t[-1] = 0, T - 1
         if B > 3:
             t[1] = t[2] = 0
         t = t.contiguous()
-        bidx = torch.arange(M, device="cuda") // rpb
+        bidx = torch.arange(M, device=dev) // rpb
         gam_rows = tab.double()[t[bidx], :D]
         gp, sel, gstride = tab.view(-1), t, 2 * D
-        nslot, nrows = B, torch.full((B,), rpb, device="cuda")
-        pre = torch.randn(B, 2 * D, generator=g, device="cuda")
-        buf, dtab = guarded(0, (B, 2 * D), 2 * 2 * D, pre)
-        dgamma, dbeta, acc_stride = dtab, dtab.view(-1)[D:], 2 * D
+        nslot, nrows = B, torch.full((B,), rpb, device=dev)
+        pre = torch.randn(B, 2 * D, generator=g, device=dev)
     else:
-        gamma = torch.randn(D, generator=g, device="cuda") + 1
+        gamma = torch.randn(D, generator=g, device=dev) + 1
         gam_rows = gamma.double().expand(M, D)
         gp, sel, gstride = gamma, None, 0
-        bidx = torch.zeros(M, dtype=torch.long, device="cuda")
-        nslot, nrows = 1, torch.full((1,), M, device="cuda")
-        pre = torch.randn(1, 2 * D, generator=g, device="cuda")
-        # dgamma and dbeta as the trainer hands them out (two arena views), with sentinel gaps around and between them
-        buf = torch.full((16 + D + 16 + D + 16,), SENT, device="cuda")
-        dgamma, dbeta = buf[16:16 + D], buf[32 + D:32 + 2 * D]
-        dgamma.copy_(pre[0, :D])
-        dbeta.copy_(pre[0, D:])
-        acc_stride = D
-    dx = G.ops.ln_bwd(dh, x, stats, gp, sel=sel, gstride=gstride, rows_per_batch=rpb, dx_in=dx_in, dgamma=dgamma, dbeta=dbeta,
-                      gacc_stride=acc_stride, acc_by_batch=by_batch)
+        bidx = torch.zeros(M, dtype=torch.long, device=dev)
+        nslot, nrows = 1, torch.full((1,), M, device=dev)
+        pre = torch.randn(1, 2 * D, generator=g, device=dev)
     # fp64 reference from the same f32 inputs
     sd = stats.double()
     xh = (xd - sd[:, :1]) * sd[:, 1:]
@@ -261,28 +302,68 @@ def test_ln_bwd_matches_fp64(G, name, M, rpb, by_batch, with_dx_in):
     want_dx = din + sd[:, 1:] * (gg - m1 - xh * m2)
     e1, e2 = gam(64) * gg.abs().mean(1, keepdim=True), (gam(64) + 3 * U) * (gg * xh).abs().mean(1, keepdim=True)
     bar_dx = sd[:, 1:] * (5 * U * (gg.abs() + m1.abs()) + 7 * U * (xh * m2).abs() + e1 + xh.abs() * e2) + U * (din.abs() + want_dx.abs())
-    r_dx = ratio(dx, want_dx, bar_dx)
-    z = torch.zeros(nslot, D, dtype=torch.float64, device="cuda")
-    sg = z.index_add(0, bidx, dh.double() * xh)
-    sb = z.index_add(0, bidx, dh.double())
-    ag = z.index_add(0, bidx, (dh.double() * xh).abs())
-    ab = z.index_add(0, bidx, dh.double().abs())
+    z = torch.zeros(nslot, D, dtype=torch.float64, device=dev)
+
+    def slot_sum(v):
+        # (one slot: the plain fp64 column sum -- index_add of 65,544 rows onto one row is 5 s of contended fp64 atomics per case)
+        return v.sum(0, keepdim=True) if nslot == 1 else z.index_add(0, bidx, v)
+    sg, sb = slot_sum(dh.double() * xh), slot_sum(dh.double())
+    ag, ab = slot_sum((dh.double() * xh).abs()), slot_sum(dh.double().abs())
     pd = pre.double()
-    if by_batch:
+    gk = gamt(nrows)[:, None]
+    want = {"dx": want_dx, "dgamma": pd[:, :D] + sg, "dbeta": pd[:, D:] + sb}
+    bars = {"dx": bar_dx, "dgamma": (gk + 3 * U) * ag + 2 * U * pd[:, :D].abs(), "dbeta": gk * ab + 2 * U * pd[:, D:].abs()}
+    return types.SimpleNamespace(M=M, rpb=rpb, by_batch=by_batch, nslot=nslot, x=x, stats=stats, dh=dh, dx_in=dx_in, gp=gp, sel=sel,
+                                 gstride=gstride, pre=pre, want=want, bars=bars)
+
+
+def ln_bwd_run(G, s):
+    """one call from a fresh copy of the prefill -> dx, the gradient slots [slots][64] (views of `buf`), the guarded buffer, guards"""
+    if s.by_batch:
+        buf, dtab = guarded(0, (s.nslot, 2 * D), 2 * 2 * D, s.pre)
+        dgamma, dbeta, acc_stride = dtab, dtab.view(-1)[D:], 2 * D
         got_g, got_b = dtab[:, :D], dtab[:, D:]
     else:
+        # dgamma and dbeta as the trainer hands them out (two arena views), with sentinel gaps around and between them
+        buf = torch.full((16 + D + 16 + D + 16,), SENT, device="cuda")
+        dgamma, dbeta = buf[16:16 + D], buf[32 + D:32 + 2 * D]
+        dgamma.copy_(s.pre[0, :D])
+        dbeta.copy_(s.pre[0, D:])
+        acc_stride = D
         got_g, got_b = dgamma[None], dbeta[None]
-    gk = gamt(nrows)[:, None]
-    r_g = ratio(got_g, pd[:, :D] + sg, (gk + 3 * U) * ag + 2 * U * pd[:, :D].abs())
-    r_b = ratio(got_b, pd[:, D:] + sb, gk * ab + 2 * U * pd[:, D:].abs())
-    if by_batch:
-        intact = guards_intact(buf, 0, nslot * 2 * D, 4 * D)
+    dx = G.ops.ln_bwd(s.dh, s.x, s.stats, s.gp, sel=s.sel, gstride=s.gstride, rows_per_batch=s.rpb, dx_in=s.dx_in, dgamma=dgamma,
+                      dbeta=dbeta, gacc_stride=acc_stride, acc_by_batch=s.by_batch)
+    if s.by_batch:
+        intact = guards_intact(buf, 0, s.nslot * 2 * D, 4 * D)
     else:
         intact = bool((buf[:16] == SENT).all()) and bool((buf[16 + D:32 + D] == SENT).all()) and bool((buf[32 + 2 * D:] == SENT).all())
-    parity_report(f"train_kernels::ln_bwd[{name}]", {"M": M, "rows_per_batch": rpb, "dx_ratio": r_dx, "dgamma_ratio": r_g,
-                                                    "dbeta_ratio": r_b, "worst_ratio": max(r_dx, r_g, r_b)})
-    assert intact, "ln_bwd wrote outside its gradient slots"
+    return {"dx": dx, "dgamma": got_g, "dbeta": got_b, "buf": buf, "intact": torch.tensor([int(intact)], dtype=torch.int32)}
+
+
+def ln_bwd_ratios(s, out):
+    return tuple(ratio(out[k], s.want[k], s.bars[k]) for k in ("dx", "dgamma", "dbeta"))
+
+
+def ln_bwd_case(G, name, M, rpb, by_batch, with_dx_in, form="fast", fast_form=None):
+    """dx, dgamma, dbeta of the LayerNorm backward in one of its two forms"""
+    s = ln_bwd_setup(M, rpb, by_batch, with_dx_in)
+    out, again, fast = run_forms(lambda: ln_bwd_run(G, s), form, fast_form)
+    r_dx, r_g, r_b = ln_bwd_ratios(s, out)
+    rit = ln_bwd_fast_rit(M, rpb, by_batch)
+    multi = (rpb % 16 != 0 or rpb > 16 * rit) if by_batch else M > 16 * rit
+    rec = form_record(out, again, fast, s.bars, multi)
+    parity_report(f"train_kernels::ln_bwd[{name}]{form_key(form)}", {"M": M, "rows_per_batch": rpb, "dx_ratio": r_dx, "dgamma_ratio": r_g,
+                                                                     "dbeta_ratio": r_b, "worst_ratio": max(r_dx, r_g, r_b), **rec})
+    assert bool(out["intact"]), "ln_bwd wrote outside its gradient slots"
     assert r_dx <= 1 and r_g <= 1 and r_b <= 1, (r_dx, r_g, r_b)
+    assert_forms(rec)
+
+
+@pytest.mark.parametrize("name,M,rpb,by_batch,with_dx_in", LN_BWD_CASES, ids=[c[0] for c in LN_BWD_CASES])
+def test_ln_bwd_matches_fp64(G, name, M, rpb, by_batch, with_dx_in):
+    """dx, dgamma, dbeta of the LayerNorm backward.  AdaLN cases use the trainer's dtab layout exactly: one [B][2D] table, dgamma =
+    dtab, dbeta = dtab + D, gacc_stride = 2D (gamma and beta gradients interleaved row by row), plus two unused slots after it."""
+    ln_bwd_case(G, name, M, rpb, by_batch, with_dx_in, form="fast")
 
 
 # ----------------------------------------------------------------------------- GELU2
@@ -327,53 +408,76 @@ def test_gelu2_forward_backward_match_fp64(G, n):
 
 
 # ----------------------------------------------------------------------------- token + position embedding
+NE = 4097
+
+
+def embed_setup(B, L, mask_frac, dev="cuda"):
+    """Tokens (out-of-range ones included), tables, dx, prefill and the fp64 reference with its bars of one embedding case"""
+    M = B * L
+    g = cgen(B * 7 + int(mask_frac * 10), dev)
+    tok = torch.randint(0, NE - 1, (M,), generator=g, device=dev)
+    tok[torch.rand(M, generator=g, device=dev) < mask_frac] = NE - 1
+    tok[5], tok[17], tok[M - 1], tok[M // 2] = -3, NE, NE + 900, -1
+    tok = tok.view(B, L).contiguous()
+    emb = torch.randn(NE, D, generator=g, device=dev)
+    pos = torch.randn(L, D, generator=g, device=dev)
+    tc = tok.view(-1).clamp(0, NE - 1)
+    dx = torch.randn(M, D, generator=g, device=dev)
+    dx[::13] *= 100
+    pre_e = torch.randn(NE, D, generator=g, device=dev)
+    pre_p = torch.randn(L, D, generator=g, device=dev)
+    dd = dx.double()
+    z = torch.zeros(NE, D, dtype=torch.float64, device=dev)
+    cnt = torch.bincount(tc, minlength=NE)
+    want = {"demb": pre_e.double() + z.index_add(0, tc, dd), "dpos": pre_p.double() + dd.view(B, L, D).sum(0)}
+    bars = {"demb": gamt(cnt)[:, None] * z.index_add(0, tc, dd.abs()) + 2 * U * pre_e.double().abs(),
+            "dpos": gam(B) * dd.abs().view(B, L, D).sum(0) + 2 * U * pre_p.double().abs()}
+    return types.SimpleNamespace(B=B, L=L, M=M, tok=tok, tc=tc, emb=emb, pos=pos, dx=dx, pre_e=pre_e, pre_p=pre_p, cnt=cnt, want=want,
+                                 bars=bars)
+
+
+def embed_bwd_run(G, s):
+    ebuf, demb = guarded(0, (NE, D), 4 * D, s.pre_e)
+    pbuf, dpos = guarded(0, (s.L, D), 4 * D, s.pre_p)
+    G.ops.d3pm_embed_bwd(s.dx, s.tok, demb, dpos)
+    return {"demb": demb, "dpos": dpos, "ebuf": ebuf, "pbuf": pbuf}
+
+
+def embed_case(G, B, L, mask_frac, form="fast", fast_form=None):
+    """x = emb[clamp(tok)] + pos[row % L]; backward demb[clamp(tok)] += dx, dpos[row % L] += dx, the backward in one of its two forms"""
+    s = embed_setup(B, L, mask_frac)
+    M = s.M
+    GUARD = 256
+    xbuf = torch.full(((M + GUARD) * D,), SENT, device="cuda")
+    O = G.ops
+    O.check(O.lib().gsdd_d3pm_embed(O.ptr(s.tok), B, L, D, O.ptr(s.emb), NE, O.ptr(s.pos), 1, O.ptr(xbuf), O.stream_ptr()))
+    x = xbuf[:M * D].view(M, D)
+    want_x = s.emb[s.tc] + s.pos.repeat(B, 1)                     # one f32 add: correctly rounded, so equal bit for bit
+    fwd_exact = bool(torch.equal(x, want_x))
+    fwd_guard = bool((xbuf[M * D:] == SENT).all())
+    out, again, fast = run_forms(lambda: embed_bwd_run(G, s), form, fast_form)
+    r_e, r_p = ratio(out["demb"], s.want["demb"], s.bars["demb"]), ratio(out["dpos"], s.want["dpos"], s.bars["dpos"])
+    untouched = bool(torch.equal(out["demb"][s.cnt == 0], s.pre_e[s.cnt == 0]))
+    guards = guards_intact(out["ebuf"], 0, NE * D, 4 * D) and guards_intact(out["pbuf"], 0, L * D, 4 * D)
+    # fast form: one atomic per row (per block for [MASK]) from blocks of 256 rows; with more than one block a position's B rows and the
+    # [MASK] row's many come from several workgroups
+    rec = form_record(out, again, fast, s.bars, M > 256)
+    parity_report(f"train_kernels::embed[B{B}_L{L}_mask{mask_frac}]{form_key(form)}",
+                  {"rows": M, "masked_rows": int(s.cnt[NE - 1]), "fwd_bit_exact": fwd_exact, "demb_ratio": r_e, "dpos_ratio": r_p,
+                   "worst_ratio": max(r_e, r_p), **rec})
+    assert fwd_exact and fwd_guard, "embedding forward"
+    assert untouched and guards, "embedding backward wrote rows of tokens that do not occur, or past its tables"
+    assert r_e <= 1 and r_p <= 1, (r_e, r_p)
+    assert_forms(rec)
+
+
 @pytest.mark.parametrize("B,L", [(16, 4096), (3, 100)])
 @pytest.mark.parametrize("mask_frac", [0.0, 0.5, 1.0])
 def test_embed_and_embed_bwd_match_fp64(G, B, L, mask_frac):
     """x = emb[clamp(tok)] + pos[row % L]; backward demb[clamp(tok)] += dx, dpos[row % L] += dx.  n_embed = 4097 (K = 4096 codes and
     [MASK] = 4096, the row the backward sums per block).  Tokens below 0 and at or above n_embed are clamped by the forward (to 0 and
     to [MASK]); the backward must send their gradient to the same rows."""
-    NE = 4097
-    M = B * L
-    g = cgen(B * 7 + int(mask_frac * 10))
-    tok = torch.randint(0, NE - 1, (M,), generator=g, device="cuda")
-    tok[torch.rand(M, generator=g, device="cuda") < mask_frac] = NE - 1
-    tok[5], tok[17], tok[M - 1], tok[M // 2] = -3, NE, NE + 900, -1
-    tok = tok.view(B, L).contiguous()
-    emb = torch.randn(NE, D, generator=g, device="cuda")
-    pos = torch.randn(L, D, generator=g, device="cuda")
-    GUARD = 256
-    xbuf = torch.full(((M + GUARD) * D,), SENT, device="cuda")
-    O = G.ops
-    O.check(O.lib().gsdd_d3pm_embed(O.ptr(tok), B, L, D, O.ptr(emb), NE, O.ptr(pos), 1, O.ptr(xbuf), O.stream_ptr()))
-    x = xbuf[:M * D].view(M, D)
-    tc = tok.view(-1).clamp(0, NE - 1)
-    want_x = emb[tc] + pos.repeat(B, 1)                          # one f32 add: correctly rounded, so equal bit for bit
-    fwd_exact = bool(torch.equal(x, want_x))
-    fwd_guard = bool((xbuf[M * D:] == SENT).all())
-    dx = torch.randn(M, D, generator=g, device="cuda")
-    dx[::13] *= 100
-    pre_e = torch.randn(NE, D, generator=g, device="cuda")
-    pre_p = torch.randn(L, D, generator=g, device="cuda")
-    ebuf, demb = guarded(0, (NE, D), 4 * D, pre_e)
-    pbuf, dpos = guarded(0, (L, D), 4 * D, pre_p)
-    O.d3pm_embed_bwd(dx, tok, demb, dpos)
-    dd = dx.double()
-    z = torch.zeros(NE, D, dtype=torch.float64, device="cuda")
-    cnt = torch.bincount(tc, minlength=NE)
-    want_e = pre_e.double() + z.index_add(0, tc, dd)
-    bar_e = gamt(cnt)[:, None] * z.index_add(0, tc, dd.abs()) + 2 * U * pre_e.double().abs()
-    want_p = pre_p.double() + dd.view(B, L, D).sum(0)
-    bar_p = gam(B) * dd.abs().view(B, L, D).sum(0) + 2 * U * pre_p.double().abs()
-    r_e, r_p = ratio(demb, want_e, bar_e), ratio(dpos, want_p, bar_p)
-    untouched = bool(torch.equal(demb[cnt == 0], pre_e[cnt == 0]))
-    guards = guards_intact(ebuf, 0, NE * D, 4 * D) and guards_intact(pbuf, 0, L * D, 4 * D)
-    parity_report(f"train_kernels::embed[B{B}_L{L}_mask{mask_frac}]",
-                  {"rows": M, "masked_rows": int(cnt[NE - 1]), "fwd_bit_exact": fwd_exact, "demb_ratio": r_e, "dpos_ratio": r_p,
-                   "worst_ratio": max(r_e, r_p)})
-    assert fwd_exact and fwd_guard, "embedding forward"
-    assert untouched and guards, "embedding backward wrote rows of tokens that do not occur, or past its tables"
-    assert r_e <= 1 and r_p <= 1, (r_e, r_p)
+    embed_case(G, B, L, mask_frac, form="fast")
 
 
 # ----------------------------------------------------------------------------- condition-token linears
@@ -436,29 +540,25 @@ def test_adaln_table_matches_fp64(G):
     assert r <= 1, r
 
 
-@pytest.mark.parametrize("B", [16, 96, 97, 128])
-def test_adaln_bwd_matches_fp64_autograd(G, B):
-    """B = 96 is the last batch whose 2 B D floats of SiLU / SiLU' fit the kernel's 48 KB of LDS; 97 the first that runs the
-    instantiation without LDS.  t holds repeated timesteps (several clips accumulating into one demb row), 0 and T - 1."""
+def adaln_bwd_setup(B, dev="cuda", one_timestep=False):
+    """Inputs, prefill and the fp64 autograd reference with its bars.  t holds repeated timesteps (several clips accumulating into one
+    demb row), 0 and T - 1; one_timestep: every clip holds timestep 7"""
     T = 100
-    g = cgen(40 + B)
-    emb = torch.randn(T, D, generator=g, device="cuda") * 2
-    w = torch.randn(2 * D, D, generator=g, device="cuda") / 8
-    t = torch.randint(0, T, (B,), generator=g, device="cuda")
+    g = cgen(40 + B, dev)
+    emb = torch.randn(T, D, generator=g, device=dev) * 2
+    w = torch.randn(2 * D, D, generator=g, device=dev) / 8
+    t = torch.randint(0, T, (B,), generator=g, device=dev)
     t[0], t[1], t[-1] = 0, T - 1, T - 1
     t[2:6] = 7
+    if one_timestep:
+        t[:] = 7
     t = t.contiguous()
-    dtab = torch.randn(B, 2 * D, generator=g, device="cuda")
-    dtab_in = dtab.clone()
-    pre_e, pre_w, pre_b = (torch.randn(*s, generator=g, device="cuda") for s in ((T, D), (2 * D, D), (2 * D,)))
-    ebuf, demb = guarded(64, (T, D), 4 * D, pre_e)
-    wbuf, dw = guarded(64, (2 * D, D), 64, pre_w)
-    bbuf, db = guarded(64, (2 * D,), 64, pre_b)
-    G.ops.adaln_bwd(dtab, t, emb, w, demb, dw, db)
+    dtab = torch.randn(B, 2 * D, generator=g, device=dev)
+    pre_e, pre_w, pre_b = (torch.randn(*s, generator=g, device=dev) for s in ((T, D), (2 * D, D), (2 * D,)))
     # fp64 autograd of table[t] = (1 + W silu(e_t) + b | W' silu(e_t) + b')
     ed = emb.double().requires_grad_(True)
     wd = w.double().requires_grad_(True)
-    bd = torch.zeros(2 * D, dtype=torch.float64, device="cuda", requires_grad=True)
+    bd = torch.zeros(2 * D, dtype=torch.float64, device=dev, requires_grad=True)
     tab = torch.nn.functional.silu(ed[t]) @ wd.t() + bd
     tab = torch.cat([1 + tab[:, :D], tab[:, D:]], 1)
     tab.backward(dtab.double())
@@ -468,18 +568,48 @@ def test_adaln_bwd_matches_fp64_autograd(G, B):
     inner = dtd @ w.double()
     inner_mag = dtd.abs() @ w.double().abs()
     per_b = gam(2 * D) * inner_mag * d1.abs() + inner.abs() * e_d1
-    z = torch.zeros(T, D, dtype=torch.float64, device="cuda")
-    bar_e = z.index_add(0, t, per_b) + gamt(cnt)[:, None] * z.index_add(0, t, (inner * d1).abs()) + 2 * U * pre_e.double().abs()
-    r_e = ratio(demb, pre_e.double() + ed.grad, bar_e)
-    r_w = ratio(dw, pre_w.double() + wd.grad, (gam(B) + ds_e.max()) * (dtd.abs().t() @ si.abs()) + 2 * U * pre_w.double().abs())
-    r_b = ratio(db, pre_b.double() + bd.grad, gam(B) * dtd.abs().sum(0) + 2 * U * pre_b.double().abs())
-    untouched = bool(torch.equal(demb[cnt == 0], pre_e[cnt == 0]))
-    guards = guards_intact(ebuf, 64, T * D, 4 * D) and guards_intact(wbuf, 64, 2 * D * D, 64) and guards_intact(bbuf, 64, 2 * D, 64)
-    parity_report(f"train_kernels::adaln_bwd[B{B}]", {"lds_instantiation": 2 * B * D * 4 <= 48 * 1024, "demb_ratio": r_e, "dw_ratio": r_w,
-                                                     "db_ratio": r_b, "worst_ratio": max(r_e, r_w, r_b)})
-    assert torch.equal(dtab, dtab_in), "adaln_bwd wrote its input"
+    z = torch.zeros(T, D, dtype=torch.float64, device=dev)
+    want = {"demb": pre_e.double() + ed.grad, "dw": pre_w.double() + wd.grad, "db": pre_b.double() + bd.grad}
+    bars = {"demb": z.index_add(0, t, per_b) + gamt(cnt)[:, None] * z.index_add(0, t, (inner * d1).abs()) + 2 * U * pre_e.double().abs(),
+            "dw": (gam(B) + ds_e.max()) * (dtd.abs().t() @ si.abs()) + 2 * U * pre_w.double().abs(),
+            "db": gam(B) * dtd.abs().sum(0) + 2 * U * pre_b.double().abs()}
+    return types.SimpleNamespace(B=B, T=T, emb=emb, w=w, t=t, dtab=dtab, pre_e=pre_e, pre_w=pre_w, pre_b=pre_b, cnt=cnt, want=want,
+                                 bars=bars)
+
+
+def adaln_bwd_run(G, s):
+    dtab = s.dtab.clone()
+    ebuf, demb = guarded(64, (s.T, D), 4 * D, s.pre_e)
+    wbuf, dw = guarded(64, (2 * D, D), 64, s.pre_w)
+    bbuf, db = guarded(64, (2 * D,), 64, s.pre_b)
+    G.ops.adaln_bwd(dtab, s.t, s.emb, s.w, demb, dw, db)
+    return {"demb": demb, "dw": dw, "db": db, "ebuf": ebuf, "wbuf": wbuf, "bbuf": bbuf, "dtab": dtab}
+
+
+def adaln_bwd_case(G, B, form="fast", fast_form=None, one_timestep=False):
+    s = adaln_bwd_setup(B, one_timestep=one_timestep)
+    out, again, fast = run_forms(lambda: adaln_bwd_run(G, s), form, fast_form)
+    r_e, r_w, r_b = (ratio(out[k], s.want[k], s.bars[k]) for k in ("demb", "dw", "db"))
+    untouched = bool(torch.equal(out["demb"][s.cnt == 0], s.pre_e[s.cnt == 0]))
+    guards = (guards_intact(out["ebuf"], 64, s.T * D, 4 * D) and guards_intact(out["wbuf"], 64, 2 * D * D, 64)
+              and guards_intact(out["bbuf"], 64, 2 * D, 64))
+    # fast form: the demb row of a repeated timestep gets one atomic per holder, from B D / 256 workgroups of 4 batch elements each
+    rec = form_record(out, again, fast, s.bars, True)
+    name = f"B{B}_one_timestep" if one_timestep else f"B{B}"
+    parity_report(f"train_kernels::adaln_bwd[{name}]{form_key(form)}",
+                  {"lds_instantiation": 2 * B * D * 4 <= 48 * 1024, "demb_ratio": r_e, "dw_ratio": r_w, "db_ratio": r_b,
+                   "worst_ratio": max(r_e, r_w, r_b), **rec})
+    assert torch.equal(out["dtab"], s.dtab), "adaln_bwd wrote its input"
     assert untouched and guards, "adaln_bwd wrote demb rows of timesteps that do not occur, or outside its outputs"
     assert r_e <= 1 and r_w <= 1 and r_b <= 1, (r_e, r_w, r_b)
+    assert_forms(rec)
+
+
+@pytest.mark.parametrize("B", [16, 96, 97, 128])
+def test_adaln_bwd_matches_fp64_autograd(G, B):
+    """B = 96 is the last batch whose 2 B D floats of SiLU / SiLU' fit the kernel's 48 KB of LDS; 97 the first that runs the
+    instantiation without LDS.  t holds repeated timesteps (several clips accumulating into one demb row), 0 and T - 1."""
+    adaln_bwd_case(G, B, form="fast")
 
 
 # ----------------------------------------------------------------------------- training attention at the C4 shape
