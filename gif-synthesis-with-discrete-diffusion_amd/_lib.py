@@ -25,6 +25,7 @@ EXPORTS = [
     "gsdd_cond_dropout", "gsdd_cond_null_grad", "gsdd_set_deterministic",
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
+    "gsdd_grad_sqnorm", "gsdd_grad_norm_finalize", "gsdd_adamw_ema_multi", "gsdd_swap_multi",
 ]
 
 _p = C.c_void_p
@@ -100,6 +101,12 @@ class LayerDesc(C.Structure):
     ]
 
 
+class OptimState(C.Structure):
+    """gsdd_optim_state: the optimiser stage's device words (the host writes step and lr, gsdd_grad_norm_finalize the rest)"""
+    _fields_ = [("step", _i64), ("skipped_steps", _i64), ("lr", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
+                ("finite", C.c_int32)]
+
+
 # variant / mode arguments of include/gsdd.h (GSDD_*): the library reads no environment variable; ops.py maps the debugging
 # environment switches onto these
 GEMM_EXACT_F32 = 1
@@ -128,7 +135,8 @@ def lib():
         L.gsdd_abi_sizeof.argtypes, L.gsdd_abi_sizeof.restype = [_i], _i64
         for which, name, cls in ((0, "gsdd_gemm_desc", GemmDesc), (1, "gsdd_layer_desc", LayerDesc), (2, "gsdd_step_desc", StepDesc),
                                  (3, "gsdd_train_desc", TrainDesc), (4, "gsdd_purity_desc", PurityDesc),
-                                 (5, "gsdd_purity_select_desc", PuritySelectDesc), (7, "gsdd_jump_desc", JumpDesc)):      # (6 is not assigned)
+                                 (5, "gsdd_purity_select_desc", PuritySelectDesc), (7, "gsdd_jump_desc", JumpDesc),
+                                 (8, "gsdd_optim_state", OptimState)):      # (6 is not assigned)
             if L.gsdd_abi_sizeof(which) != C.sizeof(cls):
                 raise GsddError(f"{LIB_PATH} was built from another revision of include/gsdd.h: sizeof({name}) is {L.gsdd_abi_sizeof(which)} "
                                 f"there and {C.sizeof(cls)} in this binding -- rebuild it with ./build.sh")
@@ -199,6 +207,10 @@ def lib():
         L.gsdd_adam.argtypes = [_p, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_float, C.c_float, _i, _p]
         L.gsdd_adam_multi.argtypes = [_p, _i, C.c_float, C.c_float, C.c_float, C.c_float, _i, _p]
         L.gsdd_adam_multi_dev.argtypes = [_p, _i, C.c_float, C.c_float, C.c_float, C.c_float, _p, _p]
+        L.gsdd_grad_sqnorm.argtypes = [_p, _i, _p, _p]
+        L.gsdd_grad_norm_finalize.argtypes = [_p, _i, C.c_float, _i, _p, _p]
+        L.gsdd_adamw_ema_multi.argtypes = [_p, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _p, _p]
+        L.gsdd_swap_multi.argtypes = [_p, _i, _p]
         L.gsdd_advance.argtypes = [_p, _i, _i64, _p, _i64, _p]
         L.gsdd_advance_floor.argtypes = [_p, _i, _i64, _i64, _p, _i64, _p]
         L.gsdd_d3pm_purity_step.argtypes = [C.POINTER(PurityDesc), _p]

@@ -5,6 +5,7 @@ torch.autograd of the CPU oracle; the sampling path does not depend on anything 
 Reference: MultistageTextMotionModel.allsplit_step (src/models/multistage_text_motion_model.py:170-206: zero_grad ->
 manual_backward -> Adam(lr 1e-4, betas (0.5, 0.999))) around DiffusionTransformer._train_loss
 (src/models/motionencoder/diffusion_transformer.py:391-457); DDP gradient averaging = configs/trainer/default.yaml:8."""
+import contextlib
 import itertools
 import os
 import warnings
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._optim import GradArena, GradBook, MultiAdam
+from ._optim import GradArena, GradBook, MultiAdam, check_stage_args, linear_warmup          # noqa: F401  (linear_warmup: the shipped lr_schedule)
 from ._lib import GsddError
 from .parallel import GradReducer, broadcast_module, world_size
 
@@ -119,15 +120,56 @@ class _RowGemm:
         return ops.linear(dy, w.t().contiguous(), out)
 
 
+def default_decay_mask(transformer, extra_no_decay=()):
+    """name -> bool over the transformer's parameters, by module type: the weight matrices of nn.Linear layers decay; biases, every
+    LayerNorm / AdaLayerNorm parameter (its embedding and its linear layer included) and every nn.Embedding table do not.  Names in
+    `extra_no_decay` (the learned null embedding) are added as non-decaying."""
+    from .d3pm import AdaLayerNorm
+    mask = {}
+
+    def walk(mod, prefix, in_norm):
+        in_norm = in_norm or isinstance(mod, (torch.nn.LayerNorm, AdaLayerNorm))
+        for nm, _ in mod.named_parameters(recurse=False):
+            mask[prefix + nm] = bool(isinstance(mod, torch.nn.Linear) and nm == "weight" and not in_norm)
+        for cn, child in mod.named_children():
+            walk(child, prefix + cn + ".", in_norm)
+
+    walk(transformer, "", False)
+    for nm in extra_no_decay:
+        mask[nm] = False
+    return mask
+
+
 class D3PMTrainer:
     NULL_NAME = "empty_text_embed"       # the learned null embedding in the gradient dict and the optimiser's parameter list
 
-    def __init__(self, dm, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, deterministic=None):
-        """deterministic: True runs the backward's reductions in their reproducible form (ops.set_deterministic: one workgroup per
+    def __init__(self, dm, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, deterministic=None, max_grad_norm=None, weight_decay=0.0,
+                 ema_decay=None, skip_nonfinite=False, lr_schedule=None, decay_mask=None):
+        """max_grad_norm / weight_decay / ema_decay / skip_nonfinite / lr_schedule: the optimiser stage (_optim.MultiAdam): global-norm
+        clipping (torch's clip_grad_norm_), decoupled weight decay (torch.optim.AdamW; `decay_mask`, name -> bool, defaults to
+        `default_decay_mask`), an exponential moving average of the weights with the warm-up decay min(ema_decay, (1 + step) /
+        (10 + step)), a guard that skips the update when the gradient norm is inf / NaN, and a learning-rate schedule (a callable
+        step -> lr, the step counted from 1, evaluated on the host before each step; `linear_warmup`).  With any of them set the
+        learning rate, the step count, the norm and the clip coefficient are device words: the captured step is keyed without the
+        learning rate and one graph serves every step of a schedule.  `last_grad_norm` is the norm as a device scalar (reading it
+        waits for the step; not reading it costs nothing), `skipped_steps` reads the guard's count from the device.  A skipped step
+        still advances the step count (the bias corrections and the EMA warm-up see it), which keeps the host's and the device's
+        counts equal without a read-back.  With all of them at their defaults the step is plain Adam, exactly as before.
+        Data-parallel runs need nothing extra: the gradients are all-reduced before the optimiser, so every rank clips by the norm of
+        the same mean gradient, takes the same decision in the guard and keeps the same average.
+        deterministic: True runs the backward's reductions in their reproducible form (ops.set_deterministic: one workgroup per
         output address instead of float atomics) -- two calls on the same inputs then give the same gradient bits, at a cost in step
         time; None reads GSDD_TRAIN_DETERMINISTIC=1.  The default (False) is the fast form, whose gradients differ from run to run in
         their last bits."""
         self.dm, self.lr, self.betas, self.eps = dm, lr, betas, eps
+        self.lr_schedule = lr_schedule
+        self._optim_kw = dict(max_grad_norm=max_grad_norm, weight_decay=weight_decay, ema_decay=ema_decay,
+                              skip_nonfinite=bool(skip_nonfinite), device_lr=lr_schedule is not None)
+        self._decay_mask = decay_mask
+        check_stage_args(max_grad_norm, weight_decay, ema_decay)           # now, not at the first step
+        self._staged = bool(max_grad_norm is not None or float(weight_decay) > 0 or ema_decay is not None or skip_nonfinite
+                            or lr_schedule is not None)
+        self._in_ema = False                # inside ema_weights(): the transformer holds the averaged weights
         self.deterministic = (os.environ.get("GSDD_TRAIN_DETERMINISTIC") == "1") if deterministic is None else bool(deterministic)
         self.step_count = 0
         self.state = {}
@@ -140,6 +182,7 @@ class D3PMTrainer:
         self._adam, self._pending_adam = None, None         # MultiAdam from the first step; a state loaded before it exists
         self._graph, self._graphs = None, {}                # the captured step in use; the two most recent by key
         self._eager_steps, self._graph_failed = 0, False
+        self.captures = 0                                   # how many times a step was captured (a schedule must not re-capture)
 
     def _sync_start(self):
         """Once, before the first data-parallel step: every rank takes rank 0's parameters and buffers (what DDP does at wrap time)."""
@@ -515,7 +558,7 @@ class D3PMTrainer:
         from the dropout decisions inside the graph."""
         dm, dev = self.dm, x0.device
         B = x0.shape[0]
-        st = {"shape": (tuple(x0.shape), tuple(cond.shape)), "lr": self.lr,
+        st = {"shape": (tuple(x0.shape), tuple(cond.shape)), "lr": None if self._staged else self.lr,      # (staged: lr is a device word)
               "x0": x0.clone().long().contiguous(), "cond": cond.clone().float().contiguous(),
               "t": torch.zeros((B,), dtype=torch.int64, device=dev), "pt": torch.full((B,), 1.0 / dm.num_timesteps, dtype=torch.float32, device=dev),
               "sid": torch.tensor([dm.noise_stream], dtype=torch.int64, device=dev),
@@ -531,9 +574,12 @@ class D3PMTrainer:
             loss, grads = self.loss_and_grads(st["x0"], st["cond"], st["t"], st["pt"], reduce=False, sid=st["sid"], null_cond=st["null"],
                                               drop=st["drop"], cond_len=st["len"])
             self._adam.lr = self.lr
-            self._adam.step(grads, step_dev=st["adam_step"])
+            # (staged: step and lr are words of the optimiser's state block, written before each replay; the stage's launches are
+            # the same nodes here as in the launch-by-launch step)
+            self._adam.step(grads, step_dev=st["adam_step"], write_words=False)
             self._write_back_null(grads, cond.shape[1])
         dm.noise_stream, self._adam.step_count = keep             # capture executed nothing
+        self.captures += 1
         st["graph"], st["loss"], st["packed"] = graph, loss, tr._packed
         tr._packed = None
         return st
@@ -544,6 +590,10 @@ class D3PMTrainer:
         cond_len: the per-sample condition lengths (loss_and_grads).
         With dm.learnable_cf the learned null embedding is updated with the transformer's parameters: its f32 copy and its gradient go
         through the same Adam launch, and rows [:Te] of the updated copy are written back into the fp64 parameter."""
+        if self._in_ema:
+            raise GsddError("D3PMTrainer.step inside ema_weights(): the transformer holds the averaged weights")
+        if self.lr_schedule is not None:
+            self.lr = float(self.lr_schedule(self._next_step()))
         self._sync_start()
         cond_len = self._check_lengths(cond, cond_len)
         if self._graph_usable(x0, cond):
@@ -563,7 +613,8 @@ class D3PMTrainer:
         graphs = self._graphs
         # ... and per condition-dropout setting: the probability is a launch constant of the dropout kernel, and the learned null
         # embedding, a mask and a caller's null condition each change the graph's nodes
-        key = (tuple(x0.shape), tuple(cond.shape), float(self.lr), float(getattr(self.dm, "cond_drop_prob", 0.0) or 0.0),
+        # (with the optimiser stage the learning rate is a device word and not part of the key: one graph serves a whole schedule)
+        key = (tuple(x0.shape), tuple(cond.shape), None if self._staged else float(self.lr), float(getattr(self.dm, "cond_drop_prob", 0.0) or 0.0),
                bool(self.dm.learnable_cf), drop is not None, null_cond is not None, self.deterministic, cond_len is not None)
         st = self._graph = graphs.get(key)
         if st is None and self._eager_steps < 2:
@@ -603,6 +654,8 @@ class D3PMTrainer:
         # must use the stream id the eager step would
         st["sid"].fill_(dm.noise_stream)
         st["adam_step"].fill_(self._adam.step_count + 1)
+        if self._staged:
+            self._adam.write_step_words(self._adam.step_count + 1, self.lr)
         st["graph"].replay()
         dm.noise_stream += 1
         self._adam.step_count += 1
@@ -621,7 +674,11 @@ class D3PMTrainer:
             # the learned null embedding joins the parameter list (last) as its f32 copy: one Adam launch updates everything, and
             # optimizer_state() / load_optimizer_state() carry its moments with the rest
             plist = list(params.items()) + ([(self.NULL_NAME, self._null32)] if learned else [])
-            self._adam = MultiAdam(plist, self.lr, self.betas, self.eps)
+            kw = {}
+            if self._staged:
+                mask = self._decay_mask if self._decay_mask is not None else default_decay_mask(tr, (self.NULL_NAME,))
+                kw = dict(self._optim_kw, decay_mask=mask)
+            self._adam = MultiAdam(plist, self.lr, self.betas, self.eps, **kw)
             self._adam.load_state(self._pending_adam)
             self._pending_adam = None
         if learned != (self._adam.params[-1][0] == self.NULL_NAME):
@@ -634,8 +691,98 @@ class D3PMTrainer:
         tr._packed = None                       # parameters changed in place through raw pointers
         return loss
 
+    # ------------------------------------------------------------------ the optimiser stage's accessors; the averaged weights
+    def _next_step(self):
+        """the count (from 1) of the coming optimiser step, a resumed state's steps included"""
+        if self._adam is not None:
+            return self._adam.step_count + 1
+        return int((self._pending_adam or {}).get("step", 0)) + 1
+
+    @property
+    def last_grad_norm(self):
+        """The last step's global gradient norm (before clipping) as a device scalar; None before the first step or when neither
+        clipping nor the non-finite guard is on.  Reading its value waits for the step; not reading it costs nothing."""
+        if self._adam is None or not (self._optim_kw["max_grad_norm"] is not None or self._optim_kw["skip_nonfinite"]):
+            return None
+        return self._adam.grad_norm
+
+    @property
+    def skipped_steps(self):
+        """how many updates the non-finite guard has skipped, read from the device on request"""
+        if self._adam is None:
+            return int((self._pending_adam or {}).get("skipped_steps", 0))
+        return self._adam.skipped_steps
+
+    @property
+    def has_ema(self):
+        return self._optim_kw["ema_decay"] is not None
+
+    def _drop_weight_caches(self):
+        """everything derived from the transformer's weights that does not notice a write through raw pointers: the packed views with
+        their AdaLN tables and the sampler's fragment images (all inside `_packed`).  The trainer's `_LinearImages` are re-packed by
+        every forward, a captured step re-packs inside its graph."""
+        self.dm.transformer._packed = None
+        self.last_fwd = None
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the transformer (and, with a learned null embedding, dm.empty_text_embed) holds the averaged weights:
+        one gsdd_swap_multi exchanges parameters and averages in place, a second one on exit puts both back, bit for bit.  Before the
+        first optimiser step the average IS the parameters and nothing is exchanged.  Nesting, or a training step inside the
+        context, raises GsddError."""
+        if not self.has_ema:
+            raise GsddError("ema_weights(): this trainer keeps no averaged weights (ema_decay is None)")
+        if self._in_ema:
+            raise GsddError("ema_weights() is already active: the context does not nest")
+        adam = self._adam if (self._adam is not None and self._adam.ema is not None) else None
+        null_live = None
+        self._in_ema = True
+        try:
+            if adam is not None:
+                learned = adam.params[-1][0] == self.NULL_NAME
+                if learned:            # the f32 copy is exchanged with the rest; the fp64 parameter takes the averaged rows for the duration
+                    null_live = self.dm.empty_text_embed.data.clone()
+                adam.swap_ema()
+                if learned:
+                    self.dm.empty_text_embed.data.copy_(self._null32)
+                self._drop_weight_caches()
+            yield self
+        finally:
+            if adam is not None:
+                adam.swap_ema()
+                if null_live is not None:
+                    self.dm.empty_text_embed.data.copy_(null_live)
+                self._drop_weight_caches()
+            self._in_ema = False
+
+    def ema_state_dict(self):
+        """The averaged weights under the transformer's state_dict keys, CPU tensors (buffers, if any, as they are):
+        transformer.load_state_dict and load_reference_checkpoint take them.  Before the first step: the current weights."""
+        if not self.has_ema:
+            raise GsddError("ema_state_dict(): this trainer keeps no averaged weights (ema_decay is None)")
+        tr = self.dm.transformer
+        sd = {k: v.detach().cpu().clone() for k, v in tr.state_dict().items()}
+        if self._adam is not None and self._adam.ema is not None:
+            if self._in_ema:
+                raise GsddError("ema_state_dict() inside ema_weights(): the average and the weights are exchanged")
+            for name, t in self._adam.ema_tensors().items():
+                if name != self.NULL_NAME:
+                    sd[name] = t.cpu()
+        return sd
+
+    def ema_null_embedding(self):
+        """the averaged learned null embedding, (77, 512) fp64 on the CPU (rows the training never reached keep the parameter's
+        values), or None when the optimiser does not carry it"""
+        a = self._adam
+        if a is None or a.ema is None or a.params[-1][0] != self.NULL_NAME:
+            return None
+        return a.ema_tensors()[self.NULL_NAME].double().cpu()
+
     # ------------------------------------------------------------------ optimiser state for checkpoints (exact resume)
     def optimizer_state(self):
+        """m, v, the step count and -- with the optimiser stage -- the averaged weights (`ema`) and the guard's `skipped_steps`"""
+        if self._in_ema:
+            raise GsddError("optimizer_state() inside ema_weights(): the average and the weights are exchanged")
         return self._adam.state() if self._adam is not None else self._pending_adam
 
     def load_optimizer_state(self, state):

@@ -741,6 +741,28 @@ def adam(p, g, m, v, lr, beta1, beta2, eps, step, stream=None):
     check(lib().gsdd_adam(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, stream_ptr(stream)))
 
 
+# ----------------------------------------------------------------------------- optimiser stage (gsdd_optim_state; _optim.MultiAdam)
+def grad_sqnorm(table, partials, stream=None):
+    """partials[b] (float64) = sum of g^2 over block b of the wide table (int64 (n_blocks, 7))"""
+    check(lib().gsdd_grad_sqnorm(ptr(table), table.shape[0], ptr(partials), stream_ptr(stream)))
+
+
+def grad_norm_finalize(partials, n_blocks, max_norm, skip_nonfinite, state, stream=None):
+    """norm, clip coefficient, finite flag and skip count into the device state block; max_norm None: no clipping"""
+    check(lib().gsdd_grad_norm_finalize(ptr(partials), n_blocks, float("inf") if max_norm is None else max_norm,
+                                        1 if skip_nonfinite else 0, ptr(state), stream_ptr(stream)))
+
+
+def adamw_ema_multi(table, beta1, beta2, eps, weight_decay, ema_decay, state, stream=None):
+    check(lib().gsdd_adamw_ema_multi(ptr(table), table.shape[0], beta1, beta2, eps, weight_decay, ema_decay or 0.0, ptr(state),
+                                     stream_ptr(stream)))
+
+
+def swap_multi(table, stream=None):
+    """exchanges every block's parameter and running average, exactly"""
+    check(lib().gsdd_swap_multi(ptr(table), table.shape[0], stream_ptr(stream)))
+
+
 def set_deterministic(on):
     """Switches the training step's gradient reductions to their reproducible form (gsdd_set_deterministic; process-wide) -> the
     previous setting.  D3PMTrainer(deterministic=True) brackets its calls with it."""

@@ -33,7 +33,7 @@ extern "C" {
 const char* gsdd_last_error(void);
 int gsdd_version(void);
 /* sizeof of a descriptor struct as this build of the library sees it (which: 0 gsdd_gemm_desc, 1 gsdd_layer_desc, 2 gsdd_step_desc,
- * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc, 7 gsdd_jump_desc; anything else, 6 included: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
+ * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc, 7 gsdd_jump_desc, 8 gsdd_optim_state; anything else, 6 included: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
  * library built from another revision of this header fails at load time instead of misreading a descriptor. */
 int64_t gsdd_abi_sizeof(int which);
 
@@ -585,6 +585,43 @@ int gsdd_adam_multi(const int64_t* table, int n_blocks, float lr, float beta1, f
  * caller sets *step_dev before each replay, or advances it with gsdd_advance inside the graph). */
 int gsdd_adam_multi_dev(const int64_t* table, int n_blocks, float lr, float beta1, float beta2, float eps, const int64_t* step_dev,
                         void* stream);
+
+/* ------------------------------------------------------------------ optimiser stage: gradient norm, clip, AdamW, EMA, non-finite skip
+ * Three launches per step whatever the number of parameters, over a WIDE block table: table[b] = {p, g, m, v, n, e, flags} (7 int64;
+ * device pointers as int64, 1 <= n <= 4096 elements of one tensor; e: the tensor's running average or 0; flags bit 0
+ * (GSDD_OPTIM_DECAYS): the tensor takes weight decay).  p and g need 4-byte alignment only (16-byte aligned ones are read four wide);
+ * m, v and e are 16-byte aligned at every block.  Everything that changes from step to step lives in the device state block, so the
+ * three launches are the same graph nodes in a launch-by-launch step and in a captured, replayed one.  The caller writes `step`
+ * (>= 1, the count of THIS update) and `lr` before the stage; gsdd_grad_norm_finalize writes the other words.  A state block that
+ * never went through finalize must hold clip_coef = 1, finite = 1.
+ * The gradient buffers are NEVER rewritten: the update applies the clip coefficient to the gradients it reads, g itself keeps the
+ * unclipped values; the norm and the coefficient are available to the caller as the device scalars state->grad_norm / clip_coef. */
+#define GSDD_OPTIM_DECAYS 1
+typedef struct {
+    int64_t step;             /* caller: the step count of this update, >= 1 (bias corrections, EMA warm-up)                          */
+    int64_t skipped_steps;    /* finalize: += 1 whenever skip_nonfinite is on and the norm is inf / NaN                               */
+    float lr;                 /* caller: this step's learning rate                                                                    */
+    float grad_norm;          /* finalize: the global L2 norm of the gradients                                                        */
+    float clip_coef;          /* finalize: min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); 1 without clipping      */
+    int32_t finite;           /* finalize: 0 iff skip_nonfinite is on and the norm is inf / NaN -- the update then writes nothing     */
+} gsdd_optim_state;
+/* partials[b] = sum of g^2 over block b, accumulated in double (the square of an f32 is exact in double); one workgroup per block,
+ * no atomics, a fixed order: the same inputs give the same bits. */
+int gsdd_grad_sqnorm(const int64_t* table, int n_blocks, double* partials, void* stream);
+/* One workgroup: sums partials[0 .. n_blocks) in a fixed order in double and writes grad_norm, clip_coef, finite and skipped_steps.
+ * max_norm > 0; +infinity means "no clipping" (clip_coef = 1).  skip_nonfinite == 0: finite is always 1 and nothing is counted (a
+ * non-finite norm then poisons the update exactly as torch's clip_grad_norm_ + AdamW would). */
+int gsdd_grad_norm_finalize(const double* partials, int n_blocks, float max_norm, int skip_nonfinite, gsdd_optim_state* state,
+                            void* stream);
+/* The update, one workgroup per block; step, lr, clip_coef and finite are read from *state.  finite == 0: nothing is written.
+ * Otherwise with g' = clip_coef g:  p <- p (1 - lr weight_decay) for tensors with GSDD_OPTIM_DECAYS (torch.optim.AdamW: decay first),
+ * then gsdd_adam_multi_dev's arithmetic on g' in its operation order (bias corrections in double per workgroup), then where e != 0
+ * e <- d e + (1 - d) p_new with d = min(ema_decay, (1 + step) / (10 + step)) evaluated in double per workgroup.
+ * weight_decay >= 0, 0 <= ema_decay < 1 (read only where a block has an e). */
+int gsdd_adamw_ema_multi(const int64_t* table, int n_blocks, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                         const gsdd_optim_state* state, void* stream);
+/* Exchanges p and e of every block that has an e, exactly (the averaged weights in and out of the model, one launch). */
+int gsdd_swap_multi(const int64_t* table, int n_blocks, void* stream);
 
 /* ------------------------------------------------------------------ classifier-free training: condition dropout, learned null embedding
  * (the reference substitutes empty_text_embed for the condition at diffusion_transformer.py:541-543) */

@@ -1,4 +1,7 @@
-"""`python src/eval.py model=discrete_diffusion ckpt_path=...` (reference: src/eval.py:8-13, src/tasks/eval_task.py:14-62)."""
+"""`python src/eval.py model=discrete_diffusion ckpt_path=...` (reference: src/eval.py:8-13, src/tasks/eval_task.py:14-62).
+`model.use_ema=true` evaluates the averaged weights a run with native_step=true and native_optim.ema_decay keeps in its checkpoint
+(checkpoint["gsdd"]["native_adam"]["ema"]; the model wrapper loads them into the generator when the checkpoint is read, and a
+checkpoint without them is an error that names the key)."""
 import os
 import sys
 

@@ -12,7 +12,13 @@ Deliberate differences, each behind a flag that restores the reference's behavio
   * `step_in_eval_splits=False`: the reference calls `opt.step()` for every optimiser in the val/test splits too (:199-200),
     re-applying the last training gradients; not reproduced unless asked for.
   * `native_step=False`: True replaces zero_grad/backward/Adam by gsdd_amd.d3pm_train.D3PMTrainer.step (same arithmetic, one
-    arena + one Adam launch, data-parallel all-reduce built in)."""
+    arena + one Adam launch, data-parallel all-reduce built in).
+  * `native_optim` (with native_step only): the native step's optimiser stage -- max_grad_norm, weight_decay, betas, ema_decay,
+    skip_nonfinite, warmup_steps (D3PMTrainer); all off by default.  With an average (ema_decay) and `sample_with_ema` every sampling
+    call of the wrapper runs on the averaged weights.  `use_ema` (evaluation): the averaged weights of the checkpoint are loaded into
+    the generator."""
+import contextlib
+
 import torch
 
 from gsdd_amd.hydra_lite import instantiate
@@ -20,11 +26,32 @@ from src.models.base import BaseModel
 from src.models.text_motion_model import _make_losses
 
 
+NATIVE_OPTIM_DEFAULTS = {"max_grad_norm": None, "weight_decay": 0.0, "betas": None, "ema_decay": None, "skip_nonfinite": False,
+                         "warmup_steps": None}
+EMA_KEY = 'checkpoint["gsdd"]["native_adam"]["ema"]'
+
+
+def check_native_optim(native_optim, native_step):
+    """-> the native_optim keys over their defaults; an unknown key, or any key set without native_step, is an error"""
+    opt = dict(NATIVE_OPTIM_DEFAULTS)
+    given = dict(native_optim or {})
+    unknown = sorted(set(given) - set(opt))
+    if unknown:
+        raise ValueError(f"native_optim: unknown keys {unknown}; the keys are {sorted(opt)}")
+    opt.update(given)
+    active = sorted(k for k, v in opt.items() if v != NATIVE_OPTIM_DEFAULTS[k])
+    if active and not native_step:
+        raise ValueError(f"native_optim.{active[0]} is set but native_step is false: the native_optim keys ({', '.join(active)}) "
+                         "configure the native HIP training step only -- set native_step=true, or leave them at their defaults "
+                         "(the torch optimiser path is not changed by them)")
+    return opt
+
+
 class MultistageTextMotionModel(BaseModel):
     def __init__(self, generator, autoencoder, generator_losses=None, autoencoder_losses=None, length_estimator_losses=None,
                  checkpoint_paths=None, evaluator=None, freeze_models_dict=None, lr_args={}, render_animations=True,
                  do_evaluation=False, devices="cpu", autoencoder_train_mode=False, step_in_eval_splits=False, native_step=False,
-                 **kwargs):
+                 native_optim=None, sample_with_ema=True, use_ema=False, **kwargs):
         super().__init__()
         self.gpu_device = devices if devices == "cpu" else "cuda:" + str(devices[0])
         self.generator = instantiate(generator, device=self.gpu_device, _recursive_=False) if isinstance(generator, dict) else generator
@@ -46,6 +73,8 @@ class MultistageTextMotionModel(BaseModel):
         self.autoencoder_train_mode = bool(autoencoder_train_mode)
         self.step_in_eval_splits = bool(step_in_eval_splits)
         self.native_step = bool(native_step)
+        self.native_optim = check_native_optim(native_optim, self.native_step)
+        self.sample_with_ema, self.use_ema = bool(sample_with_ema), bool(use_ema)
         self._native = None
         if not self.autoencoder_train_mode:
             self.autoencoder.eval()
@@ -72,15 +101,30 @@ class MultistageTextMotionModel(BaseModel):
         outputs["length"] = batch["length"]
         return outputs
 
+    def ema_scope(self):
+        """The averaged weights for the duration of a sampling call: the native trainer's ema_weights() when it keeps an average and
+        `sample_with_ema` is on (and no such scope is open already), else a context that does nothing."""
+        nt = self._native
+        if nt is None or not self.sample_with_ema or not nt.has_ema or nt._in_ema:
+            return contextlib.nullcontext()
+        return nt.ema_weights()
+
     def sample_generator_step(self, batch):                             # :160-168
-        outputs = self.generator(batch, self.autoencoder, self.length_estimator, do_inference=True)
-        outputs["length"] = batch["length"]
+        with self.ema_scope():
+            outputs = self.generator(batch, self.autoencoder, self.length_estimator, do_inference=True)
+            outputs["length"] = batch["length"]         # (the deferred by-products are VQ-VAE decodes of tokens: no transformer weight)
         return outputs
 
     def _native_train_step(self, batch):
         from gsdd_amd.d3pm_train import D3PMTrainer
         if self._native is None:
-            self._native = D3PMTrainer(self.generator.diffusion_model, lr=self.lr_args.get("gen_lr", 1e-4))
+            o, lr = self.native_optim, self.lr_args.get("gen_lr", 1e-4)
+            kw = {"betas": tuple(o["betas"])} if o["betas"] is not None else {}
+            if o["warmup_steps"] is not None:
+                from gsdd_amd.d3pm_train import linear_warmup
+                kw["lr_schedule"] = linear_warmup(lr, o["warmup_steps"])
+            self._native = D3PMTrainer(self.generator.diffusion_model, lr=lr, max_grad_norm=o["max_grad_norm"],
+                                       weight_decay=o["weight_decay"], ema_decay=o["ema_decay"], skip_nonfinite=o["skip_nonfinite"], **kw)
             self._native.load_optimizer_state(getattr(self, "_native_state", None))
         from gsdd_amd.parallel import broadcast_buffers, set_rank_noise_rows
         with torch.no_grad():
@@ -129,7 +173,8 @@ class MultistageTextMotionModel(BaseModel):
                 total_dico.update(dico)
                 total_dico[s] = total
         if self.do_evaluation and split != "train" and self.current_epoch % 5 == 0:
-            metrics = self.evaluator.evaluate_metrics(self.trainer.datamodule, self.generator)
+            with self.ema_scope():
+                metrics = self.evaluator.evaluate_metrics(self.trainer.datamodule, self.generator)
             total_dico.update({f"Metrics/{m}-{split}": v for m, v in metrics.items()})
             self.evaluator.reset()
         if split == "val" and self.current_epoch % 10 == 0:
@@ -146,6 +191,30 @@ class MultistageTextMotionModel(BaseModel):
         self._native_state = (checkpoint.get("gsdd") or {}).get("native_adam")
         if self._native is not None:
             self._native.load_optimizer_state(self._native_state)
+        if self.use_ema:
+            self.load_ema_weights(checkpoint)
+
+    def load_ema_weights(self, checkpoint):
+        """Evaluation with `use_ema`: the averaged weights the native step keeps in its optimiser state go into the generator's
+        transformer (and, when the optimiser carried it, the learned null embedding).  A checkpoint without them is an error."""
+        from gsdd_amd._optim import unflatten
+        state = (checkpoint.get("gsdd") or {}).get("native_adam") or {}
+        if state.get("ema") is None:
+            raise KeyError(f"use_ema: the checkpoint holds no averaged weights: {EMA_KEY} is missing (it is written by a run with "
+                           "native_step=true and native_optim.ema_decay set)")
+        dm = self.generator.diffusion_model
+        shapes = [(n, p.shape) for n, p in dm.transformer.named_parameters()]
+        n_tr = sum((p.numel() + 3) & ~3 for _, p in dm.transformer.named_parameters())
+        if state["ema"].numel() != n_tr:                          # the learned null embedding rides last
+            shapes.append(("empty_text_embed", dm.empty_text_embed.shape))
+        avg = unflatten(state["ema"], shapes)
+        null = avg.pop("empty_text_embed", None)
+        with torch.no_grad():
+            for n, p in dm.transformer.named_parameters():
+                p.copy_(avg[n])
+            if null is not None:
+                dm.empty_text_embed.copy_(null.double())
+        dm.transformer._packed = None
 
     def configure_optimizers(self):                                     # :240-252
         b1, b2 = 0.5, 0.999

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time one D3PM training step (config C4 per-rank shape: bs 16, 16x16x16 tokens, 19 layers, K = 4096) on the HIP path.
-usage: bench_train.py [B [steps]] [--cond-tokens N] [--cond-drop P]
+usage: bench_train.py [B [steps]] [--cond-tokens N] [--cond-drop P] [--optim]
+  --optim           the optimiser stage on: clip (max_grad_norm 1), AdamW (weight_decay 0.045, betas (0.9, 0.96)), averaged weights
+                    (ema_decay 0.99), non-finite guard, 5000-step warm-up -- three launches in place of the one Adam launch
   --cond-tokens N   N condition tokens per clip (default 1: the pooled text embedding)
   --cond-drop P     classifier-free training: a second trainer on the same weights with cond_drop_prob = P and learnable_cf (condition
                     dropout, learned null embedding) is stepped in alternation with the plain one; both medians are printed"""
@@ -26,6 +28,12 @@ def main():
         i = sys.argv.index("--cond-drop")
         p_drop = float(sys.argv[i + 1])
         del sys.argv[i:i + 2]
+    optim = {}
+    if "--optim" in sys.argv:
+        sys.argv.remove("--optim")
+        from gsdd_amd.d3pm_train import linear_warmup
+        optim = dict(max_grad_norm=1.0, weight_decay=0.045, betas=(0.9, 0.96), ema_decay=0.99, skip_nonfinite=True,
+                     lr_schedule=linear_warmup(1e-4, 5000))
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     L, K = 4096, 4096
     torch.manual_seed(0)
@@ -34,7 +42,7 @@ def main():
                                         content_spatial_size=[64, 64], condition_dim=512, diffusion_step=100)
     dm = gsdd_amd.DiffusionTransformer(transformer=tr, diffusion_step=100, alpha_init_type="alpha1", auxiliary_loss_weight=5e-4,
                                        adaptive_auxiliary_loss=True, guidance_scale=2, content_seq_len=L).cuda()
-    trainer = D3PMTrainer(dm, lr=1e-4)
+    trainer = D3PMTrainer(dm, lr=1e-4, **optim)
     if p_drop is not None:
         import copy
         dm_cf = copy.deepcopy(dm)
@@ -58,7 +66,8 @@ def main():
         hosts.append(host * 1e3)
         losses.append(float(loss[0]))
         times.append(dt * 1e3)
-        print(f"step {i}: loss {losses[-1]:.4f}  {dt * 1e3:.1f} ms  ({B / dt:.1f} samples/s)  mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+        norm = f"  grad norm {float(trainer.last_grad_norm):.4f}" if optim else ""
+        print(f"step {i}: loss {losses[-1]:.4f}  {dt * 1e3:.1f} ms  ({B / dt:.1f} samples/s)  mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB{norm}")
         if p_drop is not None:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -75,6 +84,9 @@ def main():
         tail = sorted(times[2:])
         print(f"median of steps 2..{steps - 1}: {tail[len(tail) // 2]:.2f} ms  (min {tail[0]:.2f}); host enqueue time median "
               f"{sorted(hosts[2:])[len(hosts[2:]) // 2]:.2f} ms")
+    if optim:
+        print(f"optimiser stage: {trainer._adam.n_blocks} table blocks, last gradient norm {float(trainer.last_grad_norm):.4f}, "
+              f"skipped steps {trainer.skipped_steps}, captures {trainer.captures}")
 
 
 if __name__ == "__main__":

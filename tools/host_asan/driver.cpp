@@ -525,6 +525,39 @@ int main() {
         EXPECT(gsdd_text_pool(x, eot, nullptr, Bt, S, 6, pooled, st), GSDD_E_ARG, false);
     }
 
+    // ---------------------------------------------------------------- optimiser stage: norm, finalize, AdamW + EMA, swap
+    {
+        const int nb = 1122;             // the C4 transformer's parameters in blocks of up to 4096 elements
+        int64_t* table = devp<int64_t>((size_t)nb * 7 * 8);
+        double* partials = devp<double>((size_t)nb * 8);
+        gsdd_optim_state* os = devp<gsdd_optim_state>(sizeof(gsdd_optim_state));
+        if (gsdd_abi_sizeof(8) != (int64_t)sizeof(gsdd_optim_state) || gsdd_abi_sizeof(6) != -1) {
+            std::fprintf(stderr, "FAIL gsdd_abi_sizeof(8) / (6)\n");
+            ++g_failed;
+        }
+        EXPECT(gsdd_grad_sqnorm(table, nb, partials, st), GSDD_OK, true);
+        EXPECT(gsdd_grad_sqnorm(table, 1, partials, st), GSDD_OK, true);
+        EXPECT(gsdd_grad_sqnorm(nullptr, nb, partials, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_grad_sqnorm(table, nb, nullptr, st), GSDD_E_ARG, false);
+        for (int bad : {0, -1}) EXPECT(gsdd_grad_sqnorm(table, bad, partials, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_grad_norm_finalize(partials, nb, 1.f, 1, os, st), GSDD_OK, true);
+        EXPECT(gsdd_grad_norm_finalize(partials, nb, INFINITY, 0, os, st), GSDD_OK, true);           // no clipping
+        EXPECT(gsdd_grad_norm_finalize(nullptr, nb, 1.f, 1, os, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_grad_norm_finalize(partials, nb, 1.f, 1, nullptr, st), GSDD_E_ARG, false);
+        for (int bad : {0, -1}) EXPECT(gsdd_grad_norm_finalize(partials, bad, 1.f, 1, os, st), GSDD_E_ARG, false);
+        for (float bad : {0.f, -1.f, NAN}) EXPECT(gsdd_grad_norm_finalize(partials, nb, bad, 1, os, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_adamw_ema_multi(table, nb, 0.9f, 0.96f, 1e-8f, 4.5e-2f, 0.99f, os, st), GSDD_OK, true);
+        EXPECT(gsdd_adamw_ema_multi(table, nb, 0.5f, 0.999f, 1e-8f, 0.f, 0.f, os, st), GSDD_OK, true);
+        EXPECT(gsdd_adamw_ema_multi(nullptr, nb, 0.9f, 0.96f, 1e-8f, 0.f, 0.f, os, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_adamw_ema_multi(table, nb, 0.9f, 0.96f, 1e-8f, 0.f, 0.f, nullptr, st), GSDD_E_ARG, false);
+        for (int bad : {0, -1}) EXPECT(gsdd_adamw_ema_multi(table, bad, 0.9f, 0.96f, 1e-8f, 0.f, 0.f, os, st), GSDD_E_ARG, false);
+        for (float bad : {-1e-3f, NAN}) EXPECT(gsdd_adamw_ema_multi(table, nb, 0.9f, 0.96f, 1e-8f, bad, 0.f, os, st), GSDD_E_ARG, false);
+        for (float bad : {-0.1f, 1.f, 1.5f, NAN}) EXPECT(gsdd_adamw_ema_multi(table, nb, 0.9f, 0.96f, 1e-8f, 0.f, bad, os, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_swap_multi(table, nb, st), GSDD_OK, true);
+        EXPECT(gsdd_swap_multi(nullptr, nb, st), GSDD_E_ARG, false);
+        for (int bad : {0, -1}) EXPECT(gsdd_swap_multi(table, bad, st), GSDD_E_ARG, false);
+    }
+
     // ---------------------------------------------------------------- graph capture misuse, events
     {
         void* exec = nullptr;
