@@ -549,19 +549,7 @@ __global__ __launch_bounds__(256) void adaln_bwd_kernel(const float* dtab, const
 }
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam semantics, no weight decay / amsgrad)
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                            float bc1, float bc2) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
-}
-
-// Adam over many tensors in one launch: table[b] = {p, g, m, v, n} for block b (up to ADAM_CHUNK elements of one tensor)
+// over many tensors in one launch: table[b] = {p, g, m, v, n} for block b (up to ADAM_CHUNK elements of one tensor)
 __global__ __launch_bounds__(256) void adam_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps,
                                                          float bc1, float bc2) {
     const int64_t* e = table + (int64_t)blockIdx.x * 5;
@@ -819,16 +807,6 @@ extern "C" int gsdd_adaln_bwd(const float* dtab, const int64_t* t, int B, int D,
     else
         hipLaunchKernelGGL(adaln_bwd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dtab, t, B, D, emb, w, demb,
                            dw, db, deterministic());
-    GSDD_CHECK_LAUNCH();
-    return GSDD_OK;
-}
-
-extern "C" int gsdd_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                         int step, void* stream) {
-    GSDD_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "bad args");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                       beta2, eps, bc1, bc2);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }

@@ -737,10 +737,6 @@ def adaln_bwd(dtab, t, emb, w, demb, dw, db, stream=None):
                                stream_ptr(stream)))
 
 
-def adam(p, g, m, v, lr, beta1, beta2, eps, step, stream=None):
-    check(lib().gsdd_adam(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, stream_ptr(stream)))
-
-
 # ----------------------------------------------------------------------------- optimiser stage (gsdd_optim_state; _optim.MultiAdam)
 def grad_sqnorm(table, partials, stream=None):
     """partials[b] (float64) = sum of g^2 over block b of the wide table (int64 (n_blocks, 7))"""

@@ -575,11 +575,8 @@ int gsdd_small_linear_bwd(const float* dy, const float* x, const float* w, int R
 /* backward of gsdd_adaln_table restricted to the rows t[b]: dtab [B][2D] -> demb (+=, rows t[b]), dW (+=), db (+=) */
 int gsdd_adaln_bwd(const float* dtab, const int64_t* t, int B, int D, const float* emb, const float* w, float* demb, float* dw,
                    float* db, void* stream);
-/* torch.optim.Adam update (no weight decay), step >= 1 */
-int gsdd_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
-              void* stream);
-/* The same update over many tensors in one launch: table[b] = {p, g, m, v, n} (device pointers as int64, n <= 4096 elements) for
- * block b; the caller chops every parameter into such chunks. */
+/* torch.optim.Adam update (no weight decay), step >= 1, over many tensors in one launch: table[b] = {p, g, m, v, n} (device pointers
+ * as int64, n <= 4096 elements) for block b; the caller chops every parameter into such chunks. */
 int gsdd_adam_multi(const int64_t* table, int n_blocks, float lr, float beta1, float beta2, float eps, int step, void* stream);
 /* ... with the step count (>= 1) read from device memory at execution time: the form a captured, replayed training step uses (the
  * caller sets *step_dev before each replay, or advances it with gsdd_advance inside the graph). */
@@ -615,8 +612,13 @@ int gsdd_grad_norm_finalize(const double* partials, int n_blocks, float max_norm
                             void* stream);
 /* The update, one workgroup per block; step, lr, clip_coef and finite are read from *state.  finite == 0: nothing is written.
  * Otherwise with g' = clip_coef g:  p <- p (1 - lr weight_decay) for tensors with GSDD_OPTIM_DECAYS (torch.optim.AdamW: decay first),
- * then gsdd_adam_multi_dev's arithmetic on g' in its operation order (bias corrections in double per workgroup), then where e != 0
+ * then gsdd_adam_multi_dev's arithmetic on g' in its operation order, every operation in f32 and rounded once (the library is built
+ * without contraction):  m <- beta1 m + (1 - beta1) g' ;  v <- beta2 v + ((1 - beta2) g') g' ;
+ * p <- p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)), with the bias corrections bc_i = (float)(1 - pow((double)beta_i, (double)step))
+ * evaluated in double per workgroup; then where e != 0
  * e <- d e + (1 - d) p_new with d = min(ema_decay, (1 + step) / (10 + step)) evaluated in double per workgroup.
+ * With clip_coef = 1, no flag and e = 0 the words written are gsdd_adam_multi_dev's, bit for bit: the two extra products are by 1.f
+ * (tests/golden/adam_plain_bits.npz holds that kernel's words).
  * weight_decay >= 0, 0 <= ema_decay < 1 (read only where a block has an e). */
 int gsdd_adamw_ema_multi(const int64_t* table, int n_blocks, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
                          const gsdd_optim_state* state, void* stream);

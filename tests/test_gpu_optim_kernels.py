@@ -20,6 +20,7 @@ Bars, per element, U = 2^-24, |.| of the exact values (no fitted constants):
     absolute error of 1 - d: the subtraction is exact for d >= 1/2 and rounds once below): 2 U |d e| + (U d + 2 U (1 - d)) |p'|
     + (1 - d) bar_p' + U |e'|."""
 import math
+import os
 
 import numpy as np
 import pytest
@@ -332,3 +333,57 @@ def test_defaults_are_the_plain_adam_launch(G, step):
     check(lib().gsdd_adam_multi(ptr(table), table.shape[0], LR, B1, B2, EPS, step, stream_ptr()))
     assert torch.equal(A.pbuf, Bq.pbuf) and torch.equal(A.opt.m, Bq.opt.m) and torch.equal(A.opt.v, Bq.opt.v)
     assert not torch.equal(A.pbuf, A.p0)
+
+
+# ----------------------------------------------------------------------------- the stage with nothing on: plain Adam, the recorded bits
+def ordered(words):
+    """f32 bit patterns -> integers whose differences count ulps"""
+    a = words.view(np.int32).astype(np.int64)
+    return np.where(a < 0, -(a & 0x7FFFFFFF), a)
+
+
+@pytest.mark.parametrize("align", [False, True], ids=["gap7", "aligned16"])
+def test_stage_with_nothing_on_gives_the_recorded_plain_adam_bits(G, align):
+    """gsdd_adamw_ema_multi with clip coefficient 1, no decay and no average (device_lr: the stage's kernel with nothing else on) is plain
+    Adam.  tests/golden/adam_plain_bits.npz holds the p, m and v words that gsdd_adam_multi_dev, the captured training step's plain Adam
+    kernel, wrote on the MI355X for the fixture's inputs at steps 1, 2 and 1000 (tests/golden/make_golden_adam_plain.py).  The stage's
+    kernel must give the same words on the element-wise path (gap7: every p and g misaligned) and on the four-wide one (aligned16): the
+    arithmetic does not depend on the load width.  No tolerance: a differing word is a finding about the kernel, reported as a count and
+    the largest distance in ulps."""
+    fx = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_plain_bits.npz"), allow_pickle=False)
+    sizes = [int(n) for n in fx["sizes"]]
+    assert sizes == [1, 3, 4095, 4097] and tuple(fx["hyper"]) == (LR, B1, B2, EPS) and [int(s) for s in fx["steps"]] == [1, 2, 1000]
+    L = Layout(9, sizes, align, device_lr=True)
+    opt = L.opt
+    assert opt.staged and opt.ema is None and opt.decays == [False] * 4
+    assert all((p.data_ptr() % 16 == 0 and L.grads[nm].data_ptr() % 16 == 0) == align for nm, p in L.params)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    for (name, p, sl, _), s in zip(L.slices(), starts):
+        for dst, key in ((p, "p"), (L.grads[name], "g"), (opt.m[sl], "m"), (opt.v[sl], "v")):
+            dst.copy_(torch.from_numpy(fx[key][s:s + p.numel()]))
+    assert all(float(L.grads[nm][0]) == 0.0 for nm, _ in L.params)           # (every 11th gradient is exactly zero)
+    L.snapshot()
+    bad = {}
+    for step in (1, 2, 1000):
+        L.pbuf.copy_(L.p0)
+        opt.m.copy_(L.m0)
+        opt.v.copy_(L.v0)
+        opt.step_count = step - 1
+        opt.step(L.grads)
+        assert opt._table.shape[1] == 7
+        for which in "pmv":
+            got = np.concatenate([(p if which == "p" else getattr(opt, which)[sl]).cpu().numpy() for _, p, sl, _ in L.slices()])
+            got, want = got.view(np.uint32), fx[f"{which}_step{step}"]
+            assert got.shape == want.shape == (sum(sizes),)
+            n_bad = int((got != want).sum())
+            if n_bad:
+                bad[f"{which}_step{step}"] = (n_bad, int(np.abs(ordered(got) - ordered(want)).max()))
+        assert L.untouched(), "the update wrote a gap, a gradient or the padding of m / v"
+        assert not L.state_equal() and opt.ema is None
+        words = opt.words.cpu().numpy()
+        assert int(opt.words.view(torch.int64)[0]) == step and words.view(np.float32)[4] == np.float32(LR)
+        assert words.view(np.float32)[5] == 0.0 and words.view(np.float32)[6] == 1.0 and words[7] == 1 and opt.skipped_steps == 0
+    parity_report(f"optim_kernels::plain_adam_bits[{'aligned16' if align else 'gap7'}]",
+                  {"words_compared": 9 * sum(sizes), "words_differing": sum(n for n, _ in bad.values()),
+                   "max_ulps": max([u for _, u in bad.values()], default=0)})
+    assert not bad, f"(words differing, largest distance in ulps) from the recorded plain Adam bits: {bad}"
