@@ -11,4 +11,5 @@ from .d3pm import (DalleMaskImageEmbedding, DiffusionTransformer, DiscreteDiffus
                    Text2ImageTransformer, cond_drop_rows)
 from .i3d import InceptionI3d  # noqa: F401
 from .text import ClipTextTower  # noqa: F401
+from .vision import ClipVisionTower  # noqa: F401
 from .vqvae import VQVAE  # noqa: F401

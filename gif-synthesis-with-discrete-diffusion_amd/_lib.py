@@ -20,6 +20,7 @@ EXPORTS = [
     "gsdd_adaln_bwd", "gsdd_adam_multi", "gsdd_adam_multi_dev", "gsdd_advance", "gsdd_advance_floor",
     "gsdd_d3pm_purity_step", "gsdd_d3pm_purity_select", "gsdd_advance_plan", "gsdd_d3pm_forward_jump",
     "gsdd_text_embed", "gsdd_text_attention", "gsdd_text_pool",
+    "gsdd_clip_frame_patches", "gsdd_clip_vision_embed", "gsdd_clip_attention",
     "gsdd_ln_apply", "gsdd_d3pm_cross_attention_train", "gsdd_d3pm_cross_attention_bwd", "gsdd_d3pm_cross_attention_bwd_workspace_bytes",
     "gsdd_d3pm_cross_attention_len", "gsdd_d3pm_cross_attention_train_len", "gsdd_d3pm_cross_attention_bwd_len",
     "gsdd_cond_dropout", "gsdd_cond_null_grad", "gsdd_set_deterministic",
@@ -219,6 +220,9 @@ def lib():
         L.gsdd_text_embed.argtypes = [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]
         L.gsdd_text_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]
         L.gsdd_text_pool.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p]
+        L.gsdd_clip_frame_patches.argtypes = [_p, _i, _i, _i, _i, _i, _i, _p, _p]
+        L.gsdd_clip_vision_embed.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p]
+        L.gsdd_clip_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]
         L.gsdd_set_deterministic.argtypes = [_i]
         L.gsdd_cond_dropout.argtypes = [_p, _p, _i, _i, _i, C.c_float, C.c_uint64, _p, _i64, _p, _p, _p, _p]
         L.gsdd_cond_null_grad.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]

@@ -60,6 +60,19 @@ def extract_clip_text_tower(path_or_state):
     return out or None
 
 
+def extract_clip_vision_tower(path_or_state):
+    """The CLIP image tower of a reference Lightning checkpoint: the `visual.*` tensors under `textencoder.clip_model.` (or
+    `generator.textencoder.clip_model.`) in the `clip` package's layout (what `gsdd_amd.vision.ClipVisionTower.from_openai_state_dict`
+    takes), prefix stripped, `visual.` kept.  The reference loads the whole ViT-B/32 and uses only its text side, so the image tower
+    CLIPSIM needs travels in the same file.  None when the checkpoint carries none.  load_reference_checkpoint keeps dropping
+    `textencoder.*` as dead keys."""
+    state = read_state(path_or_state)
+    out = {}
+    for prefix in CLIP_TEXT_PREFIXES:
+        out.update({k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix + "visual.")})
+    return out or None
+
+
 def load_reference_checkpoint(module, path_or_state, prefix="auto"):
     """Load into `module` (strictly, apart from the documented dead keys).  prefix: "generator." / "autoencoder." / None /
     "auto" (use the one prefix under which the module's keys are found).  Returns the list of dropped dead keys."""

@@ -5,6 +5,19 @@ whatever device the features live on), not part of the hot path."""
 import torch
 
 
+def clip_similarity(text_embeds, frame_embeds, eps=1e-12):
+    """CLIPSIM per sample: text_embeds (B, E), frame_embeds (B, T, E) -> (B,) fp64, the mean over the T frames of the cosine similarity
+    between the caption's CLIP text feature and the frame's CLIP image feature.  Computed in fp64 with torch, like frechet_distance.
+    UNSCALED: a cosine in [-1, 1]; some papers print 100 x this number (and CLIP's own logits carry its learned temperature)."""
+    t = torch.as_tensor(text_embeds).to(torch.float64)
+    f = torch.as_tensor(frame_embeds).to(torch.float64).to(t.device)
+    if t.dim() != 2 or f.dim() != 3 or f.shape[0] != t.shape[0] or f.shape[2] != t.shape[1]:
+        raise ValueError(f"clip_similarity: text_embeds {tuple(t.shape)} / frame_embeds {tuple(f.shape)} are not (B, E) / (B, T, E)")
+    t = t / t.norm(dim=-1, keepdim=True).clamp_min(eps)
+    f = f / f.norm(dim=-1, keepdim=True).clamp_min(eps)
+    return (f * t[:, None, :]).sum(dim=-1).mean(dim=1)
+
+
 def _sym_sqrt(mat, eps=1e-10):
     """U diag(sqrt(s)) V^T with singular values below eps left as they are (evaluator.py:119-122)."""
     u, s, vh = torch.linalg.svd(mat)

@@ -603,6 +603,47 @@ def text_pool(x, eot, B, S, out, eot_host=None, stream=None):
     return out
 
 
+# ----------------------------------------------------------------------------- CLIP image tower (vision.py)
+def clip_frame_patches(clips, R, P, out=None, stream=None):
+    """ImageNet-normalised clips (B, 3, T, H, W) -> CLIP-normalised patch rows [B*T*G*G][3*P*P], G = R / P (gsdd_clip_frame_patches:
+    de-normalise, quantise to uint8 levels, torch's bicubic resize to R x R, clamp, CLIP's normalisation).  H == W <= R, R % P == 0."""
+    if clips.dim() != 5 or clips.shape[1] != 3 or clips.dtype != torch.float32:
+        raise GsddError(f"clip_frame_patches: clips must be float32 (B, 3, T, H, W), got {clips.dtype} {tuple(clips.shape)}")
+    B, _, T, H, W = clips.shape
+    if H != W or H > R or P <= 0 or R % P:
+        raise GsddError(f"clip_frame_patches: frames of {H} x {W} to resolution {R} in patches of {P}: H == W <= R and R % P == 0 "
+                        "are required (non-square or shrunk frames are not supported)")
+    G = R // P
+    if out is None:
+        out = torch.empty((B * T * G * G, 3 * P * P), dtype=torch.float32, device=clips.device)
+    elif tuple(out.shape) != (B * T * G * G, 3 * P * P):
+        raise GsddError(f"clip_frame_patches: out {tuple(out.shape)} is not {(B * T * G * G, 3 * P * P)}")
+    check(lib().gsdd_clip_frame_patches(ptr(clips), B, T, H, W, R, P, ptr(out), stream_ptr(stream)))
+    return out
+
+
+def clip_vision_embed(patches, class_emb, pos_emb, N, S, x, stream=None):
+    """x[n*S] = class_emb + pos_emb[0], x[n*S + 1 + p] = patches[n*(S-1) + p] + pos_emb[1 + p] (gsdd_clip_vision_embed)."""
+    C_ = patches.shape[1]
+    if patches.shape[0] != N * (S - 1) or tuple(x.shape) != (N * S, C_) or tuple(class_emb.shape) != (C_,) \
+            or pos_emb.shape[0] < S or pos_emb.shape[1] != C_:
+        raise GsddError(f"clip_vision_embed: patches {tuple(patches.shape)} / class {tuple(class_emb.shape)} / positions "
+                        f"{tuple(pos_emb.shape)} / x {tuple(x.shape)} do not match N = {N}, S = {S}")
+    check(lib().gsdd_clip_vision_embed(ptr(patches), ptr(class_emb), ptr(pos_emb), N, S, C_, ptr(x), stream_ptr(stream)))
+    return x
+
+
+def clip_attention(qkv, B, S, n_head, out, scale=None, stream=None):
+    """Non-causal self-attention over fused q|k|v rows [B*S][3C] -> out [B*S][C] (gsdd_clip_attention); scale defaults to d^-0.5."""
+    C_ = qkv.shape[1] // 3
+    if qkv.shape[0] != B * S or qkv.shape[1] != 3 * C_ or tuple(out.shape) != (B * S, C_):
+        raise GsddError(f"clip_attention: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
+    if scale is None:
+        scale = float(C_ // n_head) ** -0.5
+    check(lib().gsdd_clip_attention(ptr(qkv), B, S, C_, n_head, scale, ptr(out), stream_ptr(stream)))
+    return out
+
+
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):
     out = torch.empty((n_rows, n_cols), dtype=torch.float32, device=device)
     check(lib().gsdd_philox_uniform(seed, stream_id, row0, n_rows, n_cols, ptr(out), stream_ptr()))

@@ -43,6 +43,22 @@ def hf_to_openai_state_dict(sd):
     return out
 
 
+def run_resblocks(layers, attention, buf, B, S, n_head, eps):
+    """CLIP's pre-LN residual blocks over the rows in buf["x"] ([B*S][C], updated in place; y / qkv / att / h / stats are scratch):
+    LayerNorm folded into the q|k|v linear, `attention` (ops.text_attention: causal, the text tower; ops.clip_attention: every key, the
+    image tower), output linear + residual, LayerNorm folded into fc1 with QuickGELU, fc2 + residual.  Shared by both towers."""
+    x, y, qkv, att, h, stats = (buf[k] for k in ("x", "y", "qkv", "att", "h", "stats"))
+    for lay in layers:
+        ops.row_stats(x, stats, eps=eps)
+        ops.linear(x, lay["wqkv"], qkv, bias=lay["bqkv"], ln=(stats, lay["g1"], lay["be1"], None, 0))
+        attention(qkv, B, S, n_head, att)
+        ops.linear(att, lay["wo"], y, bias=lay["bo"], residual=x)
+        ops.row_stats(y, stats, eps=eps)
+        ops.linear(y, lay["w1"], h, bias=lay["b1"], ln=(stats, lay["g2"], lay["be2"], None, 0), act=ops.ACT_GELU2)
+        ops.linear(h, lay["w2"], x, bias=lay["b2"], residual=y)
+    return x
+
+
 class ClipTextTower:
     """Frozen fp32 device weights of a CLIP text tower and its forward pass on the HIP kernels.
 
@@ -162,16 +178,9 @@ class ClipTextTower:
         ids_dev = ids.contiguous() if ids.device == dev else ids_host.to(dev)
         eot_dev = eot_host.to(dev)
         buf = self._get_buffers(B, S)
-        x, y, qkv, att, h, stats = (buf[k] for k in ("x", "y", "qkv", "att", "h", "stats"))
+        x, stats = buf["x"], buf["stats"]
         ops.text_embed(ids_dev, self.tok_emb, self.pos_emb, x, S, ids_host=ids_host)
-        for lay in self.layers:
-            ops.row_stats(x, stats, eps=self.eps)
-            ops.linear(x, lay["wqkv"], qkv, bias=lay["bqkv"], ln=(stats, lay["g1"], lay["be1"], None, 0))
-            ops.text_attention(qkv, B, S, self.n_head, att)
-            ops.linear(att, lay["wo"], y, bias=lay["bo"], residual=x)
-            ops.row_stats(y, stats, eps=self.eps)
-            ops.linear(y, lay["w1"], h, bias=lay["b1"], ln=(stats, lay["g2"], lay["be2"], None, 0), act=ops.ACT_GELU2)
-            ops.linear(h, lay["w2"], x, bias=lay["b2"], residual=y)
+        run_resblocks(self.layers, ops.text_attention, buf, B, S, self.n_head, self.eps)
         if tokens:
             ops.row_stats(x, stats, eps=self.eps)
             return ops.ln_apply(x, stats, self.gf, self.bf).view(B, S, self.width)

@@ -677,6 +677,32 @@ int gsdd_text_attention(const float* qkv, int B, int S, int C, int n_head, float
  * projection then run on these B rows).  eot: int64 [B], each in [0, S). */
 int gsdd_text_pool(const float* x, const int64_t* eot, const int64_t* eot_host, int B, int S, int C, float* out, void* stream);
 
+/* ------------------------------------------------------------------ CLIP image tower (CLIPSIM in the evaluator)
+ * The three pieces of clip.model.VisionTransformer / transformers.CLIPVisionModelWithProjection that are not a gsdd_gemm /
+ * gsdd_row_stats / gsdd_ln_apply / gsdd_text_pool call; gif-synthesis-with-discrete-diffusion_amd/vision.py strings the tower
+ * together.  Every pointer is a device pointer. */
+/* clips[B][3][T][H][W] f32, ImageNet-normalised (what the decoder returns and the evaluator receives) -> patch rows
+ * out[B*T*G*G][3*P*P], G = R / P: row (b*T + t)*G*G + gy*G + gx holds the patch's pixels in the order [c][py][px] of a
+ * Conv2d(3, C, P, stride P) weight flattened to [C][3*P*P], so the patch embedding is one plain gsdd_gemm linear.
+ * Per pixel, in this order: undo the ImageNet mean / std; quantise to a uint8 level as the evaluator does ((x*255) truncated and
+ * clamped to 0..255, kept as level / 255); bicubic resize to R x R; clamp to [0, 1]; normalise with CLIP's mean (0.48145466,
+ * 0.4578275, 0.40821073) and std (0.26862954, 0.26130258, 0.27577711).
+ * The resize is TORCH's bicubic -- F.interpolate(mode="bicubic", align_corners=False, antialias=False): Keys' kernel with
+ * a = -0.75, border indices clamped -- and NOT PIL's (a = -0.5, fixed-point weights, antialiasing), which the `clip` package's
+ * preprocessing uses: parity with that preprocessing is not claimed.  H == W <= R <= 4096 and R % P == 0, anything else is
+ * GSDD_E_ARG (non-square or shrunk frames would need PIL's crop / antialiasing).  At H == R the result is the quantised frame. */
+int gsdd_clip_frame_patches(const float* clips, int B, int T, int H, int W, int R, int P, float* out, void* stream);
+/* x[n][0][:] = class_emb + pos[0],  x[n][1 + p][:] = patches[n*(S-1) + p][:] + pos[1 + p]   (the class token in FRONT of the
+ * patches, then the position embedding).  patches rows [N*(S-1)][C] (the patch gemm's output), class_emb [C], pos [S][C],
+ * x rows [N*S][C]; S = G*G + 1, 1 <= S <= 77, C % 4 == 0, rows 16-byte aligned. */
+int gsdd_clip_vision_embed(const float* patches, const float* class_emb, const float* pos, int N, int S, int C, float* x, void* stream);
+/* NON-causal multi-head self-attention over fused rows qkv[B*S][3C] = (q | k | v), head h at columns h*d of each third,
+ * d = C / n_head in {64, 32, 16}; out rows [B*S][C] = softmax(scale q k^T) v; 1 <= S <= 77 (ViT-B/32 at 224: S = 50; ViT-B/16 and
+ * ViT-L/14 have longer sequences and are out of range).  The contract and the layout of gsdd_text_attention (exact-f32 matrix
+ * instructions, v_mfma_f32_16x16x4_f32) with every query seeing every key: the keys of the last 16-key tile at positions >= S are
+ * masked before the row maximum and the sum. */
+int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */
 int gsdd_graph_begin(void* stream);

@@ -1,15 +1,21 @@
-"""FVD evaluator with the reference's interface (src/utils/evaluator.py:10-116): push_vals(batch, batch_idx, outputs) ->
-evaluate_metrics(...) -> {'fvd': ...} -> reset().  The statistic is gsdd_amd.metrics.frechet_distance (pinned to values of the
+"""FVD (and, with a scorer, CLIPSIM) evaluator with the reference's interface (src/utils/evaluator.py:10-116): push_vals(batch,
+batch_idx, outputs) -> evaluate_metrics(...) -> {'fvd': ...} -> reset().  The statistic is gsdd_amd.metrics.frechet_distance (pinned to values of the
 reference's function, tests/golden/frechet.npz).  The feature extractor is the reference's Kinetics-400 I3D
 (src/models/motionencoder/pytorch_i3d.py -> gsdd_amd/i3d.py: the same architecture and state_dict keys on the HIP conv path,
 pinned to the reference module on seeded weights) fed with clips de-normalised, resized to 224 and scaled to [-1, 1]; its
 pretrained weights cannot be obtained offline, so `checkpoint_paths` must point at a supplied state_dict (or `videoencoder` at
 any other module mapping (B,3,T,H,W) clips to features).  Unlike the reference (which never leaves train mode here:
-evaluator.py:14-29), the extractor runs in eval mode."""
+evaluator.py:14-29), the extractor runs in eval mode.
+
+CLIPSIM (not in the reference; text-to-video work on MSR-VTT reports it next to FVD): with `clip_scorer` set, push_vals also scores the
+sampled clips against `batch["text"]` -- the mean over frames of the cosine between the caption's CLIP text feature and each frame's
+CLIP image feature (gsdd_amd.metrics.clip_similarity, unscaled) -- and evaluate_metrics returns {'fvd': ..., 'clipsim': ...}, the mean
+over every sample pushed.  The image tower is gsdd_amd.vision.ClipVisionTower on the HIP kernels; its preprocessing is torch's bicubic
+on the quantised frames, not the `clip` package's PIL resize.  Without a scorer nothing of this runs and the dict is {'fvd': ...}."""
 import torch
 
 from gsdd_amd.hydra_lite import instantiate
-from gsdd_amd.metrics import frechet_distance
+from gsdd_amd.metrics import clip_similarity, frechet_distance
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
@@ -29,9 +35,47 @@ class MeanPoolEncoder(torch.nn.Module):
         return torch.nn.functional.adaptive_avg_pool3d(clips.float(), self.grid).flatten(1)
 
 
+class ClipSimScorer:
+    """CLIPSIM of clips against their captions.  text_embedder: any callable mapping a list of B strings to (B, E) features (a
+    `CLIPTextEmbedding(weights=<directory>)` is one); vision_tower: a gsdd_amd.vision.ClipVisionTower of the same CLIP model, on the
+    device it is to run on.  __call__(texts, clips (B, 3, T, H, W), ImageNet-normalised as the decoder returns them) -> (B,) fp64 on
+    the host."""
+
+    def __init__(self, text_embedder, vision_tower):
+        self.text_embedder, self.vision_tower = text_embedder, vision_tower
+
+    @torch.no_grad()
+    def __call__(self, texts, clips):
+        text = self.text_embedder(list(texts))
+        frames = self.vision_tower(clips)
+        return clip_similarity(text.detach().cpu(), frames.detach().cpu())
+
+
+def clip_scorer_from_pretrained(weights, device="cuda"):
+    """A ClipSimScorer with both towers of one CLIP model, from a LOCAL directory in the Hugging Face layout (config.json,
+    model.safetensors, vocab.json, merges.txt of e.g. `openai/clip-vit-base-patch32`).  Nothing is ever fetched: the directory must
+    exist.  Usable as a `_target_` of configs/model/evaluator.yaml's `clip_scorer`."""
+    import os
+    from transformers import CLIPVisionModelWithProjection
+    from gsdd_amd.vision import ClipVisionTower
+    from src.models.text_models.clip_text_embedding import CLIPTextEmbedding
+    if not os.path.isdir(weights):
+        raise FileNotFoundError(f"clip_scorer_from_pretrained({weights!r}): not a directory; a local copy of the CLIP model is needed "
+                                "-- nothing is downloaded")
+    vm = CLIPVisionModelWithProjection.from_pretrained(weights, local_files_only=True).eval()
+    vc = vm.config
+    text = CLIPTextEmbedding(clip_dim=vc.projection_dim, weights=weights).to(device)
+    tower = ClipVisionTower.from_hf_state_dict(vm.state_dict(), vc.num_attention_heads, eps=vc.layer_norm_eps,
+                                               hidden_act=vc.hidden_act).to(device)
+    return ClipSimScorer(text, tower)
+
+
 class Evaluator:
-    def __init__(self, device, videoencoder, checkpoint_paths=None, target_resolution=224):
+    def __init__(self, device, videoencoder, checkpoint_paths=None, target_resolution=224, clip_scorer=None):
         self.device, self.target_resolution = device, target_resolution
+        if isinstance(clip_scorer, dict):
+            clip_scorer = instantiate(clip_scorer, _recursive_=False)
+        self.clip_scorer = clip_scorer
         self.videoencoder = instantiate(videoencoder, _recursive_=False) if isinstance(videoencoder, dict) else videoencoder
         if checkpoint_paths and checkpoint_paths != "__None__":
             self.videoencoder.load_state_dict(torch.load(checkpoint_paths, map_location="cpu", weights_only=True))
@@ -44,6 +88,7 @@ class Evaluator:
 
     def reset(self):
         self.all_video_embeds_generated, self.all_video_embeds_gt = [], []
+        self.all_clip_scores = []
 
     def _prepare(self, clips):
         """evaluator.py:42-70: undo the ImageNet normalisation, quantise to uint8, preprocess at 224 (x2: [-1, 1]-ish range),
@@ -61,8 +106,13 @@ class Evaluator:
     def push_vals(self, batch, batch_idx, outputs):
         self.all_video_embeds_generated.append(self.videoencoder(self._prepare(outputs)).float().cpu())
         self.all_video_embeds_gt.append(self.videoencoder(self._prepare(batch["video"])).float().cpu())
+        if self.clip_scorer is not None:
+            self.all_clip_scores.append(self.clip_scorer(batch["text"], outputs))
 
     def evaluate_metrics(self, val_dataset=None, generator=None):
         gen = torch.cat(self.all_video_embeds_generated).flatten(1)
         gt = torch.cat(self.all_video_embeds_gt).flatten(1)
-        return {"fvd": float(frechet_distance(gen, gt))}
+        metrics = {"fvd": float(frechet_distance(gen, gt))}
+        if self.clip_scorer is not None:
+            metrics["clipsim"] = float(torch.cat(self.all_clip_scores).mean())
+        return metrics

@@ -525,6 +525,59 @@ int main() {
         EXPECT(gsdd_text_pool(x, eot, nullptr, Bt, S, 6, pooled, st), GSDD_E_ARG, false);
     }
 
+    // ---------------------------------------------------------------- CLIP image tower: frame patches, embed, non-causal attention
+    {
+        const int Bv = 16, Tv = 16, Hh = 128, R = 224, P = 32, C = 768, heads = 12, S = 50, N = Bv * Tv;
+        float *clips = devp((size_t)Bv * 3 * Tv * Hh * Hh * 4), *rows = devp((size_t)N * 49 * 3 * P * P * 4), *pe = devp((size_t)N * 49 * C * 4);
+        float *cls = devp(), *pos = devp(), *x = devp((size_t)N * S * C * 4), *qkv = devp((size_t)N * S * 3 * C * 4), *att = devp((size_t)N * S * C * 4);
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh, R, P, rows, st), GSDD_OK, true);
+        EXPECT(gsdd_clip_frame_patches(clips, 2, 3, 8, 8, 8, 8, rows, st), GSDD_OK, true);                   // H == R, one patch
+        EXPECT(gsdd_clip_frame_patches(clips, 2, 3, 37, 37, 64, 32, rows, st), GSDD_OK, true);
+        EXPECT(gsdd_clip_frame_patches(clips, 1, 1, 1, 1, 4096, 4096, rows, st), GSDD_OK, true);             // the largest resolution
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh + 1, R, P, rows, st), GSDD_E_ARG, false);       // H != W
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, 256, 256, R, P, rows, st), GSDD_E_ARG, false);         // H > R
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh, R, 48, rows, st), GSDD_E_ARG, false);          // R % P != 0
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh, 4128, P, rows, st), GSDD_E_ARG, false);        // R > 4096
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh, R, 0, rows, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(clips, 0, Tv, Hh, Hh, R, P, rows, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, -1, Hh, Hh, R, P, rows, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, 0, 0, R, P, rows, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(nullptr, Bv, Tv, Hh, Hh, R, P, rows, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(clips, Bv, Tv, Hh, Hh, R, P, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_frame_patches(clips, 1 << 20, 1 << 10, Hh, Hh, R, P, rows, st), GSDD_E_ARG, false); // grid beyond 2^31
+        EXPECT(gsdd_clip_frame_patches(clips, 1 << 30, 1 << 30, 1, 1, 1, 1, rows, st), GSDD_E_ARG, false);   // 2^60 frames
+
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, S, C, x, st), GSDD_OK, true);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, 1, C, x, st), GSDD_OK, true);                         // the class token alone
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, 77, C, x, st), GSDD_OK, true);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, 0, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, 78, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, S, 766, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, 0, S, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(nullptr, cls, pos, N, S, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, nullptr, pos, N, S, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, nullptr, N, S, C, x, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, N, S, C, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_vision_embed(pe, cls + 1, pos, N, S, C, x, st), GSDD_E_ARG, false);                 // misaligned
+        EXPECT(gsdd_clip_vision_embed(pe, cls, pos, 1 << 30, 77, 1 << 20, x, st), GSDD_E_ARG, false);        // grid beyond 2^31
+
+        for (int s : {1, 16, 17, 50, 77}) EXPECT(gsdd_clip_attention(qkv, N, s, C, heads, 0.125f, att, st), GSDD_OK, true);
+        EXPECT(gsdd_clip_attention(qkv, N, S, 64, 2, 0.1767767f, att, st), GSDD_OK, true);                   // d = 32
+        EXPECT(gsdd_clip_attention(qkv, N, S, 32, 2, 0.25f, att, st), GSDD_OK, true);                        // d = 16
+        EXPECT(gsdd_clip_attention(qkv, N, 78, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, 0, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, 5, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, 6, 0.125f, att, st), GSDD_E_ARG, false);                    // d = 128
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, 0, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, heads, 0.f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, heads, NAN, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, 0, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(nullptr, N, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv, N, S, C, heads, 0.125f, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_clip_attention(qkv + 1, N, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);            // misaligned
+        EXPECT(gsdd_clip_attention(qkv, 1 << 28, S, C, heads, 0.125f, att, st), GSDD_E_ARG, false);          // grid beyond 2^31
+    }
+
     // ---------------------------------------------------------------- optimiser stage: norm, finalize, AdamW + EMA, swap
     {
         const int nb = 1122;             // the C4 transformer's parameters in blocks of up to 4096 elements
