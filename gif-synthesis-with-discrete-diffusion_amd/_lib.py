@@ -244,14 +244,20 @@ def check(rc):
         raise GsddError(f"gsdd error {rc}: {lib().gsdd_last_error().decode()}")
 
 
+_keeper = None     # the `kept` list of the ops.Graph being recorded (set by its begin, cleared by its end), else None
+
+
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL).  Tensors must live on the GPU and be contiguous."""
+    """Device pointer of a tensor (None -> NULL).  Tensors must live on the GPU and be contiguous.  While an ops.Graph records, the
+    tensor also joins the graph's `kept` list: the address is baked into the graph, so the graph keeps its owner alive."""
     if t is None:
         return None
     if not t.is_cuda:
         raise GsddError("the HIP path needs tensors on a ROCm device (no CPU fallback)")
     if not t.is_contiguous():
         raise GsddError("non-contiguous tensor handed to the C ABI")
+    if _keeper is not None:
+        _keeper.append(t)
     return C.c_void_p(t.data_ptr())
 
 

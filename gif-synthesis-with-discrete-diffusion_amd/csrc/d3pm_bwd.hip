@@ -700,9 +700,20 @@ extern "C" int gsdd_colsum(const float* Y, int ld, int64_t M, int N, float* out,
     return GSDD_OK;
 }
 
+// out[0 .. n) = 0.  The per-batch sums' zero fill is a kernel, not hipMemsetAsync: this call is recorded into the captured training
+// step, and the memset NODE of that graph did not take effect on replays that followed eager work on the same stream (the sums then
+// started from what the pool's block held before).  A kernel node is ordered like every other node of the step.
+__global__ __launch_bounds__(256) void zero_f32_kernel(float* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = 0.f;
+}
+
 extern "C" int gsdd_batch_rowsum(const float* Y, int B, int L, int C, float* out, void* stream) {
     GSDD_CHECK_ARG(Y && out && B > 0 && L > 0 && C > 0, "bad args");
-    GSDD_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)B * C * sizeof(float), (hipStream_t)stream));
+    const int64_t n_out = (int64_t)B * C;
+    GSDD_CHECK_ARG((n_out + 255) / 256 < (1ll << 31), "too many elements");
+    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n_out);
+    GSDD_CHECK_LAUNCH();
     const int cpb = colsum_cpb(C);
     if (deterministic()) {                         // reproducible form: the column sums of one batch element by one block per column group
         for (int b = 0; b < B; ++b) {

@@ -879,8 +879,10 @@ class _Lane:
             if action == "capture":
                 g = self.graphs[kind] = ops.Graph()
                 g.begin(self.st)
-                self.OPS[kind](self)            # recorded, not executed
-                g.end(self.st)
+                try:
+                    self.OPS[kind](self)        # recorded, not executed; the graph keeps every tensor the op hands to the C ABI
+                finally:
+                    g.end(self.st)
             else:
                 self.OPS[kind](self)
                 if trace is not None:

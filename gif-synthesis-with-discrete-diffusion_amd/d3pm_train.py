@@ -32,7 +32,6 @@ class _LinearImages:
         self.tr = tr
         self.ptrs = None
         self.cross = False
-        self._retired = None       # (buf, table) from before `cross` was switched on: a step captured earlier still replays on them
 
     def _pieces(self, blk):
         a, m = blk.attn1, blk.mlp
@@ -86,10 +85,8 @@ class _LinearImages:
         """cross: the step needs the attn2.query / attn2.proj images too.  Once asked for they stay in the table (a one-token step
         that follows does not rebuild it); a trainer that only ever sees one token never packs them."""
         if cross and not self.cross:
-            # A step captured before this one replays the pack launch on the old table and images, so they stay allocated.  One retired
-            # set is enough: `cross` only ever goes from False to True, so this rebuild happens at most once per trainer.
-            if self.ptrs is not None:
-                self._retired = (self.buf, self.table)
+            # A step captured before this one replays the pack launch on the old table and images: its graph pins them
+            # (D3PMTrainer._pins), so they are simply replaced here.
             self.cross, self.ptrs = True, None
         if self.ptrs is None or self.ptrs != self._current_ptrs():
             self._build()
@@ -581,8 +578,23 @@ class D3PMTrainer:
         dm.noise_stream, self._adam.step_count = keep             # capture executed nothing
         self.captures += 1
         st["graph"], st["loss"], st["packed"] = graph, loss, tr._packed
+        st["pins"] = self._pins()
         tr._packed = None
         return st
+
+    def _pins(self):
+        """name -> tensor: everything outside a captured step's own pool that its graph replays on and that the trainer reaches only
+        through an attribute it may re-assign -- the gradient arena, Adam's address table, moments, averages, state block and partial
+        sums, the weight images with their descriptor table, the f32 null embedding.  Taken right after the capture and kept in the
+        graph's `st`: a later step that outgrows the arena, rebuilds a table or adds the cross-attention images then replaces the
+        trainer's attribute only, and the graph goes on replaying on buffers it owns.  (The parameters and the schedule buffers belong
+        to the module.)"""
+        a, im = self._adam, self._images
+        pins = {"arena.buf": self._arena.buf, "adam.table": a._table, "adam.m": a.m, "adam.v": a.v, "adam.ema": a.ema,
+                "adam.words": a.words, "adam.partials": a.partials, "null32": self._null32}
+        if im is not None and im.ptrs is not None:
+            pins["images.buf"], pins["images.table"] = im.buf, im.table
+        return {k: v for k, v in pins.items() if v is not None}
 
     @torch.no_grad()
     def step(self, x0, cond, t=None, pt=None, null_cond=None, drop=None, cond_len=None):

@@ -651,15 +651,20 @@ def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):
 
 
 class Graph:
-    """A captured hipGraph of one reverse step (gsdd_graph_* in include/gsdd.h)."""
+    """A captured hipGraph of one reverse step (gsdd_graph_* in include/gsdd.h).  The capture is a bare stream capture, with no
+    allocator pool of its own: `kept` holds every tensor handed to `ptr()` between `begin` and `end` (the temporaries an op's wrapper
+    allocates included), so that no address the graph replays on returns to the allocator before the graph is gone."""
 
     def __init__(self):
         self.handle = C.c_void_p()
+        self.kept = []
 
     def begin(self, stream):
         check(lib().gsdd_graph_begin(stream_ptr(stream)))
+        abi._keeper = self.kept
 
     def end(self, stream):
+        abi._keeper = None
         check(lib().gsdd_graph_end(stream_ptr(stream), C.byref(self.handle)))
 
     def launch(self, stream):
