@@ -27,6 +27,7 @@ EXPORTS = [
     "gsdd_philox_uniform", "gsdd_graph_begin", "gsdd_graph_end", "gsdd_graph_launch", "gsdd_graph_destroy",
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
     "gsdd_grad_sqnorm", "gsdd_grad_norm_finalize", "gsdd_adamw_ema_multi", "gsdd_swap_multi",
+    "gsdd_gif_histogram", "gsdd_gif_box_sums", "gsdd_gif_map", "gsdd_gif_median_cut", "gsdd_gif_encode_bound", "gsdd_gif_encode",
 ]
 
 _p = C.c_void_p
@@ -223,6 +224,14 @@ def lib():
         L.gsdd_clip_frame_patches.argtypes = [_p, _i, _i, _i, _i, _i, _i, _p, _p]
         L.gsdd_clip_vision_embed.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p]
         L.gsdd_clip_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]
+        L.gsdd_gif_histogram.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p]
+        L.gsdd_gif_box_sums.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p]
+        L.gsdd_gif_map.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]
+        L.gsdd_gif_median_cut.argtypes = [_p, _i, _p, C.POINTER(_i)]             # (host pointers)
+        L.gsdd_gif_encode_bound.argtypes = [_i, _i, _i]
+        L.gsdd_gif_encode_bound.restype = _i64
+        L.gsdd_gif_encode.argtypes = [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i64, C.POINTER(_i64)]
+        L.gsdd_gif_encode.restype = _i64
         L.gsdd_set_deterministic.argtypes = [_i]
         L.gsdd_cond_dropout.argtypes = [_p, _p, _i, _i, _i, C.c_float, C.c_uint64, _p, _i64, _p, _p, _p, _p]
         L.gsdd_cond_null_grad.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]

@@ -1,0 +1,97 @@
+"""Sampled clips as GIF files: colour quantisation on the device, median cut and the GIF89a / LZW writer in the library's host code.
+
+    clips (B, 3, T, H, W), ImageNet-normalised fp32 on the device (what the decoder returns)
+      -> gsdd_gif_histogram          15-bit colour histogram per group (a clip, or a frame with palette="frame")
+      -> one device-to-host copy     G x 128 KB
+      -> gsdd_gif_median_cut         (host, integer, deterministic) bin -> box table per group
+      -> gsdd_gif_box_sums           count and R, G, B sums per box; the palette is the rounded mean, formed with integer torch ops
+      -> gsdd_gif_map                nearest palette entry per pixel (optional ordered dither)
+      -> gsdd_gif_encode             (host) GIF89a file
+
+Every stage is integer arithmetic behind one fp32 step (the evaluator's uint8 rule), so the indices, the palette and the file's bytes
+are exactly reproducible; tests/gif_ref.py restates all of it in numpy.
+
+Synchronisation: quantize_clips synchronises ONCE, for the histogram the host's median cut reads (encode_gif / write_gifs copy the
+indices to the host as well, which is the point of them).  Rendering happens outside the sampling loop and must stay outside any
+captured graph: none of this can be recorded."""
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import GsddError
+
+
+def quantize_clips(clips, colors=256, palette="clip", dither=0):
+    """clips (B, 3, T, H, W) -> (indices (B, T, H, W) uint8 on the device, palette (G, 256, 3) uint8 on the device, n_colors (G,) int32
+    on the device).  G = B with palette="clip" (one palette per clip), B*T with palette="frame" (one per frame, group b*T + t).
+    colors: at most this many palette entries, 2 .. 256; entries behind n_colors[g] are zeros.  dither: ordered-dither amplitude
+    0 .. 64, 0 = off."""
+    if palette not in ("clip", "frame"):
+        raise GsddError(f'quantize_clips: palette is "clip" or "frame", got {palette!r}')
+    if not isinstance(colors, int) or isinstance(colors, bool) or not 2 <= colors <= 256:
+        raise GsddError(f"quantize_clips: colors is an integer in 2 .. 256, got {colors!r}")
+    if not isinstance(dither, int) or isinstance(dither, bool) or not 0 <= dither <= 64:
+        raise GsddError(f"quantize_clips: dither is an integer amplitude in 0 .. 64, got {dither!r}")
+    per_frame = palette == "frame"
+    clips = clips.contiguous() if torch.is_tensor(clips) else clips
+    hist = ops.gif_histogram(clips, per_frame)
+    hist_host = hist.cpu().numpy().view(np.uint32)                     # the one synchronisation
+    G = hist_host.shape[0]
+    box = np.empty((G, ops.GIF_BINS), dtype=np.uint8)
+    n = np.empty(G, dtype=np.int32)
+    for g in range(G):
+        box[g], n[g] = ops.gif_median_cut(hist_host[g], colors)
+    dev = clips.device
+    sums = ops.gif_box_sums(clips, torch.from_numpy(box).to(dev), per_frame).to(torch.int64) & 0xFFFFFFFF
+    count = sums[..., :1]
+    mean = (2 * sums[..., 1:] + count) // (2 * count).clamp(min=1)     # rounded mean; an empty box gives 0
+    pal4 = torch.zeros((G, 256, 4), dtype=torch.uint8, device=dev)
+    pal4[..., :3] = mean.to(torch.uint8)
+    n_dev = torch.from_numpy(n).to(dev)
+    indices = ops.gif_map(clips, pal4, n_dev, per_frame, dither)
+    return indices, pal4[..., :3].contiguous(), n_dev
+
+
+def delay_centiseconds(fps):
+    """round(100 / fps), the GIF's per-frame delay; an fps that rounds to 0 (or to more than 65535) is an error"""
+    if not fps > 0:
+        raise GsddError(f"fps must be positive, got {fps!r}")
+    delay = int(round(100.0 / fps))
+    if not 1 <= delay <= 65535:
+        raise GsddError(f"fps = {fps!r} gives a delay of {delay} centiseconds: a GIF holds 1 .. 65535")
+    return delay
+
+
+def encode_gif(indices, palette, n_colors, fps=5, loop=0):
+    """One clip -> the bytes of a GIF89a file.  indices (T, H, W) uint8; palette (256, 3) with n_colors an int or a 1-element tensor (a
+    global colour table) or palette (T, 256, 3) with n_colors (T,) (one local table per frame); tensors on any device, or numpy."""
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    idx, pal = host(indices), host(palette)
+    if pal.ndim == 2:
+        pal = pal[None]
+    n = np.asarray(host(n_colors), dtype=np.int32).reshape(-1)
+    data, _ = ops.gif_encode(idx, pal, n, delay_centiseconds(fps), loop)
+    return data
+
+
+def write_gifs(clips, paths, fps=5, loop=0, **quantize_kwargs):
+    """Quantise clips (B, 3, T, H, W) and write clip b to paths[b] (directories are created).  -> (indices, palette, n_colors) of
+    quantize_clips."""
+    paths = list(paths)
+    if not torch.is_tensor(clips) or clips.dim() != 5 or len(paths) != clips.shape[0]:
+        raise GsddError("write_gifs: one path per clip of (B, 3, T, H, W)")
+    delay_centiseconds(fps)
+    indices, palette, n_colors = quantize_clips(clips, **quantize_kwargs)
+    B, T = indices.shape[:2]
+    idx, pal, n = indices.cpu().numpy(), palette.cpu().numpy(), n_colors.cpu().numpy()
+    per_frame = quantize_kwargs.get("palette", "clip") == "frame"
+    for b, path in enumerate(paths):
+        p, c = (pal[b * T:(b + 1) * T], n[b * T:(b + 1) * T]) if per_frame else (pal[b:b + 1], n[b:b + 1])
+        data, _ = ops.gif_encode(idx[b], p, c, delay_centiseconds(fps), loop)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
+    return indices, palette, n_colors

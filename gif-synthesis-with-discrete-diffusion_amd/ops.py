@@ -644,6 +644,118 @@ def clip_attention(qkv, B, S, n_head, out, scale=None, stream=None):
     return out
 
 
+# ----------------------------------------------------------------------------- GIF export (gif.py)
+GIF_BINS = 32768
+
+
+def _gif_clips(what, clips, per_frame):
+    """-> (B, T, H, W, G) of ImageNet-normalised float32 clips (B, 3, T, H, W) on the device"""
+    if not torch.is_tensor(clips) or clips.dim() != 5 or clips.shape[1] != 3 or clips.dtype != torch.float32:
+        got = f"{clips.dtype} {tuple(clips.shape)}" if torch.is_tensor(clips) else type(clips).__name__
+        raise GsddError(f"{what}: clips must be float32 (B, 3, T, H, W), got {got}")
+    if not clips.is_cuda:
+        raise GsddError(f"{what}: clips must live on a ROCm device (no CPU fallback)")
+    B, _, T, H, W = clips.shape
+    return B, T, H, W, (B * T if per_frame else B)
+
+
+def _gif_words(what, t, shape, device):
+    """a 32-bit integer tensor of `shape` on `device` (torch has no arithmetic on uint32: the kernels' uint32 words travel as int32)"""
+    if t is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise GsddError(f"{what}: out must be int32 {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def gif_histogram(clips, per_frame=False, out=None, stream=None):
+    """-> hist (G, 32768) int32 holding uint32 counts: pixels per 15-bit colour bin of every group (gsdd_gif_histogram); G = B, or
+    B*T with per_frame."""
+    B, T, H, W, G = _gif_clips("gif_histogram", clips, per_frame)
+    out = _gif_words("gif_histogram", out, (G, GIF_BINS), clips.device)
+    check(lib().gsdd_gif_histogram(ptr(clips), B, T, H, W, int(bool(per_frame)), ptr(out), stream_ptr(stream)))
+    return out
+
+
+def gif_box_sums(clips, box_of_bin, per_frame=False, out=None, stream=None):
+    """box_of_bin (G, 32768) uint8 on the device -> sums (G, 256, 4) int32 holding uint32 (count, R, G, B sums) per box
+    (gsdd_gif_box_sums)."""
+    B, T, H, W, G = _gif_clips("gif_box_sums", clips, per_frame)
+    if not torch.is_tensor(box_of_bin) or box_of_bin.dtype != torch.uint8 or tuple(box_of_bin.shape) != (G, GIF_BINS):
+        raise GsddError(f"gif_box_sums: box_of_bin must be uint8 {(G, GIF_BINS)}")
+    out = _gif_words("gif_box_sums", out, (G, 256, 4), clips.device)
+    check(lib().gsdd_gif_box_sums(ptr(clips), B, T, H, W, int(bool(per_frame)), ptr(box_of_bin), ptr(out), stream_ptr(stream)))
+    return out
+
+
+def gif_map(clips, palette, n_colors, per_frame=False, dither=0, out=None, stream=None):
+    """palette (G, 256, 4) uint8 (R, G, B, unused), n_colors (G,) int32, both on the device -> indices (B, T, H, W) uint8: the nearest of
+    the first n_colors entries, lowest index on ties; dither: ordered-dither amplitude 0 .. 64 (gsdd_gif_map)."""
+    if not isinstance(dither, int) or isinstance(dither, bool) or not 0 <= dither <= 64:
+        raise GsddError(f"gif_map: dither is an integer amplitude in 0 .. 64, got {dither!r}")
+    B, T, H, W, G = _gif_clips("gif_map", clips, per_frame)
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (G, 256, 4):
+        raise GsddError(f"gif_map: palette must be uint8 {(G, 256, 4)}")
+    if not torch.is_tensor(n_colors) or n_colors.dtype != torch.int32 or tuple(n_colors.shape) != (G,):
+        raise GsddError(f"gif_map: n_colors must be int32 {(G,)}")
+    if out is None:
+        out = torch.empty((B, T, H, W), dtype=torch.uint8, device=clips.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, T, H, W):
+        raise GsddError(f"gif_map: out must be uint8 {(B, T, H, W)}")
+    check(lib().gsdd_gif_map(ptr(clips), B, T, H, W, int(bool(per_frame)), ptr(palette), ptr(n_colors), dither, ptr(out),
+                             stream_ptr(stream)))
+    return out
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def gif_median_cut(hist, colors=256):
+    """Host: hist (32768,) uint32 numpy -> (box_of_bin (32768,) uint8 numpy, number of boxes) (gsdd_gif_median_cut)."""
+    import numpy as np
+    if not isinstance(hist, np.ndarray) or hist.dtype != np.uint32 or hist.shape != (GIF_BINS,):
+        raise GsddError("gif_median_cut: hist must be a uint32 numpy array of 32768 bins")
+    if not isinstance(colors, int) or isinstance(colors, bool) or not 2 <= colors <= 256:
+        raise GsddError(f"gif_median_cut: colors is an integer in 2 .. 256, got {colors!r}")
+    hist = np.ascontiguousarray(hist)
+    box = np.empty(GIF_BINS, dtype=np.uint8)
+    n = C.c_int(0)
+    check(lib().gsdd_gif_median_cut(_np_ptr(hist), colors, _np_ptr(box), C.byref(n)))
+    return box, n.value
+
+
+def gif_encode(indices, palettes, n_colors, delay_cs, loop=0, cap=None):
+    """Host: indices (T, H, W) uint8, palettes (1 or T, 256, 3) uint8, n_colors (1 or T,) int32, all numpy -> (the GIF89a file as
+    bytes, the clear codes its LZW streams hold) (gsdd_gif_encode).  cap: the output buffer's size (default: gsdd_gif_encode_bound)."""
+    import numpy as np
+    if not isinstance(indices, np.ndarray) or indices.dtype != np.uint8 or indices.ndim != 3:
+        raise GsddError("gif_encode: indices must be a uint8 numpy array (T, H, W)")
+    T, H, W = indices.shape
+    if not isinstance(palettes, np.ndarray) or palettes.dtype != np.uint8 or palettes.ndim != 3 or palettes.shape[1:] != (256, 3) \
+            or palettes.shape[0] not in (1, T):
+        raise GsddError(f"gif_encode: palettes must be uint8 (1 or {T}, 256, 3)")
+    n_colors = np.ascontiguousarray(n_colors, dtype=np.int32).reshape(-1)
+    if n_colors.shape[0] != palettes.shape[0]:
+        raise GsddError("gif_encode: one colour count per palette")
+    indices, palettes = np.ascontiguousarray(indices), np.ascontiguousarray(palettes)
+    L = lib()
+    if cap is None:
+        cap = L.gsdd_gif_encode_bound(T, H, W)
+        if cap < 0:
+            check(int(cap))
+    buf = np.empty(cap + 1, dtype=np.uint8)
+    buf[cap] = 0xA5                                            # a guard byte behind the buffer
+    clears = C.c_int64(0)
+    n = L.gsdd_gif_encode(_np_ptr(indices), T, H, W, _np_ptr(palettes), _np_ptr(n_colors), palettes.shape[0], int(delay_cs), int(loop),
+                          _np_ptr(buf), cap, C.byref(clears))
+    if buf[cap] != 0xA5:
+        raise GsddError("gif_encode: the encoder wrote behind its buffer")
+    if n < 0:
+        check(int(n))
+    return buf[:n].tobytes(), clears.value
+
+
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):
     out = torch.empty((n_rows, n_cols), dtype=torch.float32, device=device)
     check(lib().gsdd_philox_uniform(seed, stream_id, row0, n_rows, n_cols, ptr(out), stream_ptr()))

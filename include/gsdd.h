@@ -29,6 +29,7 @@ extern "C" {
 #define GSDD_E_ARG (-1)     /* bad argument (null pointer, unsupported shape)  */
 #define GSDD_E_HIP (-2)     /* a HIP runtime call failed                        */
 #define GSDD_E_STATE (-3)   /* graph capture misuse                             */
+#define GSDD_E_CAP (-4)     /* a host output buffer is too small                */
 
 const char* gsdd_last_error(void);
 int gsdd_version(void);
@@ -702,6 +703,44 @@ int gsdd_clip_vision_embed(const float* patches, const float* class_emb, const f
  * instructions, v_mfma_f32_16x16x4_f32) with every query seeing every key: the keys of the last 16-key tile at positions >= S are
  * masked before the row maximum and the sum. */
 int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
+
+/* ------------------------------------------------------------------ GIF export of decoded clips (gif.py; csrc/gif.hip, csrc/gif_host.hpp)
+ * Colour quantisation on the device, median cut and the GIF89a / LZW writer on the host.  clips[B][3][T][H][W] f32 are the decoder's
+ * ImageNet-normalised clips.  Each pixel's uint8 channels are formed by the evaluator's rule: v = (x*std[c] + mean[c]) * 255 in fp32
+ * in that order, clamped to [0, 255] (NaN -> 0), truncated.  Everything after that step is integer arithmetic with integer atomics:
+ * every output below is exact and does not depend on the order the workgroups run in.  A "group" shares one palette: one clip
+ * (per_frame = 0, G = B) or one frame (per_frame = 1, G = B*T).  H, W <= 65535 and at most 2^24 pixels per group (so that no box sum
+ * overflows 32 bits), anything else is GSDD_E_ARG before any launch. */
+/* hist[G][32768] uint32 (zeroed by the call): pixels per bin, bin = (r>>3)<<10 | (g>>3)<<5 | (b>>3). */
+int gsdd_gif_histogram(const float* clips, int B, int T, int H, int W, int per_frame, uint32_t* hist, void* stream);
+/* box_of_bin[G][32768] uint8 (device, 16-byte aligned; gsdd_gif_median_cut's table) -> sums[G][256][4] uint32 (zeroed by the call): per
+ * box the pixel count and the sums of the R, G and B uint8 values.  A palette colour is the rounded mean (2*sum + count) / (2*count). */
+int gsdd_gif_box_sums(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* box_of_bin, uint32_t* sums,
+                      void* stream);
+/* palette[G][256][4] uint8 (R, G, B, unused; 4-byte aligned), n_colors[G] int32 (device) -> out[B][T][H][W] uint8: per pixel the index
+ * among entries 0 .. n_colors-1 with the smallest integer squared RGB distance, the lowest index on ties.  dither is an amplitude in
+ * 0 .. 64 (0 = off): every channel first gets the ordered-dither offset ((M[y&7][x&7] * dither) >> 6) - (dither >> 1) and is clamped
+ * to [0, 255]; M is the 8 x 8 Bayer matrix M(x,y) = sum_{i=0..2} ((((x>>i)^(y>>i))&1) << (2*(2-i)+1) | ((y>>i)&1) << (2*(2-i))). */
+int gsdd_gif_map(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* palette, const int32_t* n_colors, int dither,
+                 uint8_t* out, void* stream);
+/* The three entries below are HOST code on HOST pointers: nothing is launched, no stream. */
+/* Deterministic integer median cut of one histogram into at most `colors` (2 .. 256) boxes: start with one box of every occupied bin;
+ * split the box with the largest pixel count among those with more than one occupied bin (ties: lowest index) along its axis of largest
+ * extent in bin coordinates (ties R, G, B), after the first plane where twice the cumulative count reaches the box total (one plane
+ * earlier if that is the last plane); the lower part keeps the index, the upper part is appended; stop when no box can be split.
+ * box_of_bin[32768]: the box of each occupied bin, 255 for an unoccupied one; *n_boxes: the boxes made (0 for an empty histogram). */
+int gsdd_gif_median_cut(const uint32_t* hist, int colors, uint8_t* box_of_bin, int* n_boxes);
+/* A buffer size that always holds the file of T frames of H x W. */
+int64_t gsdd_gif_encode_bound(int T, int H, int W);
+/* GIF89a file of indices[T][H][W] -> out[0 .. return value).  palettes[n_palettes][256][3] uint8 with n_colors[n_palettes] in 1 .. 256:
+ * n_palettes = 1 is a global colour table, n_palettes = T one local table per frame; tables are padded with zeros to a power of two
+ * of at least 2 entries.  delay_cs: centiseconds per frame, loop: NETSCAPE2.0 loop count (0 = for ever), both 0 .. 65535.  One graphic
+ * control extension per frame (disposal 1), LZW with minimum code size max(2, bits), a clear code first and again whenever the table
+ * holds 4096 entries; no frame differencing, no transparency.  *clear_codes (may be NULL): the clear codes written, all frames.
+ * Returns the byte count; GSDD_E_ARG for bad arguments (an index outside its table included); GSDD_E_CAP when cap is too small --
+ * nothing is written at or behind out[cap] in any case. */
+int64_t gsdd_gif_encode(const uint8_t* indices, int T, int H, int W, const uint8_t* palettes, const int32_t* n_colors, int n_palettes,
+                        int delay_cs, int loop, uint8_t* out, int64_t cap, int64_t* clear_codes);
 
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */

@@ -82,9 +82,47 @@ class BaseModel(_Base):
     def test_epoch_end(self, outputs):
         return self.allsplit_epoch_end("test", outputs)
 
+    # ---- GIF export of sampled clips (gsdd_amd.gif); off unless `render_dir` is set
+    render_dir, render_fps, render_max = None, 5, 16
+
+    def _render_setup(self, render_dir, render_fps, render_max):
+        self.render_dir = str(render_dir) if render_dir not in (None, "", "__None__") else None
+        self.render_fps, self.render_max = render_fps, int(render_max)
+        self._rendered = 0                                       # clips written by the test split so far
+
+    def _write_gifs(self, clips, directory, names, captions):
+        """clips (N, 3, T, H, W) on the device -> <directory>/<name> each, and one `<name>\\t<caption>` line each in captions.txt"""
+        import os
+        from gsdd_amd.gif import write_gifs
+        write_gifs(clips.detach().float(), [os.path.join(directory, n) for n in names], fps=self.render_fps)
+        with open(os.path.join(directory, "captions.txt"), "a") as f:
+            for n, c in zip(names, captions):
+                f.write(f"{n}\t{' '.join(str(c).split())}\n")
+
+    def render_test_batch(self, batch, batch_idx, sampled=None):
+        """Test split with `render_dir` set: the batch's sampled clips as <render_dir>/test/<batch_idx>_<i>.gif, at most `render_max`
+        in all (`render_dir` alone switches this on: the shipped configs keep `render_animations`, the validation item's switch,
+        off).  `sampled`: what do_evaluation has already sampled for this batch (reused); None = the sample is made here."""
+        if not self.render_dir or self._rendered >= self.render_max:
+            return
+        import os
+        if sampled is None:
+            was_training = self.generator.training
+            self.generator.eval()
+            with torch.no_grad():
+                sampled = self.sample_generator_step(batch)
+            self.generator.train(was_training)
+        clips = sampled["pred_data"][:self.render_max - self._rendered]
+        text = batch.get("text") if isinstance(batch.get("text"), (list, tuple)) else [""] * clips.shape[0]
+        names = [f"{batch_idx}_{i}.gif" for i in range(clips.shape[0])]
+        self._write_gifs(clips, os.path.join(self.render_dir, "test"), names, text[:clips.shape[0]])
+        self._rendered += clips.shape[0]
+
     def render_sample_results(self):
-        """The reference writes .mp4 files through its OpenGL renderer (multistage_text_motion_model.py:254-281); rendering is
-        out of scope.  The sampled clips of one validation item are kept on `self.last_sample`."""
+        """The reference writes animations of one validation item through matplotlib and ffmpeg (multistage_text_motion_model.py:
+        254-281).  Here the sampled clips of that item are kept on `self.last_sample`, and with `render_dir` set they are written
+        as <render_dir>/epoch_<n>/pred.gif next to the item itself as gt.gif (gsdd_amd.gif: quantiser on the device, GIF89a writer
+        in the library).  Rendering runs outside the sampling loop and outside any captured graph; it synchronises."""
         if not getattr(self, "render_animations", False) or self.trainer is None:
             return
         loader = self.trainer.datamodule.val_dataloader()
@@ -97,6 +135,13 @@ class BaseModel(_Base):
         with torch.no_grad():
             self.last_sample = self.sample_generator_step(one)
         self.generator.train(was_training)
+        if self.render_dir:
+            import os
+            pred = self.last_sample["pred_data"]
+            caption = one["text"][0] if isinstance(one.get("text"), (list, tuple)) and one["text"] else ""
+            directory = os.path.join(self.render_dir, f"epoch_{self.current_epoch}")
+            self._write_gifs(pred[:1], directory, ["pred.gif"], [caption])
+            self._write_gifs(one["video"][:1].to(pred.device), directory, ["gt.gif"], [caption])
 
     # ---- state that is not in state_dict but decides the next training step (exact resume)
     def _diffusion_models(self):

@@ -51,8 +51,9 @@ class MultistageTextMotionModel(BaseModel):
     def __init__(self, generator, autoencoder, generator_losses=None, autoencoder_losses=None, length_estimator_losses=None,
                  checkpoint_paths=None, evaluator=None, freeze_models_dict=None, lr_args={}, render_animations=True,
                  do_evaluation=False, devices="cpu", autoencoder_train_mode=False, step_in_eval_splits=False, native_step=False,
-                 native_optim=None, sample_with_ema=True, use_ema=False, **kwargs):
+                 native_optim=None, sample_with_ema=True, use_ema=False, render_dir=None, render_fps=5, render_max=16, **kwargs):
         super().__init__()
+        self._render_setup(render_dir, render_fps, render_max)
         self.gpu_device = devices if devices == "cpu" else "cuda:" + str(devices[0])
         self.generator = instantiate(generator, device=self.gpu_device, _recursive_=False) if isinstance(generator, dict) else generator
         self.autoencoder = instantiate(autoencoder, device=self.gpu_device, _recursive_=False) \
@@ -146,9 +147,12 @@ class MultistageTextMotionModel(BaseModel):
         optimizers = self.optimizers()
         optimizers = list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
         outputs = self.generator_step(batch)
+        eval_outputs = None
         if self.do_evaluation and split != "train" and len(batch["length"]) != 1 and self.current_epoch % 5 == 0:
             eval_outputs = self.sample_generator_step(batch)
             self.evaluator.push_vals(batch, batch_idx, eval_outputs["pred_data"])
+        if split == "test":
+            self.render_test_batch(batch, batch_idx, eval_outputs)      # (nothing unless render_dir is set)
         # (the reference zips the optimisers into this loop, :189; outside fit() Lightning hands back no optimisers, the zip is
         # empty and its test split accumulates nothing -- here the losses are accumulated in every split)
         for i, (loss, key) in enumerate(zip(self.losses, [k + "_loss" for k in self.keys])):

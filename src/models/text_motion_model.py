@@ -20,8 +20,9 @@ def _make_losses(cfg):
 
 class TextMotionModel(BaseModel):
     def __init__(self, generator, losses=None, checkpoint_paths=None, evaluator=None, lr_args={}, render_animations=True,
-                 do_evaluation=False, devices="cpu", **kwargs):
+                 do_evaluation=False, devices="cpu", render_dir=None, render_fps=5, render_max=16, **kwargs):
         super().__init__()
+        self._render_setup(render_dir, render_fps, render_max)
         self.gpu_device = devices if devices == "cpu" else "cuda:" + str(devices[0])
         self.generator = instantiate(generator, device=self.gpu_device, _recursive_=False) \
             if isinstance(generator, dict) else generator
@@ -44,9 +45,12 @@ class TextMotionModel(BaseModel):
 
     def allsplit_step(self, split, batch, batch_idx):                   # :93-107
         outputs = self.generator_step(batch)
+        eval_outputs = None
         if self.do_evaluation and split != "train" and len(batch["length"]) != 1:
             eval_outputs = self.sample_generator_step(batch)
             self.evaluator.push_vals(batch, batch_idx, eval_outputs["pred_data"])
+        if split == "test":
+            self.render_test_batch(batch, batch_idx, eval_outputs)      # (nothing unless render_dir is set)
         loss = self.losses[split].update(outputs)
         ex = self._extra[split]
         ex["recon"] = ex["recon"] + outputs["losses"]["recon_loss"].detach()

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Time of the GIF export (gsdd_amd.gif) on 16 clips of 16 frames of 128 x 128 -- ImageNet-normalised floats (16, 3, 16, 128, 128) as
+the decoder returns them; a moving colour ramp with sigma-5 noise, so that neighbouring pixels share bins as video does -- per stage:
+the three kernels (histogram, box sums, map without and with dither) with HIP events around each call, the whole quantize_clips (its
+device-to-host copy, the host's median cuts and the palette included) and the host's encode of the 16 files by the wall clock.
+Beside them, in the same run, the host baseline the export replaces: PIL's quantize(MEDIANCUT) per frame and save of the same clips
+from their uint8 frames (the copy to the host not counted).  Warm-up first, the cases in alternating rounds (a drift of the clocks
+hits all alike), the median over the rounds reported with the spread; a round that takes longer than the time limit ends the run with
+an error instead of hanging on.  usage: bench_gif.py [out.csv]"""
+import io
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from PIL import Image
+
+from gsdd_amd import gif, ops
+
+ROUNDS, WARMUP, ITERS, STEP_LIMIT_S = 7, 2, 5, 120.0
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def timed(fn, iters, events=True):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.monotonic()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    wall = time.monotonic() - t0
+    if wall > STEP_LIMIT_S:
+        raise SystemExit(f"bench_gif: {iters} calls took more than {STEP_LIMIT_S:.0f} s; giving up")
+    return (e0.elapsed_time(e1) if events else wall * 1e3) / iters
+
+
+def make_levels(B, T, HW):
+    g = torch.Generator().manual_seed(0)
+    t, y, x = torch.meshgrid(torch.arange(T), torch.arange(HW), torch.arange(HW), indexing="ij")
+    base = torch.stack([(2 * x + 10 * t) % 256, (2 * y) % 256, ((x + y) + 30 * t) % 256], dim=-1).float()      # (T, H, W, 3)
+    shift = torch.arange(B).view(B, 1, 1, 1, 1) * 9.0
+    v = (base[None] + shift) % 256 + torch.randn((B, T, HW, HW, 3), generator=g) * 5.0
+    return v.round().clamp(0, 255).to(torch.uint8)
+
+
+def main():
+    B, T, HW = 16, 16, 128
+    levels = make_levels(B, T, HW)
+    mean, std = torch.tensor(MEAN, dtype=torch.float64), torch.tensor(STD, dtype=torch.float64)
+    clips = (((levels.double() + 0.5) / 255 - mean) / std).permute(0, 4, 1, 2, 3).float().contiguous().cuda()
+    idx, pal, n = gif.quantize_clips(clips)
+    hist = ops.gif_histogram(clips)
+    box = torch.from_numpy(np.stack([ops.gif_median_cut(h, 256)[0] for h in hist.cpu().numpy().view(np.uint32)])).cuda()
+    pal4 = torch.cat([pal, torch.zeros_like(pal[..., :1])], dim=-1).contiguous()
+    sums = torch.empty((B, 256, 4), dtype=torch.int32, device="cuda")
+    out = torch.empty((B, T, HW, HW), dtype=torch.uint8, device="cuda")
+    idx_h, pal_h, n_h = idx.cpu().numpy(), pal.cpu().numpy(), n.cpu().numpy()
+    frames_h = levels.numpy()
+
+    def encode_all():
+        return [ops.gif_encode(idx_h[b], pal_h[b:b + 1], n_h[b:b + 1], 20, 0)[0] for b in range(B)]
+
+    def pil_all():
+        sizes = []
+        for b in range(B):
+            fr = [Image.fromarray(f, "RGB").quantize(256, method=Image.Quantize.MEDIANCUT, dither=Image.Dither.NONE) for f in frames_h[b]]
+            buf = io.BytesIO()
+            fr[0].save(buf, format="GIF", save_all=True, append_images=fr[1:], duration=200, loop=0)
+            sizes.append(buf.tell())
+        return sizes
+
+    cases = [("histogram", lambda: ops.gif_histogram(clips, out=hist), True),
+             ("box_sums", lambda: ops.gif_box_sums(clips, box, out=sums), True),
+             ("map", lambda: ops.gif_map(clips, pal4, n, out=out), True),
+             ("map_dither32", lambda: ops.gif_map(clips, pal4, n, dither=32, out=out), True),
+             ("quantize_clips_wall", lambda: gif.quantize_clips(clips), False),
+             ("encode_16_files_host_wall", encode_all, False),
+             ("pil_mediancut_save_16_files_host_wall", pil_all, False)]
+    for _, fn, ev in cases:
+        timed(fn, WARMUP, ev)
+    ms = {name: [] for name, _, _ in cases}
+    for _ in range(ROUNDS):
+        for name, fn, ev in cases:
+            ms[name].append(timed(fn, ITERS if ev else 1, ev))
+    ours, theirs = sum(len(d) for d in encode_all()), sum(pil_all())
+    lines = ["case,clips,frames,rounds,iters_per_round,ms_per_call_median,ms_per_call_min,ms_per_call_max"]
+    for name, _, ev in cases:
+        v = ms[name]
+        lines.append(f"{name},{B},{B * T},{ROUNDS},{ITERS if ev else 1},{statistics.median(v):.4f},{min(v):.4f},{max(v):.4f}")
+    lines.append(f"# bytes of the 16 files: {ours} (one palette per clip, no frame differencing) vs PIL {theirs} (one palette per frame, frame differencing)")
+    print("\n".join(lines))
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -6,6 +6,7 @@
 //   (3) null pointers, bad sizes, unknown variant / mode values: GSDD_E_ARG, nothing launched;
 //   (4) a failing hipFuncSetAttribute: reported as GSDD_E_HIP by that call and retried (successfully) by the next one.
 // Exit code 0 = all expectations met and no sanitizer report.  Test infrastructure only.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -609,6 +610,118 @@ int main() {
         EXPECT(gsdd_swap_multi(table, nb, st), GSDD_OK, true);
         EXPECT(gsdd_swap_multi(nullptr, nb, st), GSDD_E_ARG, false);
         for (int bad : {0, -1}) EXPECT(gsdd_swap_multi(table, bad, st), GSDD_E_ARG, false);
+    }
+
+    // ---------------------------------------------------------------- GIF export: the device entries' checks; median cut and encoder RUN here
+    {
+        const int Bv = 16, Tv = 16, Hh = 128;
+        float* clips = devp((size_t)Bv * 3 * Tv * Hh * Hh * 4);
+        uint32_t *hist = devp<uint32_t>((size_t)Bv * Tv * 32768 * 4), *sums = devp<uint32_t>((size_t)Bv * Tv * 1024 * 4);
+        uint8_t *box = devp<uint8_t>((size_t)Bv * Tv * 32768), *pal = devp<uint8_t>((size_t)Bv * Tv * 1024), *idx = devp<uint8_t>((size_t)Bv * Tv * Hh * Hh);
+        int32_t* ncol = devp<int32_t>((size_t)Bv * Tv * 4);
+        for (int pf = 0; pf <= 1; ++pf) {
+            EXPECT(gsdd_gif_histogram(clips, Bv, Tv, Hh, Hh, pf, hist, st), GSDD_OK, true);
+            EXPECT(gsdd_gif_box_sums(clips, Bv, Tv, Hh, Hh, pf, box, sums, st), GSDD_OK, true);
+            for (int d : {0, 1, 64}) EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, pf, pal, ncol, d, idx, st), GSDD_OK, true);
+        }
+        EXPECT(gsdd_gif_histogram(clips, 1, 1, 1, 1, 0, hist, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_histogram(clips, 1, 1, 4096, 4096, 1, hist, st), GSDD_OK, true);                     // 2^24 pixels: the largest group
+        EXPECT(gsdd_gif_histogram(clips, 1, 2, 4096, 4096, 0, hist, st), GSDD_E_ARG, false);                 // 2^25 pixels in a clip
+        EXPECT(gsdd_gif_histogram(clips, 1, 2, 4096, 4096, 1, hist, st), GSDD_OK, true);                     // ... but 2^24 in a frame
+        EXPECT(gsdd_gif_histogram(clips, 1, 1, 1, 65535, 0, hist, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_histogram(clips, 1, 1, 1, 65536, 0, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, 1, 1, 65536, 1, 0, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, 0, Tv, Hh, Hh, 0, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, Bv, -1, Hh, Hh, 0, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, Bv, Tv, Hh, Hh, 2, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(nullptr, Bv, Tv, Hh, Hh, 0, hist, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, Bv, Tv, Hh, Hh, 0, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_histogram(clips, 1 << 30, 4, 1, 1, 1, hist, st), GSDD_E_ARG, false);                 // 2^32 frames
+        EXPECT(gsdd_gif_histogram(clips, 1 << 21, 1, 4096, 4096, 0, hist, st), GSDD_E_ARG, false);           // grid of 2^31
+        EXPECT(gsdd_gif_box_sums(clips, Bv, Tv, Hh, Hh, 0, nullptr, sums, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_box_sums(clips, Bv, Tv, Hh, Hh, 0, box, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_box_sums(clips, Bv, Tv, Hh, Hh, 0, box + 1, sums, st), GSDD_E_ARG, false);           // misaligned table
+        EXPECT(gsdd_gif_box_sums(clips, Bv, Tv, 0, Hh, 0, box, sums, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_box_sums(clips, 1, 2, 4096, 4096, 0, box, sums, st), GSDD_E_ARG, false);
+        for (int bad : {-1, 65, 1000}) EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, bad, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, nullptr, ncol, 0, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal, nullptr, 0, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal + 2, ncol, 0, idx, st), GSDD_E_ARG, false);        // misaligned palette
+        EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, 70000, 0, pal, ncol, 0, idx, st), GSDD_E_ARG, false);
+
+        // median cut on real host memory: a smooth ramp, every bin, one bin, nothing
+        std::vector<uint32_t> h(32768, 0u);
+        std::vector<uint8_t> bx(32768, 7);
+        int nb = -1;
+        for (int i = 0; i < 32768; ++i) h[i] = (uint32_t)((i * 2654435761u) >> 28);
+        for (int colors : {2, 16, 255, 256}) {
+            EXPECT(gsdd_gif_median_cut(h.data(), colors, bx.data(), &nb), GSDD_OK, false);
+            if (nb != colors) { std::fprintf(stderr, "FAIL median cut made %d boxes of %d\n", nb, colors); ++g_failed; }
+        }
+        std::fill(h.begin(), h.end(), 0xFFFFFFFFu);                                                          // 2^47 pixels: 64-bit counts
+        EXPECT(gsdd_gif_median_cut(h.data(), 256, bx.data(), &nb), GSDD_OK, false);
+        std::fill(h.begin(), h.end(), 0u);
+        EXPECT(gsdd_gif_median_cut(h.data(), 256, bx.data(), &nb), GSDD_OK, false);
+        if (nb != 0 || bx[0] != 255) { std::fprintf(stderr, "FAIL median cut of an empty histogram\n"); ++g_failed; }
+        h[32767] = 5u;
+        EXPECT(gsdd_gif_median_cut(h.data(), 2, bx.data(), &nb), GSDD_OK, false);
+        if (nb != 1 || bx[32767] != 0) { std::fprintf(stderr, "FAIL median cut of one bin\n"); ++g_failed; }
+        for (int bad : {-1, 0, 1, 257}) EXPECT(gsdd_gif_median_cut(h.data(), bad, bx.data(), &nb), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_median_cut(nullptr, 16, bx.data(), &nb), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_median_cut(h.data(), 16, nullptr, &nb), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_median_cut(h.data(), 16, bx.data(), nullptr), GSDD_E_ARG, false);
+
+        // encoder: exact-size heap buffers, so that one byte too many is a sanitizer report
+        const int Te = 3, He = 96, We = 96;
+        std::vector<uint8_t> px((size_t)Te * He * We), table((size_t)Te * 768);
+        for (size_t i = 0; i < table.size(); ++i) table[i] = (uint8_t)(i * 7);
+        uint32_t lcg = 1u;
+        auto fill = [&](int n) { for (auto& v : px) { lcg = lcg * 1664525u + 1013904223u; v = (uint8_t)((lcg >> 24) % (uint32_t)n); } };
+        auto encode_exact = [&](const int32_t* nc, int npal, int T2) -> int64_t {
+            std::vector<uint8_t> big((size_t)gsdd_gif_encode_bound(T2, He, We));
+            int64_t clears = -1;
+            const int64_t n = gsdd_gif_encode(px.data(), T2, He, We, table.data(), nc, npal, 20, 0, big.data(), (int64_t)big.size(), &clears);
+            ++g_checked;
+            if (n <= 0 || clears < T2) { std::fprintf(stderr, "FAIL gsdd_gif_encode -> %lld [%s]\n", (long long)n, gsdd_last_error()); ++g_failed; return n; }
+            std::vector<uint8_t> exact((size_t)n), shorter((size_t)n - 1);
+            ++g_checked;
+            if (gsdd_gif_encode(px.data(), T2, He, We, table.data(), nc, npal, 20, 0, exact.data(), n, nullptr) != n ||
+                std::memcmp(exact.data(), big.data(), (size_t)n) != 0) { std::fprintf(stderr, "FAIL gsdd_gif_encode at the exact size\n"); ++g_failed; }
+            ++g_checked;
+            if (gsdd_gif_encode(px.data(), T2, He, We, table.data(), nc, npal, 20, 0, shorter.data(), n - 1, nullptr) != GSDD_E_CAP) {
+                std::fprintf(stderr, "FAIL gsdd_gif_encode one byte short\n"); ++g_failed; }
+            ++g_checked;
+            if (gsdd_gif_encode(px.data(), T2, He, We, table.data(), nc, npal, 20, 0, shorter.data(), 0, nullptr) != GSDD_E_CAP) {
+                std::fprintf(stderr, "FAIL gsdd_gif_encode into nothing\n"); ++g_failed; }
+            return n;
+        };
+        const int32_t one_colour[1] = {1}, full[1] = {256}, mixed[3] = {2, 5, 256};
+        fill(1);
+        encode_exact(one_colour, 1, Te);                                                                     // a 1-colour table
+        fill(256);
+        encode_exact(full, 1, Te);                                                                           // 256 colours: mid-stream clears
+        encode_exact(full, 1, 1);
+        fill(2);
+        encode_exact(mixed, 3, Te);                                                                          // local tables
+        std::vector<uint8_t> out((size_t)gsdd_gif_encode_bound(Te, He, We));
+        const int64_t cap = (int64_t)out.size();
+        fill(256);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), mixed, 3, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);  // index >= n_colors
+        const int32_t zero[1] = {0}, many[1] = {257};
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), zero, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), many, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), mixed, 2, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);   // 2 palettes, 3 frames
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, 1, -1, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, 1, 20, 65536, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), 0, He, We, table.data(), full, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, 1, 20, 0, out.data(), -1, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(nullptr, Te, He, We, table.data(), full, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, nullptr, full, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), nullptr, 1, 20, 0, out.data(), cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, 1, 20, 0, nullptr, cap, nullptr), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode_bound(0, He, We), GSDD_E_ARG, false);
+        EXPECT((int)gsdd_gif_encode_bound(1, 65536, We), GSDD_E_ARG, false);
     }
 
     // ---------------------------------------------------------------- graph capture misuse, events

@@ -2,7 +2,8 @@
 """Registers, scratch and occupancy of the sampler's kernels as hipcc reports them for gfx950 (-Rpass-analysis=kernel-resource-usage).
 Cross-compiles the device code of the sampler's source files with build.sh's flags (no GPU needed) and writes one CSV row per kernel
 instantiation.  Scratch is what a kernel spills: every byte per lane is a store and a reload through the memory hierarchy.
-usage: kernel_resources.py [out.csv]   (default profiles/r5_kernel_resources.csv; '-' prints to stdout)"""
+usage: kernel_resources.py [out.csv [source.hip ...]]   (default profiles/r5_kernel_resources.csv; '-' prints to stdout; sources default
+to the sampler's, e.g. `kernel_resources.py profiles/rQ_gif_kernel_resources.csv gif.hip`)"""
 import concurrent.futures
 import csv
 import io
@@ -67,7 +68,7 @@ def collect(sources=SOURCES):
 
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "profiles", "r5_kernel_resources.csv")
-    rows = collect()
+    rows = collect(sys.argv[2:] or SOURCES)
     cols = ["source", "kernel", "vgprs", "agprs", "sgprs", "scratch_bytes_per_lane", "vgpr_spill", "occupancy_waves_per_simd",
             "static_lds_bytes"]
     buf = io.StringIO()
