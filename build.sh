@@ -10,7 +10,7 @@ OBJS=""
 PIDS=""
 for f in $SRC/*.hip; do
   o="build/$(basename "${f%.hip}").o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$SRC/common.hpp" -nt "$o" ] || [ "$SRC/d3pm_rows.hpp" -nt "$o" ] || [ include/gsdd.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ -n "$(find "$SRC" -name '*.hpp' -newer "$o")" ] || [ include/gsdd.h -nt "$o" ]; then
     echo "hipcc $f"
     rm -f "$o"                      # a failed compile must not leave a stale object behind for the link
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form -Wall -Wno-unused-function \

@@ -11,9 +11,12 @@
 Every stage is integer arithmetic behind one fp32 step (the evaluator's uint8 rule), so the indices, the palette and the file's bytes
 are exactly reproducible; tests/gif_ref.py restates all of it in numpy.
 
+The way back is probe_gif / read_gif at the end of this file: a GIF file -> uint8 frames (T, H, W, 3) on the device.
+
 Synchronisation: quantize_clips synchronises ONCE, for the histogram the host's median cut reads (encode_gif / write_gifs copy the
 indices to the host as well, which is the point of them).  Rendering happens outside the sampling loop and must stay outside any
 captured graph: none of this can be recorded."""
+import contextlib
 import os
 
 import numpy as np
@@ -95,3 +98,58 @@ def write_gifs(clips, paths, fps=5, loop=0, **quantize_kwargs):
         with open(path, "wb") as f:
             f.write(data)
     return indices, palette, n_colors
+
+
+# ----------------------------------------------------------------------------- reading
+# The way back: the host walks the file and decodes the LZW streams (gsdd_gif_decode, the serial part), the device composites the
+# frame rectangles onto the canvas -- transparency, disposal -- and expands the indices to RGB (gsdd_gif_compose).  What crosses to
+# the device is one byte per DRAWN pixel and the small tables, not three bytes per canvas pixel per frame.
+def _gif_file(what, path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview, np.ndarray)):
+        return path_or_bytes, "<bytes>"
+    try:
+        with open(path_or_bytes, "rb") as f:
+            return f.read(), os.fspath(path_or_bytes)
+    except (OSError, TypeError) as e:
+        raise GsddError(f"{what}: cannot read {path_or_bytes!r}: {e}")
+
+
+def probe_gif(path_or_bytes):
+    """A GIF's block structure, without decoding it -> dict of width, height, frames, palettes (colour tables), raster_bytes (the sum
+    of the frame rectangles' areas), loop (-1: no loop extension), global_table, version (87 / 89)."""
+    data, name = _gif_file("probe_gif", path_or_bytes)
+    try:
+        return ops.gif_probe(data)
+    except GsddError as e:
+        raise GsddError(f"probe_gif: {name}: {e}")
+
+
+def read_gif(path_or_bytes, device, frames=None, matte=(0, 0, 0), stream=None):
+    """-> (uint8 (T, H, W, 3) on the device -- what data.preprocess takes --, the delays of the returned frames in centiseconds, info
+    of probe_gif).  frames: the frame numbers to return, non-decreasing, repeats allowed (a short clip padded with its last frame);
+    default: every frame.  matte: the (R, G, B) of pixels nothing has drawn yet and of disposal 2.  A host decode, one host-to-device
+    copy each of the index rasters and of the tables, one launch; no device-to-host copy, no synchronisation."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise GsddError("read_gif: the compositor runs on a ROCm device (no CPU fallback)")
+    data, name = _gif_file("read_gif", path_or_bytes)
+    try:
+        table, delays, palettes, raster, info = ops.gif_decode(data)
+    except GsddError as e:
+        raise GsddError(f"read_gif: {name}: {e}")
+    F = info["frames"]
+    try:
+        select = np.arange(F, dtype=np.int32) if frames is None else np.asarray(list(frames), dtype=np.int64).astype(np.int32)
+    except (TypeError, ValueError, OverflowError):
+        raise GsddError(f"read_gif: frames is a list of frame numbers, got {frames!r}")
+    if select.ndim != 1 or select.size < 1 or select.min() < 0 or select.max() >= F or np.any(np.diff(select) < 0):
+        raise GsddError(f"read_gif: {name}: frames must be a non-empty non-decreasing list within 0 .. {F - 1}, got {frames!r}")
+    # the tables travel as one buffer: palettes | frame table | select (each a multiple of four bytes)
+    parts = (palettes.reshape(-1), table.reshape(-1).view(np.uint8), select.view(np.uint8))
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        raster_dev = torch.from_numpy(raster).to(device)
+        tables_dev = torch.from_numpy(np.concatenate(parts)).to(device)
+    a, b = parts[0].size, parts[0].size + parts[1].size
+    out = ops.gif_compose(raster_dev, tables_dev[a:b].view(torch.int32).view(F, 8), tables_dev[:a].view(-1, 256, 4), info["width"],
+                          info["height"], select, matte, stream=stream, select_dev=tables_dev[b:].view(torch.int32))
+    return out, [int(delays[f]) for f in select], info

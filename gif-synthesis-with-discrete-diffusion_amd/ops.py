@@ -756,6 +756,94 @@ def gif_encode(indices, palettes, n_colors, delay_cs, loop=0, cap=None):
     return buf[:n].tobytes(), clears.value
 
 
+# ----------------------------------------------------------------------------- GIF import (gif.py)
+GIF_INFO = ("width", "height", "frames", "palettes", "raster_bytes", "loop", "global_table", "version")
+
+
+def _gif_bytes(what, data):
+    import numpy as np
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(data, dtype=np.uint8)
+    if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.ndim != 1:
+        raise GsddError(f"{what}: the file is bytes or a one-dimensional uint8 numpy array")
+    return np.ascontiguousarray(data)
+
+
+def gif_probe(data):
+    """Host: the bytes of a GIF -> dict of width, height, frames, palettes (colour tables, global + local), raster_bytes (the sum of
+    w*h over the frames), loop (-1: none), global_table (0 / 1), version (87 / 89); block structure only, no LZW (gsdd_gif_probe)."""
+    import numpy as np
+    data = _gif_bytes("gif_probe", data)
+    info = np.zeros(8, dtype=np.int64)
+    check(lib().gsdd_gif_probe(_np_ptr(data), data.size, _np_ptr(info)))
+    return dict(zip(GIF_INFO, (int(v) for v in info)))
+
+
+def gif_decode(data, raster_cap=None):
+    """Host: the bytes of a GIF -> (frames (F, 8) int32 [x, y, w, h, raster offset, palette row, transparent index or -1, disposal],
+    delays (F,) int32 centiseconds, palettes (P, 256, 4) uint8, raster (raster_bytes,) uint8 in display order, info of gif_probe)
+    (gsdd_gif_decode).  raster_cap: the raster buffer's size (default: the probe's raster_bytes)."""
+    import numpy as np
+    data = _gif_bytes("gif_decode", data)
+    info = gif_probe(data)
+    F, P = info["frames"], info["palettes"]
+    cap = info["raster_bytes"] if raster_cap is None else int(raster_cap)
+    if cap < 0:
+        raise GsddError("gif_decode: raster_cap is not negative")
+    frames = np.zeros((F, 8), dtype=np.int32)
+    delays = np.zeros(F, dtype=np.int32)
+    palettes = np.zeros((P, 256, 4), dtype=np.uint8)
+    raster = np.zeros(cap + 1, dtype=np.uint8)
+    raster[cap] = 0xA5                                         # a guard byte behind the buffer
+    rc = lib().gsdd_gif_decode(_np_ptr(data), data.size, _np_ptr(frames), _np_ptr(delays), _np_ptr(palettes), _np_ptr(raster), cap)
+    if raster[cap] != 0xA5:
+        raise GsddError("gif_decode: the decoder wrote behind its buffer")
+    check(rc)
+    return frames, delays, palettes, raster[:cap], info
+
+
+def gif_compose(raster, frames, palettes, W, H, select, matte=(0, 0, 0), out=None, stream=None, select_dev=None):
+    """raster uint8 (n,), frames int32 (F, 8), palettes uint8 (P, 256, 4) on the device as gif_decode returned them; select: a list of
+    frame numbers, non-decreasing in 0 .. F-1 -> out (T_out, H, W, 3) uint8: the composited canvas behind each selected frame
+    (gsdd_gif_compose).  select_dev: `select` as an int32 tensor on the device, if the caller has copied it already (else it is
+    copied here).  One launch, no synchronisation."""
+    import contextlib
+
+    import numpy as np
+    if not (torch.is_tensor(raster) and raster.dtype == torch.uint8 and raster.dim() == 1):
+        raise GsddError("gif_compose: raster must be a one-dimensional uint8 tensor")
+    if not (torch.is_tensor(frames) and frames.dtype == torch.int32 and frames.dim() == 2 and frames.shape[1] == 8):
+        raise GsddError("gif_compose: frames must be int32 (F, 8)")
+    if not (torch.is_tensor(palettes) and palettes.dtype == torch.uint8 and palettes.dim() == 3 and tuple(palettes.shape[1:]) == (256, 4)):
+        raise GsddError("gif_compose: palettes must be uint8 (P, 256, 4)")
+    if not raster.is_cuda:
+        raise GsddError("gif_compose: the tables must live on a ROCm device (no CPU fallback)")
+    try:
+        sel = np.ascontiguousarray(np.asarray(select, dtype=np.int64).reshape(-1).astype(np.int32))
+        matte = tuple(int(c) for c in matte)
+    except (TypeError, ValueError, OverflowError):
+        raise GsddError("gif_compose: select is a list of frame numbers, matte an (R, G, B) of 0 .. 255")
+    if len(matte) != 3 or not all(0 <= c <= 255 for c in matte):
+        raise GsddError(f"gif_compose: matte is an (R, G, B) of 0 .. 255, got {matte!r}")
+    T_out, W, H = int(sel.size), int(W), int(H)
+    shape = (T_out, H, W, 3)
+    if out is None:
+        if T_out < 1 or not (1 <= W <= 65535 and 1 <= H <= 65535):
+            shape = (1, 1, 1, 3)                               # (the library reports the bad sizes)
+        out = torch.empty(shape, dtype=torch.uint8, device=raster.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape:
+        raise GsddError(f"gif_compose: out must be uint8 {shape}")
+    if select_dev is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            select_dev = torch.from_numpy(sel if T_out else np.zeros(1, dtype=np.int32)).to(raster.device)
+    elif not (torch.is_tensor(select_dev) and select_dev.dtype == torch.int32 and tuple(select_dev.shape) == (T_out,)):
+        raise GsddError(f"gif_compose: select_dev must be int32 {(T_out,)}")
+    sel_dev = select_dev
+    check(lib().gsdd_gif_compose(ptr(raster), ptr(frames), ptr(palettes), frames.shape[0], W, H, ptr(sel_dev), _np_ptr(sel), T_out,
+                                 (matte[0] << 16) | (matte[1] << 8) | matte[2], ptr(out), stream_ptr(stream)))
+    return out
+
+
 def philox_uniform(seed, stream_id, n_rows, n_cols, device, row0=0):
     out = torch.empty((n_rows, n_cols), dtype=torch.float32, device=device)
     check(lib().gsdd_philox_uniform(seed, stream_id, row0, n_rows, n_cols, ptr(out), stream_ptr()))

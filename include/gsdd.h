@@ -742,6 +742,40 @@ int64_t gsdd_gif_encode_bound(int T, int H, int W);
 int64_t gsdd_gif_encode(const uint8_t* indices, int T, int H, int W, const uint8_t* palettes, const int32_t* n_colors, int n_palettes,
                         int delay_cs, int loop, uint8_t* out, int64_t cap, int64_t* clear_codes);
 
+/* ------------------------------------------------------------------ GIF import (gif.py; csrc/gif_read.hip, csrc/gif_read_host.hpp)
+ * The host walks the file and decodes the LZW streams; the device composites the frame rectangles (transparency, disposal) onto the
+ * canvas and expands palette indices to RGB.  Tables are plain integers, no struct: frames[F][8] int32 = x, y, w, h, raster offset,
+ * palette row, transparent index (-1 = none), disposal (0 .. 3; 4 .. 7 are stored as 0); palettes[P][256][4] uint8 (R, G, B, 0 -- the
+ * layout of gsdd_gif_map; zeros behind a table's size), the global table first if there is one, then the local ones in file order.
+ * The first two entries are HOST code on HOST pointers reading FOREIGN bytes: nothing is launched, no stream; they never read outside
+ * data[0 .. n).  Malformed input -- a bad signature, an empty canvas, an image that leaves the canvas or has w = 0 or h = 0, an image
+ * without any colour table, a minimum code size outside 1 .. 8, an unknown block, no frames, an LZW code above the next free table
+ * entry, a first code after a clear code that is not a literal, data that ends before w*h pixels, a sub-block chain cut off by the end
+ * of the data -- is GSDD_E_ARG with gsdd_last_error() naming the byte offset.  A missing trailer behind a complete frame is accepted. */
+/* Block structure only, no LZW.  info[8]: W, H, frames F, colour tables P (global + local), raster bytes (the sum of w*h over the
+ * frames), NETSCAPE2.0 loop count (-1 if absent), 1 if a global table exists, the version (87 or 89). */
+int gsdd_gif_probe(const uint8_t* data, int64_t n, int64_t* info);
+/* frames[F][8], delays[F] (centiseconds; 0 for a frame without a graphic control extension), palettes[P][256][4] and raster (the
+ * decoded indices of every frame rectangle back to back, rows in DISPLAY order: interlacing is undone) with F, P of gsdd_gif_probe on
+ * the same bytes.  LZW: clear and end codes, KwKwK, a deferred clear (with 4096 entries the table stops growing and codes stay 12
+ * bits), sub-blocks of 1 .. 255 bytes; decoding of a frame stops at w*h pixels.  GSDD_E_CAP when the frames hold more than raster_cap
+ * (or more than 2^31 - 1) pixels: nothing is written at or behind raster[raster_cap] in any case. */
+int gsdd_gif_decode(const uint8_t* data, int64_t n, int32_t* frames, int32_t* delays, uint8_t* palettes, uint8_t* raster,
+                    int64_t raster_cap);
+/* Device: raster, frames[F][8], palettes (4-byte aligned) as gsdd_gif_decode wrote them, select[T_out] int32 -> out[T_out][H][W][3]
+ * uint8, the input of gsdd_preprocess_clip.  Per pixel, starting from the matte (0xRRGGBB), for f = 0 .. select[T_out-1]:
+ *   1. f > 0: frame f-1's disposal inside frame f-1's rectangle: 2 sets the pixel to the matte (not the logical screen's background
+ *      colour), 3 to the value saved in step 2 of frame f-1, 0 and 1 leave it;
+ *   2. if frame f has disposal 3 the pixel's value is saved;
+ *   3. inside frame f's rectangle an index other than f's transparent index sets the pixel to palettes[row_f][index];
+ *   4. the pixel is written to every slot k with select[k] == f.
+ * select is non-decreasing in 0 .. F-1 and may repeat a frame (a short clip padded with its last frame).  select_host[T_out] is the
+ * HOST copy of select: the call checks it before anything is launched and reads the last frame to walk from it (the library never
+ * reads device memory on the host).  A select_host that decreases or leaves 0 .. F-1, W or H outside 1 .. 65535, T_out < 1, F < 1 or
+ * a matte outside 0 .. 0xFFFFFF is GSDD_E_ARG.  One launch; every byte of out is written. */
+int gsdd_gif_compose(const uint8_t* raster, const int32_t* frames, const uint8_t* palettes, int F, int W, int H, const int32_t* select,
+                     const int32_t* select_host, int T_out, int matte_rgb, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */
 int gsdd_graph_begin(void* stream);

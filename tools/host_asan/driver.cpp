@@ -724,6 +724,176 @@ int main() {
         EXPECT((int)gsdd_gif_encode_bound(1, 65536, We), GSDD_E_ARG, false);
     }
 
+    // ---------------------------------------------------------------- GIF import: the decoder of FOREIGN bytes RUNS here, on exact-size heap copies
+    {
+        // probe, then decode into exact-size tables, then once more with the raster one byte short; -> the decode's (or the failed probe's) code
+        auto walk_file = [&](const std::vector<uint8_t>& file, std::vector<uint8_t>* raster_out = nullptr) -> int {
+            const int64_t n = (int64_t)file.size();
+            uint8_t* d = new uint8_t[(size_t)n];                                                             // (n = 0: a valid pointer to nothing)
+            std::copy(file.begin(), file.end(), d);
+            int64_t info[8];
+            int rc = gsdd_gif_probe(d, n, info);
+            ++g_checked;
+            if (rc != GSDD_OK && rc != GSDD_E_ARG) { std::fprintf(stderr, "FAIL gsdd_gif_probe -> %d\n", rc); ++g_failed; }
+            if (rc == GSDD_OK) {
+                const size_t F = (size_t)info[2], P = (size_t)info[3], total = (size_t)info[4];
+                std::vector<int32_t> frames(F * 8), delays(F);
+                std::vector<uint8_t> palettes(P * 1024), raster(total), shorter(total - 1);
+                rc = gsdd_gif_decode(d, n, frames.data(), delays.data(), palettes.data(), raster.data(), (int64_t)total);
+                ++g_checked;
+                if (rc != GSDD_OK && rc != GSDD_E_ARG) { std::fprintf(stderr, "FAIL gsdd_gif_decode -> %d\n", rc); ++g_failed; }
+                if (rc == GSDD_OK) {
+                    uint8_t* nothing = new uint8_t[0];
+                    const int rc_short = gsdd_gif_decode(d, n, frames.data(), delays.data(), palettes.data(),
+                                                         total > 1 ? shorter.data() : nothing, (int64_t)total - 1);
+                    delete[] nothing;
+                    ++g_checked;
+                    if (rc_short != GSDD_E_CAP) { std::fprintf(stderr, "FAIL gsdd_gif_decode one raster byte short -> %d\n", rc_short); ++g_failed; }
+                    if (raster_out) *raster_out = raster;
+                }
+            }
+            delete[] d;
+            return rc;
+        };
+        auto expect_file = [&](const char* what, const std::vector<uint8_t>& file, int want) {
+            const int rc = walk_file(file);
+            ++g_checked;
+            if (rc != want) { std::fprintf(stderr, "FAIL GIF import of %s -> %d (want %d) [%s]\n", what, rc, want, gsdd_last_error()); ++g_failed; }
+        };
+        // the project's own writer's files: 96 x 96 noise with mid-stream clear codes, global and local tables
+        {
+            const int Te = 2, He = 96, We = 96;
+            std::vector<uint8_t> px((size_t)Te * He * We), table((size_t)Te * 768);
+            uint32_t lcg = 7u;
+            for (auto& v : px) { lcg = lcg * 1664525u + 1013904223u; v = (uint8_t)(lcg >> 24); }
+            for (size_t i = 0; i < table.size(); ++i) table[i] = (uint8_t)(i * 5);
+            const int32_t full[2] = {256, 256};
+            for (int npal : {1, 2}) {
+                std::vector<uint8_t> file((size_t)gsdd_gif_encode_bound(Te, He, We)), raster;
+                const int64_t n = gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, npal, 20, 0, file.data(), (int64_t)file.size(), nullptr);
+                file.resize((size_t)(n > 0 ? n : 0));
+                const int rc = walk_file(file, &raster);
+                ++g_checked;
+                if (rc != GSDD_OK || raster != px) { std::fprintf(stderr, "FAIL the writer's file does not decode to its pixels (%d)\n", rc); ++g_failed; }
+            }
+        }
+        // a hand-made file: 3-bit codes with a clear code before every pair of pixels, so that the width never changes
+        auto stream = [](const std::vector<int>& codes) {
+            std::vector<uint8_t> bytes;
+            uint32_t acc = 0;
+            int nbits = 0;
+            for (int c : codes) { acc |= (uint32_t)c << nbits; nbits += 3; while (nbits >= 8) { bytes.push_back((uint8_t)acc); acc >>= 8; nbits -= 8; } }
+            if (nbits) bytes.push_back((uint8_t)acc);
+            std::vector<uint8_t> out;
+            out.push_back(2);                                                                                // minimum code size
+            for (size_t i = 0; i < bytes.size(); i += 2) {                                                   // sub-blocks of 2 bytes
+                const size_t len = std::min<size_t>(2, bytes.size() - i);
+                out.push_back((uint8_t)len);
+                out.insert(out.end(), bytes.begin() + (long)i, bytes.begin() + (long)(i + len));
+            }
+            out.push_back(0);
+            return out;
+        };
+        auto image = [&](int x, int y, int w, int h, int flags, const std::vector<int>& codes) {
+            std::vector<uint8_t> out = {0x2C, (uint8_t)x, 0, (uint8_t)y, 0, (uint8_t)w, 0, (uint8_t)h, 0, (uint8_t)flags};
+            const std::vector<uint8_t> s = stream(codes);
+            out.insert(out.end(), s.begin(), s.end());
+            return out;
+        };
+        auto cat = [](std::vector<uint8_t> a, const std::vector<uint8_t>& b) { a.insert(a.end(), b.begin(), b.end()); return a; };
+        const std::vector<uint8_t> head = {'G', 'I', 'F', '8', '9', 'a', 4, 0, 3, 0, 0x81, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12};
+        const std::vector<uint8_t> loop = {0x21, 0xFF, 11, 'N', 'E', 'T', 'S', 'C', 'A', 'P', 'E', '2', '.', '0', 3, 1, 5, 0, 0};
+        const std::vector<uint8_t> gce = {0x21, 0xF9, 4, 0x09, 7, 0, 2, 0}, trailer = {0x3B};
+        const std::vector<int> twelve = {4, 0, 1, 4, 2, 3, 4, 0, 6, 4, 1, 2, 4, 3, 3, 4, 0, 0, 5};               // 2 + 2 + 3 (KwKwK) + 2 + 2 + 2 pixels: one too many
+        std::vector<uint8_t> good = cat(cat(cat(head, loop), image(0, 0, 4, 3, 0, twelve)), gce);
+        good = cat(cat(good, image(1, 0, 2, 3, 0x40, {4, 1, 1, 4, 2, 2, 4, 3, 3, 5})), trailer);                // interlaced 2 x 3
+        {
+            std::vector<uint8_t> raster;
+            const int rc = walk_file(good, &raster);
+            const std::vector<uint8_t> want = {0, 1, 2, 3, 0, 0, 0, 1, 2, 3, 3, 0, /* rows 0, 2, 1 of the stored 1 1 | 2 2 | 3 3 */ 1, 1, 3, 3, 2, 2};
+            ++g_checked;
+            if (rc != GSDD_OK || raster != want) { std::fprintf(stderr, "FAIL the hand-made GIF (%d) [%s]\n", rc, gsdd_last_error()); ++g_failed; }
+        }
+        int accepted = 0;
+        for (size_t n = 0; n < good.size(); ++n) {                                                           // every truncation
+            const int rc = walk_file(std::vector<uint8_t>(good.begin(), good.begin() + (long)n));
+            accepted += rc == GSDD_OK;
+        }
+        ++g_checked;
+        if (accepted != 3) { std::fprintf(stderr, "FAIL %d truncations of the hand-made GIF decode (want 3: behind frame 0, behind frame 1's control extension, behind frame 1)\n", accepted); ++g_failed; }
+        const std::vector<uint8_t> body = cat(head, {});
+        auto patched = [&](size_t at, uint8_t v) { std::vector<uint8_t> f = cat(cat(head, image(0, 0, 4, 3, 0, twelve)), trailer); f[at] = v; return f; };
+        expect_file("a good single frame", patched(0, 'G'), GSDD_OK);
+        expect_file("a bad signature", patched(3, '9'), GSDD_E_ARG);
+        expect_file("an empty canvas", patched(6, 0), GSDD_E_ARG);
+        expect_file("x + w beyond the canvas", patched(head.size() + 1, 1), GSDD_E_ARG);
+        expect_file("y + h beyond the canvas", patched(head.size() + 3, 1), GSDD_E_ARG);
+        expect_file("w = 0", patched(head.size() + 5, 0), GSDD_E_ARG);
+        expect_file("h = 0", patched(head.size() + 7, 0), GSDD_E_ARG);
+        expect_file("minimum code size 0", patched(head.size() + 10, 0), GSDD_E_ARG);
+        expect_file("minimum code size 9", patched(head.size() + 10, 9), GSDD_E_ARG);
+        expect_file("an unknown block", patched(head.size(), 0x2D), GSDD_E_ARG);
+        expect_file("a table without its flag", patched(10, 0x01), GSDD_E_ARG);
+        expect_file("no frames, a trailer", cat(body, trailer), GSDD_E_ARG);
+        expect_file("no frames, no trailer", body, GSDD_E_ARG);
+        expect_file("no frames, extensions only", cat(cat(cat(body, loop), gce), trailer), GSDD_E_ARG);
+        expect_file("a code above the next free entry", cat(cat(head, image(0, 0, 4, 3, 0, {4, 0, 7, 5})), trailer), GSDD_E_ARG);
+        expect_file("a first code that is no literal", cat(cat(head, image(0, 0, 4, 3, 0, {4, 6, 5})), trailer), GSDD_E_ARG);
+        expect_file("the same behind a second clear code", cat(cat(head, image(0, 0, 4, 3, 0, {4, 0, 4, 7, 5})), trailer), GSDD_E_ARG);
+        expect_file("an end code before w * h pixels", cat(cat(head, image(0, 0, 4, 3, 0, {4, 0, 1, 5})), trailer), GSDD_E_ARG);
+        expect_file("a chain that closes before w * h pixels", cat(cat(head, image(0, 0, 4, 3, 0, {4, 0, 1})), trailer), GSDD_E_ARG);
+        expect_file("pixels beyond w * h", cat(cat(head, image(0, 0, 1, 1, 0, twelve)), trailer), GSDD_OK);
+        {
+            std::vector<uint8_t> cut = cat(head, image(0, 0, 4, 3, 0, twelve));
+            cut.pop_back();                                                                                  // the chain's zero length
+            expect_file("a chain without its end", cut, GSDD_E_ARG);
+            cut.pop_back();
+            expect_file("a chain cut inside a sub-block", cut, GSDD_E_ARG);
+        }
+        int64_t info[8];
+        int32_t fr[8], dl[1];
+        uint8_t pl[1024], rs[16];
+        EXPECT(gsdd_gif_probe(nullptr, 10, info), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_probe(good.data(), (int64_t)good.size(), nullptr), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_probe(good.data(), -1, info), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(nullptr, 10, fr, dl, pl, rs, 16), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(good.data(), (int64_t)good.size(), nullptr, dl, pl, rs, 16), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(good.data(), (int64_t)good.size(), fr, nullptr, pl, rs, 16), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(good.data(), (int64_t)good.size(), fr, dl, nullptr, rs, 16), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(good.data(), (int64_t)good.size(), fr, dl, pl, nullptr, 16), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_decode(good.data(), (int64_t)good.size(), fr, dl, pl, rs, -1), GSDD_E_ARG, false);
+
+        // the compositor's checks (fake device pointers; select_host is real host memory, exact size)
+        const int F = 16, W = 128, H = 128;
+        uint8_t *raster = devp<uint8_t>((size_t)F * W * H), *pal = devp<uint8_t>(1024), *out = devp<uint8_t>((size_t)F * W * H * 3);
+        int32_t *frames = devp<int32_t>((size_t)F * 32), *sel = devp<int32_t>((size_t)F * 4);
+        std::vector<int32_t> all(F), padded = {0, 4, 8, 15, 15, 15}, one = {15}, down = {0, 2, 1}, below = {-1, 0}, above = {0, 16};
+        for (int i = 0; i < F; ++i) all[i] = i;
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, all.data(), F, 0, out, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, padded.data(), 6, 0xFFFFFF, out, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, one.data(), 1, 0x102030, out, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, 1, 1, sel, one.data(), 1, 0, out, st), GSDD_OK, true);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, 65535, 65535, sel, one.data(), 1, 0, out, st), GSDD_OK, true);   // 2^32 - 131071 pixels
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, down.data(), 3, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, below.data(), 2, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, above.data(), 2, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, all.data(), 0, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, all.data(), -1, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, 0, W, H, sel, all.data(), 1, 0, out, st), GSDD_E_ARG, false);
+        for (int bad : {0, -1, 65536}) {
+            EXPECT(gsdd_gif_compose(raster, frames, pal, F, bad, H, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, bad, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+        }
+        for (int bad : {-1, 1 << 24}) EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, all.data(), F, bad, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(nullptr, frames, pal, F, W, H, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, nullptr, pal, F, W, H, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, nullptr, F, W, H, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, nullptr, all.data(), F, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, nullptr, F, 0, out, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal, F, W, H, sel, all.data(), F, 0, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_compose(raster, frames, pal + 2, F, W, H, sel, all.data(), F, 0, out, st), GSDD_E_ARG, false);   // misaligned palette
+    }
+
     // ---------------------------------------------------------------- graph capture misuse, events
     {
         void* exec = nullptr;
