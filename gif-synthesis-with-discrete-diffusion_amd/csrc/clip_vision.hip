@@ -1,7 +1,8 @@
 // The pieces of the CLIP image tower (clip.model.VisionTransformer / transformers.CLIPVisionModelWithProjection) that are not a
-// gsdd_gemm / gsdd_row_stats / gsdd_ln_apply / gsdd_text_pool call: frames -> patch rows, class token + position embedding, and the
-// NON-causal multi-head self-attention over at most 77 positions.  gif-synthesis-with-discrete-diffusion_amd/vision.py strings the
-// tower together; the evaluator scores sampled clips against their captions with it (CLIPSIM).
+// gsdd_gemm / gsdd_row_stats / gsdd_ln_apply / gsdd_text_pool / gsdd_clip_attention call: frames -> patch rows, and class token +
+// position embedding.  The non-causal self-attention is clip_attention.hip's, the kernel both CLIP towers share.
+// gif-synthesis-with-discrete-diffusion_amd/vision.py strings the tower together; the evaluator scores sampled clips against their
+// captions with it (CLIPSIM).
 //
 // Frame patches.  One thread per resized pixel (frame, channel, y, x) of the R x R image.  The source pixels are the decoder's
 // ImageNet-normalised floats; each of the 4 x 4 taps is de-normalised and quantised to its uint8 level exactly as the evaluator's
@@ -12,25 +13,11 @@
 // coordinate is the rational ((2 o + 1) H - R) / (2 R): its floor and its fraction are taken in integers, so the weights carry one
 // rounding of t and not the rounding of a coordinate near H (torch forms the coordinate in fp32).  At H == R every fraction is 0,
 // the weights are exactly (0, 1, 0, 0) and the result is the quantised frame.
-//
-// Attention.  text_tower.hip's layout: one workgroup per (row, head), one wave per 16-query tile (at most five), Q (pre-scaled), K
-// and V of the head in LDS at a pitch of D + 4 floats (rows behind S written as zeros), every product a 16x16 tile of
-// v_mfma_f32_16x16x4_f32 (exact f32; operand maps: A lane (li = l & 15, g = l >> 4) gives A[li][k = g], B gives B[k = g][li], the
-// result D[4 g + r][li], r = 0..3).  Scores are computed as K Q^T -- query on the lane, keys 4 g + r in registers -- which is the
-// A operand of the product with V, so the probabilities never leave registers.  What differs from the causal kernel: EVERY wave
-// walks ALL ceil(S / 16) key tiles, and nothing causal hides the zero-filled tail of the last one (a zero K row scores 0, which
-// is a probability of exp(-m) and not of 0), so keys at positions >= S are set to -inf BEFORE the row maximum and the sum.
-// exp(-inf - m) is an exact 0 and the V rows behind S are zeros: the tail contributes exact zeros.  Query rows at positions >= S
-// of the last wave's tile compute on zero Q rows (finite throughout) and are not stored.
 #include "common.hpp"
 
 namespace gsdd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CLIPV_MAX_S = 77;                   // the attention kernel's LDS images hold 80 rows
-constexpr int CLIPV_TILES = (CLIPV_MAX_S + 15) / 16;
-constexpr int CLIPV_ROWS = 16 * CLIPV_TILES;
+constexpr int CLIPV_MAX_S = 77;                   // the longest sequence the attention kernel holds (clip_attention.hip)
 
 struct ClipNorm { float im_mean[3], im_std[3], clip_mean[3], clip_std[3]; };
 
@@ -111,102 +98,6 @@ __global__ __launch_bounds__(256) void clip_vision_embed_kernel(const float* __r
     *reinterpret_cast<float4*>(x + row * C + c) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
 }
 
-__device__ __forceinline__ float clipv_groups_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
-__device__ __forceinline__ float clipv_groups_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
-
-// qkv rows [B*S][3C] = (q | k | v), head h at columns h*D of each third; out rows [B*S][C].  blockDim.x = 64 * ceil(S / 16).
-template <int D>
-__global__ __launch_bounds__(64 * CLIPV_TILES) void clip_attention_kernel(const float* __restrict__ qkv, int S, int C, int n_head,
-                                                                          float scale, float* __restrict__ out) {
-    constexpr int P = D + 4;
-    __shared__ __attribute__((aligned(16))) float sq[CLIPV_ROWS * P];
-    __shared__ __attribute__((aligned(16))) float sk[CLIPV_ROWS * P];
-    __shared__ __attribute__((aligned(16))) float sv[CLIPV_ROWS * P];
-    const int b = blockIdx.x / n_head, h = blockIdx.x - b * n_head;
-    const int nt = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));      // key (and query) tiles, <= CLIPV_TILES
-    const int nrow = 16 * nt;                                      // S rounded up to whole tiles, <= CLIPV_ROWS
-    const float* base = qkv + (int64_t)b * S * 3 * C + h * D;
-    for (int i = threadIdx.x; i < nrow * (D / 4); i += blockDim.x) {
-        const int r = i / (D / 4), c = 4 * (i - r * (D / 4));
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f), k = q, v = q;
-        if (r < S) {
-            const float* p = base + (int64_t)r * 3 * C + c;
-            q = *reinterpret_cast<const float4*>(p);
-            k = *reinterpret_cast<const float4*>(p + C);
-            v = *reinterpret_cast<const float4*>(p + 2 * C);
-            q = make_float4(q.x * scale, q.y * scale, q.z * scale, q.w * scale);      // q scaled before the product, as the tower does
-        }
-        *reinterpret_cast<float4*>(sq + r * P + c) = q;
-        *reinterpret_cast<float4*>(sk + r * P + c) = k;
-        *reinterpret_cast<float4*>(sv + r * P + c) = v;
-    }
-    __syncthreads();
-
-    const int qt = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    const int query = 16 * qt + li;
-    float q[D / 4];
-#pragma unroll
-    for (int s = 0; s < D / 4; ++s) q[s] = sq[query * P + 4 * s + g];
-    // scores with the query on the lane: p[kt][r] = <q[query], k[16 kt + 4 g + r]>, -inf for a key behind S
-    float p[CLIPV_TILES][4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < CLIPV_TILES; ++kt) {
-        if (kt < nt) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            const float* kr = sk + (16 * kt + li) * P + g;
-#pragma unroll
-            for (int s = 0; s < D / 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[4 * s], q[s], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                p[kt][r] = (16 * kt + 4 * g + r < S) ? acc[r] : -INFINITY;
-                m = fmaxf(m, p[kt][r]);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[kt][r] = -INFINITY;
-        }
-    }
-    m = clipv_groups_max(m);                                       // key 0 is in front of S for every query: m is finite
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < CLIPV_TILES; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            p[kt][r] = expf(p[kt][r] - m);
-            l += p[kt][r];
-        }
-    l = clipv_groups_sum(l);
-    // o[t][r'] = O[16 qt + 4 g + r'][16 t + li] = sum over (kt, r, g) of P[li][16 kt + 4 g + r] V[16 kt + 4 g + r][16 t + li]
-    f32x4 o[D / 16];
-#pragma unroll
-    for (int t = 0; t < D / 16; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < CLIPV_TILES; ++kt) {
-        if (kt < nt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pn = p[kt][r] / l;                         // (a true division, as torch.softmax)
-                const float* vr = sv + (16 * kt + 4 * g + r) * P + li;
-#pragma unroll
-                for (int t = 0; t < D / 16; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(pn, vr[16 * t], o[t], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 16 * qt + 4 * g + r;
-        if (row < S) {
-            float* dst = out + ((int64_t)b * S + row) * C + h * D + li;
-#pragma unroll
-            for (int t = 0; t < D / 16; ++t) dst[16 * t] = o[t][r];
-        }
-    }
-}
-
-static inline bool clipv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace gsdd
 
 using namespace gsdd;
@@ -234,30 +125,13 @@ extern "C" int gsdd_clip_vision_embed(const float* patches, const float* class_e
     GSDD_CHECK_ARG(patches && class_emb && pos && x, "null pointer");
     GSDD_CHECK_ARG(N > 0 && S >= 1 && S <= CLIPV_MAX_S, "1 <= S <= 77 (S = patches per frame + 1)");
     GSDD_CHECK_ARG(C > 0 && C % 4 == 0, "C must be a multiple of 4");
-    GSDD_CHECK_ARG(clipv_aligned16(patches) && clipv_aligned16(class_emb) && clipv_aligned16(pos) && clipv_aligned16(x),
-                   "rows must be 16-byte aligned");
+    GSDD_CHECK_ARG(aligned16(patches) && aligned16(class_emb) && aligned16(pos) && aligned16(x), "rows must be 16-byte aligned");
     const int64_t rows = (int64_t)N * S;
     GSDD_CHECK_ARG(rows < (1ll << 31), "too many rows");
     const int64_t n = rows * (C / 4);
     GSDD_CHECK_ARG((n + 255) / 256 < (1ll << 31), "too many elements");
     hipLaunchKernelGGL(clip_vision_embed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, patches, class_emb,
                        pos, rows, S, C, x);
-    GSDD_CHECK_LAUNCH();
-    return GSDD_OK;
-}
-
-extern "C" int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream) {
-    GSDD_CHECK_ARG(qkv && out, "null pointer");
-    GSDD_CHECK_ARG(B > 0 && S >= 1 && S <= CLIPV_MAX_S, "1 <= S <= 77");
-    GSDD_CHECK_ARG(C > 0 && n_head > 0 && C % n_head == 0 && (C / n_head == 64 || C / n_head == 32 || C / n_head == 16),
-                   "head dimension must be 64, 32 or 16");
-    GSDD_CHECK_ARG((int64_t)B * n_head < (1ll << 31), "too many (row, head) pairs");
-    GSDD_CHECK_ARG(clipv_aligned16(qkv), "qkv must be 16-byte aligned");
-    GSDD_CHECK_ARG(scale == scale && scale > 0.f && scale < INFINITY, "scale must be finite and positive");
-    const dim3 grid((unsigned)(B * n_head)), block(64 * ((S + 15) / 16));
-    if (C / n_head == 64) hipLaunchKernelGGL(clip_attention_kernel<64>, grid, block, 0, (hipStream_t)stream, qkv, S, C, n_head, scale, out);
-    else if (C / n_head == 32) hipLaunchKernelGGL(clip_attention_kernel<32>, grid, block, 0, (hipStream_t)stream, qkv, S, C, n_head, scale, out);
-    else hipLaunchKernelGGL(clip_attention_kernel<16>, grid, block, 0, (hipStream_t)stream, qkv, S, C, n_head, scale, out);
     GSDD_CHECK_LAUNCH();
     return GSDD_OK;
 }

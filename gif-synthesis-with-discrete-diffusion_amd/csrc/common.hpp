@@ -14,24 +14,32 @@ namespace gsdd {
 void set_error(const std::string& s);
 int deterministic();            // gsdd_set_deterministic: the gradient reductions of the training step in their reproducible form
 
-#define GSDD_CHECK_ARG(cond, msg)                                                      \
+// The _AS forms report under the name `fn` instead of the enclosing function's: for a launcher that several entry points share.
+#define GSDD_CHECK_ARG_TEXT(fn, cond, text, msg)                                       \
     do {                                                                               \
         if (!(cond)) {                                                                 \
-            ::gsdd::set_error(std::string(__func__) + ": " + (msg) + " [" #cond "]"); \
+            ::gsdd::set_error(std::string(fn) + ": " + (msg) + " [" text "]");        \
             return GSDD_E_ARG;                                                         \
         }                                                                              \
     } while (0)
+#define GSDD_CHECK_ARG(cond, msg) GSDD_CHECK_ARG_TEXT(__func__, cond, #cond, msg)
+#define GSDD_CHECK_ARG_AS(fn, cond, msg) GSDD_CHECK_ARG_TEXT(fn, cond, #cond, msg)
 
-#define GSDD_CHECK_HIP(expr)                                                                   \
+#define GSDD_CHECK_HIP_TEXT(fn, expr, text)                                                    \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess) {                                                                \
-            ::gsdd::set_error(std::string(__func__) + ": " #expr " -> " + hipGetErrorString(e_)); \
+            ::gsdd::set_error(std::string(fn) + ": " text " -> " + hipGetErrorString(e_));     \
             return GSDD_E_HIP;                                                                 \
         }                                                                                      \
     } while (0)
+#define GSDD_CHECK_HIP(expr) GSDD_CHECK_HIP_TEXT(__func__, expr, #expr)
+#define GSDD_CHECK_HIP_AS(fn, expr) GSDD_CHECK_HIP_TEXT(fn, expr, #expr)
 
 #define GSDD_CHECK_LAUNCH() GSDD_CHECK_HIP(hipGetLastError())
+
+// the 16-byte alignment the float4 kernels need of their rows (host-side check)
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Per-device, per-call-site set-up (hipFuncSetAttribute for dynamic LDS above 64 KB is per device).  The call site's mask holds one bit per
 // device; a bit is set only AFTER every call of the set-up body has succeeded, so a failed hipFuncSetAttribute is reported by this call

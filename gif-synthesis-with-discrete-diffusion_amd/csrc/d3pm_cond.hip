@@ -73,7 +73,6 @@ __global__ __launch_bounds__(256) void cond_null_grad_kernel(const float* __rest
     }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool overlap(const void* a, const void* b, int64_t a_bytes, int64_t b_bytes) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + (uintptr_t)b_bytes && y < x + (uintptr_t)a_bytes;

@@ -582,15 +582,20 @@ def text_embed(ids, tok_emb, pos_emb, x, S, ids_host=None, stream=None):
     return x
 
 
-def text_attention(qkv, B, S, n_head, out, scale=None, stream=None):
-    """Causal self-attention over fused q|k|v rows [B*S][3C] -> out [B*S][C] (gsdd_text_attention); scale defaults to d^-0.5."""
+def _clip_attention(name, entry, qkv, B, S, n_head, out, scale, stream):
+    """The two attention entry points of the CLIP towers (csrc/clip_attention.hip): `entry` is gsdd_<name>; scale defaults to d^-0.5."""
     C_ = qkv.shape[1] // 3
     if qkv.shape[0] != B * S or qkv.shape[1] != 3 * C_ or tuple(out.shape) != (B * S, C_):
-        raise GsddError(f"text_attention: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
+        raise GsddError(f"{name}: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
     if scale is None:
         scale = float(C_ // n_head) ** -0.5
-    check(lib().gsdd_text_attention(ptr(qkv), B, S, C_, n_head, scale, ptr(out), stream_ptr(stream)))
+    check(entry(ptr(qkv), B, S, C_, n_head, scale, ptr(out), stream_ptr(stream)))
     return out
+
+
+def text_attention(qkv, B, S, n_head, out, scale=None, stream=None):
+    """Causal self-attention over fused q|k|v rows [B*S][3C] -> out [B*S][C] (gsdd_text_attention); scale defaults to d^-0.5."""
+    return _clip_attention("text_attention", lib().gsdd_text_attention, qkv, B, S, n_head, out, scale, stream)
 
 
 def text_pool(x, eot, B, S, out, eot_host=None, stream=None):
@@ -635,13 +640,7 @@ def clip_vision_embed(patches, class_emb, pos_emb, N, S, x, stream=None):
 
 def clip_attention(qkv, B, S, n_head, out, scale=None, stream=None):
     """Non-causal self-attention over fused q|k|v rows [B*S][3C] -> out [B*S][C] (gsdd_clip_attention); scale defaults to d^-0.5."""
-    C_ = qkv.shape[1] // 3
-    if qkv.shape[0] != B * S or qkv.shape[1] != 3 * C_ or tuple(out.shape) != (B * S, C_):
-        raise GsddError(f"clip_attention: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not match B = {B}, S = {S}")
-    if scale is None:
-        scale = float(C_ // n_head) ** -0.5
-    check(lib().gsdd_clip_attention(ptr(qkv), B, S, C_, n_head, scale, ptr(out), stream_ptr(stream)))
-    return out
+    return _clip_attention("clip_attention", lib().gsdd_clip_attention, qkv, B, S, n_head, out, scale, stream)
 
 
 # ----------------------------------------------------------------------------- GIF export (gif.py)

@@ -3,11 +3,11 @@ class token + position embedding, pre-LayerNorm, pre-LN transformer with QuickGE
 final LayerNorm, the bias-free projection).  It is the image half of CLIPSIM (gsdd_amd.metrics.clip_similarity): the cosine between a
 caption's CLIP text feature (gsdd_amd.text.ClipTextTower) and the CLIP image feature of every generated frame.
 
-Every computation is a kernel of libgsdd.so: gsdd_clip_frame_patches / gsdd_clip_vision_embed / gsdd_clip_attention
-(csrc/clip_vision.hip), gsdd_text_pool with every position 0 (the class-token row), and gsdd_row_stats / gsdd_ln_apply / gsdd_gemm for
-the LayerNorms and the linears -- the patch embedding, a Conv2d(3, C, P, stride P, bias=False), is one plain linear over patch rows.
-The residual blocks are text.run_resblocks, the loop the text tower runs, with the non-causal attention.  fp32 throughout; the
-reference's `clip` package runs the tower in fp16.
+Every computation is a kernel of libgsdd.so: gsdd_clip_frame_patches / gsdd_clip_vision_embed (csrc/clip_vision.hip),
+gsdd_clip_attention (csrc/clip_attention.hip), gsdd_text_pool with every position 0 (the class-token row), and gsdd_row_stats /
+gsdd_ln_apply / gsdd_gemm for the LayerNorms and the linears -- the patch embedding, a Conv2d(3, C, P, stride P, bias=False), is one
+plain linear over patch rows.  The residual blocks and the tower base are _clip.py's, shared with the text tower; here they run with
+the non-causal attention.  fp32 throughout; the reference's `clip` package runs the tower in fp16.
 
 Frames reach `forward` as the decoder returns them (ImageNet-normalised floats) and are quantised to uint8 levels as the evaluator
 does, resized with TORCH's bicubic and normalised with CLIP's statistics; the `clip` package resizes with PIL's (another kernel,
@@ -16,45 +16,36 @@ already at the tower's resolution and CLIP-normalised.
 
 The attention kernel holds a sequence of at most 77 positions, so ViT-B/32 at 224 (7 x 7 patches + 1 = 50) fits and ViT-B/16 (197)
 and ViT-L/14 (257) do not."""
-import re
-
 import torch
 
 from . import ops
+from ._clip import LN_EPS, MAX_POSITIONS, ClipTower, _f32, hf_layers_to_openai, layers_from_hf, layers_from_openai, run_resblocks
 from ._lib import GsddError
-from .text import LN_EPS, MAX_CONTEXT, _f32, run_resblocks
 
-MAX_SEQUENCE = MAX_CONTEXT                # 77: the rows the attention kernels' LDS images hold
+MAX_SEQUENCE = MAX_POSITIONS
 
 
 def hf_to_openai_vision_state_dict(sd):
     """Keys of transformers.CLIPVisionModelWithProjection -> the `clip` package's `visual.*` keys (q|k|v concatenated into in_proj,
     visual_projection transposed to [C][E]).  The inverse of what from_openai_state_dict undoes; used by tests and by exporters."""
     e = "vision_model.embeddings."
-    out = {"visual.conv1.weight": sd[e + "patch_embedding.weight"], "visual.class_embedding": sd[e + "class_embedding"],
-           "visual.positional_embedding": sd[e + "position_embedding.weight"],
-           "visual.ln_pre.weight": sd["vision_model.pre_layrnorm.weight"], "visual.ln_pre.bias": sd["vision_model.pre_layrnorm.bias"],
-           "visual.ln_post.weight": sd["vision_model.post_layernorm.weight"], "visual.ln_post.bias": sd["vision_model.post_layernorm.bias"],
-           "visual.proj": sd["visual_projection.weight"].t().contiguous()}
-    n = 0
-    while f"vision_model.encoder.layers.{n}.layer_norm1.weight" in sd:
-        s, d = f"vision_model.encoder.layers.{n}.", f"visual.transformer.resblocks.{n}."
-        for wb in ("weight", "bias"):
-            out[d + "attn.in_proj_" + wb] = torch.cat([sd[s + f"self_attn.{x}_proj.{wb}"] for x in "qkv"], dim=0)
-            for a, b in (("self_attn.out_proj", "attn.out_proj"), ("layer_norm1", "ln_1"), ("layer_norm2", "ln_2"),
-                         ("mlp.fc1", "mlp.c_fc"), ("mlp.fc2", "mlp.c_proj")):
-                out[d + f"{b}.{wb}"] = sd[s + f"{a}.{wb}"]
-        n += 1
-    return out
+    return {"visual.conv1.weight": sd[e + "patch_embedding.weight"], "visual.class_embedding": sd[e + "class_embedding"],
+            "visual.positional_embedding": sd[e + "position_embedding.weight"],
+            "visual.ln_pre.weight": sd["vision_model.pre_layrnorm.weight"], "visual.ln_pre.bias": sd["vision_model.pre_layrnorm.bias"],
+            "visual.ln_post.weight": sd["vision_model.post_layernorm.weight"], "visual.ln_post.bias": sd["vision_model.post_layernorm.bias"],
+            "visual.proj": sd["visual_projection.weight"].t().contiguous(),
+            **hf_layers_to_openai(sd, "vision_model.encoder.layers.", "visual.transformer.resblocks.")}
 
 
-class ClipVisionTower:
+class ClipVisionTower(ClipTower):
     """Frozen fp32 device weights of a CLIP image tower and its forward pass on the HIP kernels.
 
     Operands: `patch_w` [C][3*P*P] (the conv weight flattened, element order [c][py][px]), `class_emb` [C], `pos_emb` [S][C],
     `g_pre` / `b_pre` and `g_post` / `b_post` (the LayerNorms in front of and behind the transformer), `proj` [E][C] (applied as
     x @ proj.T, no bias), and per layer the text tower's: `wqkv` / `bqkv`, `wo` / `bo`, `w1` / `b1`, `w2` / `b2`, `g1` / `be1`,
     `g2` / `be2`."""
+
+    _VECTORS = ("patch_w", "class_emb", "pos_emb", "g_pre", "b_pre", "g_post", "b_post", "proj")
 
     def __init__(self, patch_w, class_emb, pos_emb, g_pre, b_pre, layers, g_post, b_post, proj, n_head, eps=LN_EPS, hidden_act="quick_gelu"):
         if hidden_act != "quick_gelu":
@@ -65,30 +56,17 @@ class ClipVisionTower:
         self.patch_w = _f32(patch_w).reshape(patch_w.shape[0], -1).contiguous()
         self.class_emb, self.pos_emb, self.proj = _f32(class_emb).reshape(-1), _f32(pos_emb), _f32(proj)
         self.g_pre, self.b_pre, self.g_post, self.b_post = _f32(g_pre), _f32(b_pre), _f32(g_post), _f32(b_post)
-        self.layers = [{k: _f32(v) for k, v in lay.items()} for lay in layers]
-        self.n_head, self.eps = int(n_head), float(eps)
         self.width = self.patch_w.shape[0]
         self.seq = int(self.pos_emb.shape[0])
         self.grid = int(round((self.seq - 1) ** 0.5))
         self.resolution = self.grid * self.patch
-        if not self.layers:
-            raise GsddError("ClipVisionTower: no transformer layers found in the state dict")
+        self._set_layers(layers, n_head, eps)
         if self.grid * self.grid + 1 != self.seq:
             raise GsddError(f"ClipVisionTower: {self.seq} position embeddings are not a square grid of patches plus the class token")
         if self.seq > MAX_SEQUENCE:
             raise GsddError(f"ClipVisionTower: a sequence of {self.seq} positions ({self.grid} x {self.grid} patches + the class token); "
                             f"the attention kernel holds at most {MAX_SEQUENCE} (ViT-B/32 at 224 has 50; ViT-B/16 and ViT-L/14 do not fit)")
-        if self.width % self.n_head or self.width // self.n_head not in (64, 32, 16):
-            raise GsddError(f"ClipVisionTower: width {self.width} over {self.n_head} heads gives a head dimension other than 64, 32 or 16")
-        if self.proj.shape[1] != self.width or self.pos_emb.shape[1] != self.width or self.class_emb.shape[0] != self.width:
-            raise GsddError("ClipVisionTower: embedding / projection widths do not match")
-        for lay in self.layers:
-            if tuple(lay["wqkv"].shape) != (3 * self.width, self.width) or lay["w2"].shape[1] != lay["w1"].shape[0] \
-                    or lay["w1"].shape[0] != self.layers[0]["w1"].shape[0]:
-                raise GsddError("ClipVisionTower: layer operand shapes do not match the tower's width")
-        self._buffers = {}
-
-    _VECTORS = ("patch_w", "class_emb", "pos_emb", "g_pre", "b_pre", "g_post", "b_post", "proj")
+        self._check_shapes(self.proj.shape[1] == self.width and self.pos_emb.shape[1] == self.width and self.class_emb.shape[0] == self.width)
 
     # ------------------------------------------------------------------ weight import
     @classmethod
@@ -96,18 +74,7 @@ class ClipVisionTower:
         """sd: state dict of transformers.CLIPVisionModelWithProjection (vision_model.embeddings.*, vision_model.pre_layrnorm.* -- the
         library's spelling --, vision_model.encoder.layers.N.*, vision_model.post_layernorm.*, visual_projection.weight).  The head
         count is not recoverable from the tensors."""
-        layers, n = [], 0
-        while f"vision_model.encoder.layers.{n}.layer_norm1.weight" in sd:
-            p = f"vision_model.encoder.layers.{n}."
-            layers.append({
-                "wqkv": torch.cat([_f32(sd[p + f"self_attn.{x}_proj.weight"]) for x in "qkv"], dim=0),
-                "bqkv": torch.cat([_f32(sd[p + f"self_attn.{x}_proj.bias"]) for x in "qkv"], dim=0),
-                "wo": sd[p + "self_attn.out_proj.weight"], "bo": sd[p + "self_attn.out_proj.bias"],
-                "g1": sd[p + "layer_norm1.weight"], "be1": sd[p + "layer_norm1.bias"],
-                "g2": sd[p + "layer_norm2.weight"], "be2": sd[p + "layer_norm2.bias"],
-                "w1": sd[p + "mlp.fc1.weight"], "b1": sd[p + "mlp.fc1.bias"],
-                "w2": sd[p + "mlp.fc2.weight"], "b2": sd[p + "mlp.fc2.bias"]})
-            n += 1
+        layers = layers_from_hf(sd, "vision_model.encoder.layers.")
         e = "vision_model.embeddings."
         return cls(sd[e + "patch_embedding.weight"], sd[e + "class_embedding"], sd[e + "position_embedding.weight"],
                    sd["vision_model.pre_layrnorm.weight"], sd["vision_model.pre_layrnorm.bias"], layers,
@@ -119,17 +86,7 @@ class ClipVisionTower:
         """sd: the `clip` package's keys (what the reference's Lightning checkpoints carry under `textencoder.clip_model.`, see
         checkpoint.extract_clip_vision_tower): fp16 tensors are widened, `visual.proj` ([C][E], applied as x @ P) is transposed,
         heads = width / 64 (clip.model.CLIP: vision_heads = vision_width // 64), the text tower's keys are ignored."""
-        pat = re.compile(r"^visual\.transformer\.resblocks\.(\d+)\.ln_1\.weight$")
-        n_layer = 1 + max((int(m.group(1)) for m in map(pat.match, sd) if m), default=-1)
-        layers = []
-        for n in range(n_layer):
-            p = f"visual.transformer.resblocks.{n}."
-            layers.append({
-                "wqkv": sd[p + "attn.in_proj_weight"], "bqkv": sd[p + "attn.in_proj_bias"],
-                "wo": sd[p + "attn.out_proj.weight"], "bo": sd[p + "attn.out_proj.bias"],
-                "g1": sd[p + "ln_1.weight"], "be1": sd[p + "ln_1.bias"], "g2": sd[p + "ln_2.weight"], "be2": sd[p + "ln_2.bias"],
-                "w1": sd[p + "mlp.c_fc.weight"], "b1": sd[p + "mlp.c_fc.bias"],
-                "w2": sd[p + "mlp.c_proj.weight"], "b2": sd[p + "mlp.c_proj.bias"]})
+        layers = layers_from_openai(sd, "visual.transformer.resblocks.")
         width = sd["visual.conv1.weight"].shape[0]
         if width % 64:
             raise GsddError(f"ClipVisionTower: the clip package uses width / 64 heads; width {width} is not a multiple of 64")
@@ -137,37 +94,10 @@ class ClipVisionTower:
                    sd["visual.ln_pre.bias"], layers, sd["visual.ln_post.weight"], sd["visual.ln_post.bias"], _f32(sd["visual.proj"]).t(),
                    width // 64, eps)
 
-    def to(self, device):
-        dev = torch.device(device)
-        for k in self._VECTORS:
-            setattr(self, k, getattr(self, k).to(dev))
-        self.layers = [{k: v.to(dev) for k, v in lay.items()} for lay in self.layers]
-        self._buffers = {}
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    @property
-    def device(self):
-        return self.patch_w.device
-
     # ------------------------------------------------------------------ forward
-    def _get_buffers(self, N, S):
-        buf = self._buffers.get((N, S))
-        if buf is None:
-            f = dict(dtype=torch.float32, device=self.device)
-            Cw, M, inner = self.width, N * S, self.layers[0]["w1"].shape[0]
-            buf = {"x": torch.empty((M, Cw), **f), "y": torch.empty((M, Cw), **f), "qkv": torch.empty((M, 3 * Cw), **f),
-                   "att": torch.empty((M, Cw), **f), "h": torch.empty((M, inner), **f), "stats": torch.empty((M, 2), **f),
-                   "pe": torch.empty((N * (S - 1), Cw), **f), "pooled": torch.empty((N, Cw), **f), "pstats": torch.empty((N, 2), **f),
-                   "first": torch.zeros((N,), dtype=torch.int64, device=self.device), "first_host": torch.zeros((N,), dtype=torch.int64)}
-            self._buffers[(N, S)] = buf
-        return buf
-
-    def _need_device(self, what):
-        if not self.device.type == "cuda":
-            raise GsddError(f"ClipVisionTower.{what} needs the weights on a ROCm device (no CPU fallback): call .to(device) first")
+    def _extra_buffers(self, N, S, f):
+        return {"pe": torch.empty((N * (S - 1), self.width), **f), "first": torch.zeros((N,), dtype=torch.int64, device=self.device),
+                "first_host": torch.zeros((N,), dtype=torch.int64)}
 
     def _run(self, rows, N):
         """rows: patch rows [N*G*G][3*P*P] on the device -> (N, E)."""
@@ -179,11 +109,7 @@ class ClipVisionTower:
         ops.row_stats(y, stats, eps=self.eps)
         ops.ln_apply(y, stats, self.g_pre, self.b_pre, out=x)
         run_resblocks(self.layers, ops.clip_attention, buf, N, S, self.n_head, self.eps)
-        ops.text_pool(x, buf["first"], N, S, buf["pooled"], eot_host=buf["first_host"])          # the class-token row of every frame
-        ops.row_stats(buf["pooled"], buf["pstats"], eps=self.eps)
-        out = torch.empty((N, self.proj.shape[0]), dtype=torch.float32, device=self.device)
-        ops.linear(buf["pooled"], self.proj, out, ln=(buf["pstats"], self.g_post, self.b_post, None, 0))
-        return out
+        return self._pool_project(buf, buf["first"], buf["first_host"], N, S, self.g_post, self.b_post)      # the class-token row of every frame
 
     @torch.no_grad()
     def forward(self, clips):

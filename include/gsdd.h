@@ -659,7 +659,8 @@ int gsdd_philox_uniform(uint64_t seed, int64_t stream_id, int64_t row0, int64_t 
 
 /* ------------------------------------------------------------------ CLIP text tower (text-conditioned sampling)
  * The three pieces of clip.model.CLIP.encode_text (called by the reference at src/models/text_models/clip_text_embedding.py:56-65)
- * that are not a gsdd_gemm / gsdd_row_stats call; gif-synthesis-with-discrete-diffusion_amd/text.py strings the tower together.
+ * that are not a gsdd_gemm / gsdd_row_stats call (csrc/text_tower.hip; the attention is csrc/clip_attention.hip, one kernel template
+ * for both CLIP towers); gif-synthesis-with-discrete-diffusion_amd/text.py strings the tower together.
  * `ids_host` / `eot_host` are the one exception to "every pointer is a device pointer": an optional HOST copy of the same integers
  * (the tokenizer produces them on the host).  When given, every value is range-checked before anything is launched and an
  * out-of-range one returns GSDD_E_ARG; without it (NULL) the kernels still never read out of range: the offending output row is
@@ -680,8 +681,8 @@ int gsdd_text_pool(const float* x, const int64_t* eot, const int64_t* eot_host, 
 
 /* ------------------------------------------------------------------ CLIP image tower (CLIPSIM in the evaluator)
  * The three pieces of clip.model.VisionTransformer / transformers.CLIPVisionModelWithProjection that are not a gsdd_gemm /
- * gsdd_row_stats / gsdd_ln_apply / gsdd_text_pool call; gif-synthesis-with-discrete-diffusion_amd/vision.py strings the tower
- * together.  Every pointer is a device pointer. */
+ * gsdd_row_stats / gsdd_ln_apply / gsdd_text_pool call (csrc/clip_vision.hip; the attention is csrc/clip_attention.hip);
+ * gif-synthesis-with-discrete-diffusion_amd/vision.py strings the tower together.  Every pointer is a device pointer. */
 /* clips[B][3][T][H][W] f32, ImageNet-normalised (what the decoder returns and the evaluator receives) -> patch rows
  * out[B*T*G*G][3*P*P], G = R / P: row (b*T + t)*G*G + gy*G + gx holds the patch's pixels in the order [c][py][px] of a
  * Conv2d(3, C, P, stride P) weight flattened to [C][3*P*P], so the patch embedding is one plain gsdd_gemm linear.
@@ -699,8 +700,8 @@ int gsdd_clip_frame_patches(const float* clips, int B, int T, int H, int W, int 
 int gsdd_clip_vision_embed(const float* patches, const float* class_emb, const float* pos, int N, int S, int C, float* x, void* stream);
 /* NON-causal multi-head self-attention over fused rows qkv[B*S][3C] = (q | k | v), head h at columns h*d of each third,
  * d = C / n_head in {64, 32, 16}; out rows [B*S][C] = softmax(scale q k^T) v; 1 <= S <= 77 (ViT-B/32 at 224: S = 50; ViT-B/16 and
- * ViT-L/14 have longer sequences and are out of range).  The contract and the layout of gsdd_text_attention (exact-f32 matrix
- * instructions, v_mfma_f32_16x16x4_f32) with every query seeing every key: the keys of the last 16-key tile at positions >= S are
+ * ViT-L/14 have longer sequences and are out of range).  The contract, the layout and the kernel template of gsdd_text_attention
+ * (csrc/clip_attention.hip; exact-f32 matrix instructions, v_mfma_f32_16x16x4_f32) with every query seeing every key: the keys of the last 16-key tile at positions >= S are
  * masked before the row maximum and the sum. */
 int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
 
