@@ -28,7 +28,7 @@ EXPORTS = [
     "gsdd_event_create", "gsdd_event_record", "gsdd_event_elapsed_ms", "gsdd_event_destroy",
     "gsdd_grad_sqnorm", "gsdd_grad_norm_finalize", "gsdd_adamw_ema_multi", "gsdd_swap_multi",
     "gsdd_gif_histogram", "gsdd_gif_box_sums", "gsdd_gif_map", "gsdd_gif_median_cut", "gsdd_gif_encode_bound", "gsdd_gif_encode",
-    "gsdd_gif_probe", "gsdd_gif_decode", "gsdd_gif_compose",
+    "gsdd_gif_probe", "gsdd_gif_decode", "gsdd_gif_compose", "gsdd_gif_palette_sums", "gsdd_gif_diffuse",
 ]
 
 _p = C.c_void_p
@@ -228,6 +228,8 @@ def lib():
         L.gsdd_gif_histogram.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p]
         L.gsdd_gif_box_sums.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p]
         L.gsdd_gif_map.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]
+        L.gsdd_gif_palette_sums.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]
+        L.gsdd_gif_diffuse.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p]
         L.gsdd_gif_median_cut.argtypes = [_p, _i, _p, C.POINTER(_i)]             # (host pointers)
         L.gsdd_gif_encode_bound.argtypes = [_i, _i, _i]
         L.gsdd_gif_encode_bound.restype = _i64

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "gif_device.hpp"
 #include "gif_host.hpp"
 
 namespace gsdd {
@@ -30,28 +31,6 @@ constexpr int GIF_BINS = gif::BINS;
 constexpr int GIF_HIST_THREADS = 1024, GIF_HIST_CHUNK = 16384;
 constexpr int GIF_SUMS_THREADS = 256, GIF_SUMS_CHUNK = 4096;
 constexpr int GIF_MAP_THREADS = 256, GIF_MAP_CHUNK = 1024;
-constexpr int64_t GIF_MAX_GROUP_PIXELS = 1ll << 24;            // 255 * 2^24 < 2^32: a box sum cannot overflow
-
-struct GifNorm { float mean[3], std[3]; };
-
-struct GifShape {
-    int64_t chan_stride;      // T H W: from one channel plane of a clip to the next
-    int64_t group_pixels;     // P
-    int64_t frame_pixels;     // H W
-    int T, W, per_frame, chunks;
-};
-
-__device__ __forceinline__ int gif_level(float x, float mean, float std) {
-    const float v = (x * std + mean) * 255.f;
-    return (int)fminf(fmaxf(truncf(v), 0.f), 255.f);          // (fmaxf drops a NaN: level 0)
-}
-
-// float offset of pixel 0, channel 0 of group g
-__device__ __forceinline__ int64_t gif_group_base(const GifShape& s, int64_t g) {
-    if (!s.per_frame) return g * 3 * s.chan_stride;
-    const int64_t b = g / s.T, t = g - b * s.T;
-    return b * 3 * s.chan_stride + t * s.frame_pixels;
-}
 
 __global__ __launch_bounds__(GIF_HIST_THREADS) void gif_histogram_kernel(const float* __restrict__ clips, GifShape s, GifNorm nm,
                                                                          uint32_t* __restrict__ hist, int64_t zero_words) {
@@ -127,8 +106,6 @@ __device__ __forceinline__ int gif_bayer(int x, int y) {
     return m;
 }
 
-__device__ __forceinline__ int gif_clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
 __global__ __launch_bounds__(GIF_MAP_THREADS) void gif_map_kernel(const float* __restrict__ clips, GifShape s, GifNorm nm,
                                                                   const uint32_t* __restrict__ palette, const int32_t* __restrict__ n_colors,
                                                                   int dither, uint8_t* __restrict__ out) {
@@ -154,8 +131,8 @@ __global__ __launch_bounds__(GIF_MAP_THREADS) void gif_map_kernel(const float* _
             gg = gif_clamp255(gg + off);
             b = gif_clamp255(b + off);
         }
-        int best = 0, best_d = 0x7fffffff;
-        for (int i = 0; i < n; ++i) {
+        int best = 0, best_d = 0x7fffffff;                     // (gif_nearest of gif_device.hpp, spelled out: through the function the
+        for (int i = 0; i < n; ++i) {                          // loop keeps its index in a VGPR and the kernel measures 4 % slower)
             const uint32_t e = pal[i];
             const int dr = r - (int)(e & 255u), dg = gg - (int)((e >> 8) & 255u), db = b - (int)((e >> 16) & 255u);
             const int d = dr * dr + dg * dg + db * db;
@@ -166,32 +143,6 @@ __global__ __launch_bounds__(GIF_MAP_THREADS) void gif_map_kernel(const float* _
         }
         out[g * s.group_pixels + p] = (uint8_t)best;
     }
-}
-
-static const GifNorm GIF_NORM = {{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
-
-// shape checks shared by the three entries; chunk = pixels per workgroup.  false = bad arguments (message set)
-static bool gif_shape(const char* fn, int B, int T, int H, int W, int per_frame, int chunk, GifShape& s, int64_t& G, int64_t& grid) {
-    const auto bad = [&](const char* msg) {
-        set_error(std::string(fn) + ": " + msg);
-        return false;
-    };
-    if (B <= 0 || T <= 0 || H <= 0 || W <= 0) return bad("bad sizes");
-    if (H > 65535 || W > 65535) return bad("H and W are at most 65535 (a GIF's limit)");
-    if (per_frame != 0 && per_frame != 1) return bad("per_frame is 0 or 1");
-    if ((int64_t)B * T >= (1ll << 31)) return bad("too many frames");
-    s.frame_pixels = (int64_t)H * W;
-    s.chan_stride = s.frame_pixels * T;
-    s.group_pixels = per_frame ? s.frame_pixels : s.chan_stride;
-    if (s.group_pixels > GIF_MAX_GROUP_PIXELS) return bad("a group (clip, or frame with per_frame) holds at most 2^24 pixels");
-    s.T = T;
-    s.W = W;
-    s.per_frame = per_frame;
-    s.chunks = (int)((s.group_pixels + chunk - 1) / chunk);
-    G = per_frame ? (int64_t)B * T : B;
-    grid = G * s.chunks;
-    if (grid >= (1ll << 31)) return bad("too many workgroups");
-    return true;
 }
 
 }  // namespace gsdd

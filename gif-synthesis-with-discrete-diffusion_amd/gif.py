@@ -5,11 +5,13 @@
       -> one device-to-host copy     G x 128 KB
       -> gsdd_gif_median_cut         (host, integer, deterministic) bin -> box table per group
       -> gsdd_gif_box_sums           count and R, G, B sums per box; the palette is the rounded mean, formed with integer torch ops
-      -> gsdd_gif_map                nearest palette entry per pixel (optional ordered dither)
+      -> gsdd_gif_palette_sums       (refine = N > 0) N + 1 Lloyd assignment passes; the palette of smallest squared error is kept
+      -> gsdd_gif_map                nearest palette entry per pixel (optional ordered dither), or
+         gsdd_gif_diffuse            (dither = "fs") Floyd-Steinberg error diffusion within each frame
       -> gsdd_gif_encode             (host) GIF89a file
 
 Every stage is integer arithmetic behind one fp32 step (the evaluator's uint8 rule), so the indices, the palette and the file's bytes
-are exactly reproducible; tests/gif_ref.py restates all of it in numpy.
+are exactly reproducible; tests/gif_ref.py and tests/gif_refine_ref.py restate all of it in numpy.
 
 The way back is probe_gif / read_gif at the end of this file: a GIF file -> uint8 frames (T, H, W, 3) on the device.
 
@@ -17,6 +19,7 @@ Synchronisation: quantize_clips synchronises ONCE, for the histogram the host's 
 indices to the host as well, which is the point of them).  Rendering happens outside the sampling loop and must stay outside any
 captured graph: none of this can be recorded."""
 import contextlib
+import math
 import os
 
 import numpy as np
@@ -26,17 +29,56 @@ from . import ops
 from ._lib import GsddError
 
 
-def quantize_clips(clips, colors=256, palette="clip", dither=0):
-    """clips (B, 3, T, H, W) -> (indices (B, T, H, W) uint8 on the device, palette (G, 256, 3) uint8 on the device, n_colors (G,) int32
-    on the device).  G = B with palette="clip" (one palette per clip), B*T with palette="frame" (one per frame, group b*T + t).
-    colors: at most this many palette entries, 2 .. 256; entries behind n_colors[g] are zeros.  dither: ordered-dither amplitude
-    0 .. 64, 0 = off."""
+def _check_quantize(colors, palette, dither, refine):
+    """the argument checks of quantize_clips, before any device call"""
     if palette not in ("clip", "frame"):
         raise GsddError(f'quantize_clips: palette is "clip" or "frame", got {palette!r}')
     if not isinstance(colors, int) or isinstance(colors, bool) or not 2 <= colors <= 256:
         raise GsddError(f"quantize_clips: colors is an integer in 2 .. 256, got {colors!r}")
-    if not isinstance(dither, int) or isinstance(dither, bool) or not 0 <= dither <= 64:
-        raise GsddError(f"quantize_clips: dither is an integer amplitude in 0 .. 64, got {dither!r}")
+    if dither != "fs" and (not isinstance(dither, int) or isinstance(dither, bool) or not 0 <= dither <= 64):
+        raise GsddError(f'quantize_clips: dither is an integer amplitude in 0 .. 64 or "fs", got {dither!r}')
+    if not isinstance(refine, int) or isinstance(refine, bool) or not 0 <= refine <= 32:
+        raise GsddError(f"quantize_clips: refine is an integer number of passes in 0 .. 32, got {refine!r}")
+
+
+def select_palette(palettes, errors):
+    """palettes: N + 1 tensors (G, 256, C), errors: N + 1 tensors (G,) -> per group the palette of the smallest error, the earliest on
+    ties (a later one replaces the choice only when strictly better); torch.where on the tensors' device, no synchronisation"""
+    best, best_err = palettes[0], errors[0]
+    for pal, err in zip(palettes[1:], errors[1:]):
+        better = err < best_err
+        best = torch.where(better[:, None, None], pal, best)
+        best_err = torch.where(better, err, best_err)
+    return best
+
+
+def refine_palette(clips, pal4, n_colors, passes, per_frame=False):
+    """Lloyd passes from pal4 (G, 256, 4) uint8 = p_0: `passes` + 1 gsdd_gif_palette_sums launches give the errors of p_0 .. p_N,
+    p_{k+1} being the rounded mean (2*sum + count) // (2*count) of the pixels nearest to each entry of p_k (an entry with none keeps its
+    colour).  Rounding a centroid can raise the error, so the result is per group the p_k of smallest error, the earliest on ties:
+    never worse than p_0.  -> (palette (G, 256, 4) uint8, errors (passes + 1, G) int64); integer torch ops on the device, no
+    synchronisation."""
+    palettes, errors = [pal4], []
+    for k in range(passes + 1):
+        sums, sse = ops.gif_palette_sums(clips, palettes[-1], n_colors, per_frame)
+        errors.append(sse)
+        if k < passes:
+            sums = sums.to(torch.int64) & 0xFFFFFFFF
+            count = sums[..., :1]
+            mean = (2 * sums[..., 1:] + count) // (2 * count).clamp(min=1)
+            nxt = palettes[-1].clone()
+            nxt[..., :3] = torch.where(count > 0, mean.to(torch.uint8), nxt[..., :3])
+            palettes.append(nxt)
+    return select_palette(palettes, errors).contiguous(), torch.stack(errors)
+
+
+def quantize_clips(clips, colors=256, palette="clip", dither=0, refine=0):
+    """clips (B, 3, T, H, W) -> (indices (B, T, H, W) uint8 on the device, palette (G, 256, 3) uint8 on the device, n_colors (G,) int32
+    on the device).  G = B with palette="clip" (one palette per clip), B*T with palette="frame" (one per frame, group b*T + t).
+    colors: at most this many palette entries, 2 .. 256; entries behind n_colors[g] are zeros.  refine: k-means passes from the
+    median cut's palette, 0 .. 32 (refine_palette; n_colors does not change).  dither: ordered-dither amplitude 0 .. 64, 0 = off, or
+    "fs": Floyd-Steinberg error diffusion within each frame (gsdd_gif_diffuse)."""
+    _check_quantize(colors, palette, dither, refine)
     per_frame = palette == "frame"
     clips = clips.contiguous() if torch.is_tensor(clips) else clips
     hist = ops.gif_histogram(clips, per_frame)
@@ -53,8 +95,28 @@ def quantize_clips(clips, colors=256, palette="clip", dither=0):
     pal4 = torch.zeros((G, 256, 4), dtype=torch.uint8, device=dev)
     pal4[..., :3] = mean.to(torch.uint8)
     n_dev = torch.from_numpy(n).to(dev)
-    indices = ops.gif_map(clips, pal4, n_dev, per_frame, dither)
+    if refine:
+        pal4, _ = refine_palette(clips, pal4, n_dev, refine, per_frame)
+    indices = ops.gif_diffuse(clips, pal4, n_dev, per_frame) if dither == "fs" else ops.gif_map(clips, pal4, n_dev, per_frame, dither)
     return indices, pal4[..., :3].contiguous(), n_dev
+
+
+def palette_error(clips, palette, n_colors, palette_mode="clip"):
+    """-> sse (G,) int64 on the device: the squared distance of every pixel of a group to its nearest palette entry (no dither), summed
+    over the group.  palette (G, 256, 3) as quantize_clips returns it, or (G, 256, 4)."""
+    if palette_mode not in ("clip", "frame"):
+        raise GsddError(f'palette_error: palette_mode is "clip" or "frame", got {palette_mode!r}')
+    if not torch.is_tensor(palette) or palette.dim() != 3 or palette.shape[-1] not in (3, 4):
+        raise GsddError("palette_error: palette must be uint8 (G, 256, 3) or (G, 256, 4)")
+    if palette.shape[-1] == 3:
+        palette = torch.cat([palette, torch.zeros_like(palette[..., :1])], dim=-1)
+    clips = clips.contiguous() if torch.is_tensor(clips) else clips
+    return ops.gif_palette_sums(clips, palette.contiguous(), n_colors, palette_mode == "frame")[1]
+
+
+def psnr_from_sse(sse, values):
+    """the PSNR in dB of a squared error `sse` summed over `values` uint8 values (3 per pixel); inf for sse = 0"""
+    return float("inf") if sse == 0 else 10.0 * math.log10(255.0 ** 2 * values / float(sse))
 
 
 def delay_centiseconds(fps):

@@ -706,6 +706,44 @@ def gif_map(clips, palette, n_colors, per_frame=False, dither=0, out=None, strea
     return out
 
 
+def _gif_palette(what, palette, n_colors, G):
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (G, 256, 4) or not palette.is_contiguous():
+        raise GsddError(f"{what}: palette must be contiguous uint8 {(G, 256, 4)}")
+    if not torch.is_tensor(n_colors) or n_colors.dtype != torch.int32 or tuple(n_colors.shape) != (G,) or not n_colors.is_contiguous():
+        raise GsddError(f"{what}: n_colors must be int32 {(G,)}")
+    if not palette.is_cuda or not n_colors.is_cuda:
+        raise GsddError(f"{what}: palette and n_colors must live on a ROCm device (no CPU fallback)")
+
+
+def gif_palette_sums(clips, palette, n_colors, per_frame=False, out=None, sse_out=None, stream=None):
+    """One Lloyd assignment pass: palette (G, 256, 4) uint8, n_colors (G,) int32 on the device -> (sums (G, 256, 4) int32 holding
+    uint32 (count, R, G, B sums) of the pixels nearest to each of the first n_colors entries, lowest index on ties, sse (G,) int64: the
+    group's total squared distance) (gsdd_gif_palette_sums).  Both are zeroed by the call."""
+    B, T, H, W, G = _gif_clips("gif_palette_sums", clips, per_frame)
+    _gif_palette("gif_palette_sums", palette, n_colors, G)
+    out = _gif_words("gif_palette_sums", out, (G, 256, 4), clips.device)
+    if sse_out is None:
+        sse_out = torch.empty((G,), dtype=torch.int64, device=clips.device)
+    elif sse_out.dtype != torch.int64 or tuple(sse_out.shape) != (G,) or sse_out.device != clips.device or not sse_out.is_contiguous():
+        raise GsddError(f"gif_palette_sums: sse_out must be contiguous int64 {(G,)} on {clips.device}")
+    check(lib().gsdd_gif_palette_sums(ptr(clips), B, T, H, W, int(bool(per_frame)), ptr(palette), ptr(n_colors), ptr(out), ptr(sse_out),
+                                      stream_ptr(stream)))
+    return out, sse_out
+
+
+def gif_diffuse(clips, palette, n_colors, per_frame=False, out=None, stream=None):
+    """palette (G, 256, 4) uint8, n_colors (G,) int32 on the device -> indices (B, T, H, W) uint8 by Floyd-Steinberg error diffusion,
+    every frame on its own, left to right and top to bottom (gsdd_gif_diffuse; the rule in full: include/gsdd.h)."""
+    B, T, H, W, G = _gif_clips("gif_diffuse", clips, per_frame)
+    _gif_palette("gif_diffuse", palette, n_colors, G)
+    if out is None:
+        out = torch.empty((B, T, H, W), dtype=torch.uint8, device=clips.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, T, H, W) or out.device != clips.device or not out.is_contiguous():
+        raise GsddError(f"gif_diffuse: out must be contiguous uint8 {(B, T, H, W)} on {clips.device}")
+    check(lib().gsdd_gif_diffuse(ptr(clips), B, T, H, W, int(bool(per_frame)), ptr(palette), ptr(n_colors), ptr(out), stream_ptr(stream)))
+    return out
+
+
 def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
 

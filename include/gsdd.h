@@ -705,7 +705,7 @@ int gsdd_clip_vision_embed(const float* patches, const float* class_emb, const f
  * masked before the row maximum and the sum. */
 int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
 
-/* ------------------------------------------------------------------ GIF export of decoded clips (gif.py; csrc/gif.hip, csrc/gif_host.hpp)
+/* ------------------------------------------------------------------ GIF export of decoded clips (gif.py; csrc/gif.hip, csrc/gif_refine.hip, csrc/gif_host.hpp)
  * Colour quantisation on the device, median cut and the GIF89a / LZW writer on the host.  clips[B][3][T][H][W] f32 are the decoder's
  * ImageNet-normalised clips.  Each pixel's uint8 channels are formed by the evaluator's rule: v = (x*std[c] + mean[c]) * 255 in fp32
  * in that order, clamped to [0, 255] (NaN -> 0), truncated.  Everything after that step is integer arithmetic with integer atomics:
@@ -724,6 +724,25 @@ int gsdd_gif_box_sums(const float* clips, int B, int T, int H, int W, int per_fr
  * to [0, 255]; M is the 8 x 8 Bayer matrix M(x,y) = sum_{i=0..2} ((((x>>i)^(y>>i))&1) << (2*(2-i)+1) | ((y>>i)&1) << (2*(2-i))). */
 int gsdd_gif_map(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* palette, const int32_t* n_colors, int dither,
                  uint8_t* out, void* stream);
+/* One assignment pass of a k-means (Lloyd) refinement (csrc/gif_refine.hip).  palette, n_colors as gsdd_gif_map takes them ->
+ * sums[G][256][4] uint32: per entry i < n_colors the count and the R, G, B sums of the pixels whose nearest entry is i -- nearest exactly
+ * as in gsdd_gif_map without dither: integer squared distance, the lowest index on ties, so the higher of two equal entries stays empty --
+ * and sse[G] uint64 (8-byte aligned): the group's total squared distance to the nearest entries (64 bits: 3 * 255^2 * 2^24 > 2^32).  Both
+ * are zeroed by the call; with n_colors[g] <= 0 they stay 0.  The next palette of the refinement is the rounded mean
+ * (2*sum + count) / (2*count) of every entry with count > 0. */
+int gsdd_gif_palette_sums(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* palette, const int32_t* n_colors,
+                          uint32_t* sums, uint64_t* sse, void* stream);
+/* Floyd-Steinberg error diffusion (csrc/gif_refine.hip): palette, n_colors as gsdd_gif_map takes them -> out[B][T][H][W] uint8.  Every
+ * frame starts with no error, and errors outside the frame are 0: nothing is carried from frame to frame.  Pixels are visited left to
+ * right, rows top to bottom (no serpentine).  With e_c(y,x) the error of channel c left at pixel (y,x),
+ *   acc      = 7*e_c(y,x-1) + 3*e_c(y-1,x+1) + 5*e_c(y-1,x) + 1*e_c(y-1,x-1)
+ *   target_c = clamp(level_c + ((acc + 8) >> 4), 0, 255)          (>>: arithmetic, i.e. floor((acc + 8) / 16); level_c: the uint8 rule)
+ *   index    = the entry among 0 .. n_colors-1 nearest to target, as in gsdd_gif_map: integer squared distance, lowest index on ties
+ *   e_c(y,x) = target_c - palette[index]_c
+ * With n_colors[g] <= 0 the index is 0, as in gsdd_gif_map.  The result is exact and does not depend on how the kernel schedules the
+ * pixels (one workgroup per frame, one thread per row, each row two pixels behind the row above). */
+int gsdd_gif_diffuse(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* palette, const int32_t* n_colors,
+                     uint8_t* out, void* stream);
 /* The three entries below are HOST code on HOST pointers: nothing is launched, no stream. */
 /* Deterministic integer median cut of one histogram into at most `colors` (2 .. 256) boxes: start with one box of every occupied bin;
  * split the box with the largest pixel count among those with more than one occupied bin (ties: lowest index) along its axis of largest

@@ -4,7 +4,10 @@ the decoder returns them; a moving colour ramp with sigma-5 noise, so that neigh
 the three kernels (histogram, box sums, map without and with dither) with HIP events around each call, the whole quantize_clips (its
 device-to-host copy, the host's median cuts and the palette included) and the host's encode of the 16 files by the wall clock.
 Beside them, in the same run, the host baseline the export replaces: PIL's quantize(MEDIANCUT) per frame and save of the same clips
-from their uint8 frames (the copy to the host not counted).  Warm-up first, the cases in alternating rounds (a drift of the clocks
+from their uint8 frames (the copy to the host not counted).  The stages behind the median cut the same way: one assignment pass of
+the palette refinement (gsdd_gif_palette_sums), quantize_clips(refine=8) whole, the error diffusion (gsdd_gif_diffuse), and the path
+users had for it, PIL's quantize(palette=..., dither=FLOYDSTEINBERG) per frame on the host with the same palettes; the PSNR before and
+after the refinement comes from gif.palette_error.  Warm-up first, the cases in alternating rounds (a drift of the clocks
 hits all alike), the median over the rounds reported with the spread; a round that takes longer than the time limit ends the run with
 an error instead of hanging on.  usage: bench_gif.py [out.csv]"""
 import io
@@ -58,6 +61,10 @@ def main():
     box = torch.from_numpy(np.stack([ops.gif_median_cut(h, 256)[0] for h in hist.cpu().numpy().view(np.uint32)])).cuda()
     pal4 = torch.cat([pal, torch.zeros_like(pal[..., :1])], dim=-1).contiguous()
     sums = torch.empty((B, 256, 4), dtype=torch.int32, device="cuda")
+    sse = torch.empty((B,), dtype=torch.int64, device="cuda")
+    _, pal_refined, _ = gif.quantize_clips(clips, refine=8)
+    values = 3 * T * HW * HW
+    psnr = [[gif.psnr_from_sse(int(e), values) for e in gif.palette_error(clips, p, n).cpu()] for p in (pal, pal_refined)]
     out = torch.empty((B, T, HW, HW), dtype=torch.uint8, device="cuda")
     idx_h, pal_h, n_h = idx.cpu().numpy(), pal.cpu().numpy(), n.cpu().numpy()
     frames_h = levels.numpy()
@@ -74,11 +81,23 @@ def main():
             sizes.append(buf.tell())
         return sizes
 
+    def pil_fs_all():
+        for b in range(B):
+            ref = Image.new("P", (1, 1))
+            ref.putpalette(pal_h[b].reshape(-1).tolist())
+            for f in frames_h[b]:
+                Image.fromarray(f, "RGB").quantize(palette=ref, dither=Image.Dither.FLOYDSTEINBERG)
+
     cases = [("histogram", lambda: ops.gif_histogram(clips, out=hist), True),
              ("box_sums", lambda: ops.gif_box_sums(clips, box, out=sums), True),
              ("map", lambda: ops.gif_map(clips, pal4, n, out=out), True),
              ("map_dither32", lambda: ops.gif_map(clips, pal4, n, dither=32, out=out), True),
+             ("palette_sums", lambda: ops.gif_palette_sums(clips, pal4, n, out=sums, sse_out=sse), True),
+             ("diffuse", lambda: ops.gif_diffuse(clips, pal4, n, out=out), True),
              ("quantize_clips_wall", lambda: gif.quantize_clips(clips), False),
+             ("quantize_clips_refine8_wall", lambda: gif.quantize_clips(clips, refine=8), False),
+             ("quantize_clips_refine8_fs_wall", lambda: gif.quantize_clips(clips, refine=8, dither="fs"), False),
+             ("pil_floyd_steinberg_256_frames_host_wall", pil_fs_all, False),
              ("encode_16_files_host_wall", encode_all, False),
              ("pil_mediancut_save_16_files_host_wall", pil_all, False)]
     for _, fn, ev in cases:
@@ -93,6 +112,8 @@ def main():
         v = ms[name]
         lines.append(f"{name},{B},{B * T},{ROUNDS},{ITERS if ev else 1},{statistics.median(v):.4f},{min(v):.4f},{max(v):.4f}")
     lines.append(f"# bytes of the 16 files: {ours} (one palette per clip, no frame differencing) vs PIL {theirs} (one palette per frame, frame differencing)")
+    lines.append(f"# PSNR of the 16 clips against their uint8 frames, median cut -> refine=8: mean {statistics.mean(psnr[0]):.2f} -> "
+                 f"{statistics.mean(psnr[1]):.2f} dB, least gain {min(b - a for a, b in zip(*psnr)):.2f} dB")
     print("\n".join(lines))
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:

@@ -649,6 +649,30 @@ int main() {
         EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, nullptr, st), GSDD_E_ARG, false);
         EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, Hh, 0, pal + 2, ncol, 0, idx, st), GSDD_E_ARG, false);        // misaligned palette
         EXPECT(gsdd_gif_map(clips, Bv, Tv, Hh, 70000, 0, pal, ncol, 0, idx, st), GSDD_E_ARG, false);
+        // palette refinement and error diffusion (csrc/gif_refine.hip)
+        uint64_t* sse = devp<uint64_t>((size_t)Bv * Tv * 8);
+        for (int pf = 0; pf <= 1; ++pf) {
+            EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, pf, pal, ncol, sums, sse, st), GSDD_OK, true);
+            EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, pf, pal, ncol, idx, st), GSDD_OK, true);
+        }
+        EXPECT(gsdd_gif_diffuse(clips, 1, 1, 1, 65535, 0, pal, ncol, idx, st), GSDD_OK, true);                // one row, the widest
+        EXPECT(gsdd_gif_diffuse(clips, 1, 1, 65535, 1, 0, pal, ncol, idx, st), GSDD_OK, true);                // 64 bands of one column
+        EXPECT(gsdd_gif_diffuse(clips, 1, 1, 1025, 16368, 0, pal, ncol, idx, st), GSDD_OK, true);             // the longest band row
+        EXPECT(gsdd_gif_diffuse(clips, 1, 1, 1025, 16369, 0, pal, ncol, idx, st), GSDD_E_ARG, false);         // more than 2^24 pixels
+        EXPECT(gsdd_gif_palette_sums(clips, 1, 2, 4096, 4096, 0, pal, ncol, sums, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(nullptr, Bv, Tv, Hh, Hh, 0, pal, ncol, sums, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, nullptr, ncol, sums, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, pal, nullptr, sums, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, nullptr, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, sums, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, pal + 2, ncol, sums, sse, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_palette_sums(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, sums, (uint64_t*)((uint8_t*)sse + 4), st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(nullptr, Bv, Tv, Hh, Hh, 0, pal, ncol, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, 0, nullptr, ncol, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, 0, pal, nullptr, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, 0, pal, ncol, nullptr, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, 0, pal + 1, ncol, idx, st), GSDD_E_ARG, false);
+        EXPECT(gsdd_gif_diffuse(clips, Bv, Tv, Hh, Hh, 2, pal, ncol, idx, st), GSDD_E_ARG, false);
 
         // median cut on real host memory: a smooth ramp, every bin, one bin, nothing
         std::vector<uint32_t> h(32768, 0u);
