@@ -11,7 +11,9 @@
 // with zeros to a power of two of at least 2 entries; the NETSCAPE2.0 loop extension; per frame a graphic control extension
 // (disposal 1, the delay), an image descriptor and the LZW stream in sub-blocks of at most 255 bytes; the trailer.  LZW: minimum code
 // size max(2, bits), a clear code first, codes growing to 12 bits, a clear code and a table reset when the table holds 4096 entries,
-// the end-of-information code.  No frame differencing, no transparency.  Nothing is ever written at or behind out[cap].
+// the end-of-information code.  encode() writes whole frames without transparency; encode_delta() writes each frame's rectangle of
+// changed pixels with a transparent index for the pixels that keep their colour (the delta stage: csrc/gif_delta.hip).  Nothing is ever
+// written at or behind out[cap].
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -240,6 +242,89 @@ inline int64_t encode(const uint8_t* indices, int T, int H, int W, const uint8_t
         const int min_code = bits < 2 ? 2 : bits;
         w.put((uint8_t)min_code);
         clears += lzw_frame(w, indices + t * n, n, min_code);
+    }
+    w.put(0x3B);
+    if (clear_codes) *clear_codes = clears;
+    return w.pos <= cap ? w.pos : E_CAP;
+}
+
+// encode() for delta frames (gsdd_gif_delta's outputs): frame t is the sub-image rects[t] = x0, y0, x1, y1 (inclusive) of the full-frame
+// indices [T][H][W], read at stride W; the empty marker (W, H, -1, -1) is written as the 1 x 1 image at (0, 0).  transparent[n_palettes]:
+// the transparent index of each table's frames, -1 = none; a table covers it (max(n_colors, transparent + 1) entries before the
+// padding) and the graphic control extension names it.  Disposal 1, the LZW writer of encode(); encode_bound() holds.  E_ARG as
+// encode(), and for a rectangle that leaves the canvas or is inverted, a transparent index outside -1 .. 255 and an index of a
+// rectangle that is neither in front of n_colors nor the transparent one.
+inline int64_t encode_delta(const uint8_t* indices, int T, int H, int W, const uint8_t* palettes, const int32_t* n_colors, int n_palettes,
+                            const int32_t* rects, const int32_t* transparent, int delay_cs, int loop, uint8_t* out, int64_t cap,
+                            int64_t* clear_codes) {
+    if (!indices || !palettes || !n_colors || !rects || !transparent || !out) return E_ARG;
+    if (T <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || cap < 0) return E_ARG;
+    if ((n_palettes != 1 && n_palettes != T) || delay_cs < 0 || delay_cs > 65535 || loop < 0 || loop > 65535) return E_ARG;
+    for (int p = 0; p < n_palettes; ++p)
+        if (n_colors[p] < 1 || n_colors[p] > 256 || transparent[p] < -1 || transparent[p] > 255) return E_ARG;
+    const int64_t n = (int64_t)H * W;
+    const bool local = n_palettes > 1;
+    struct Rect { int x, y, w, h; };
+    std::vector<Rect> boxes((size_t)T);
+    for (int t = 0; t < T; ++t) {
+        const int32_t* r = rects + 4 * (int64_t)t;
+        if (r[0] == W && r[1] == H && r[2] == -1 && r[3] == -1) {
+            boxes[t] = {0, 0, 1, 1};
+        } else {
+            if (r[0] < 0 || r[1] < 0 || r[2] < r[0] || r[3] < r[1] || r[2] >= W || r[3] >= H) return E_ARG;
+            boxes[t] = {r[0], r[1], r[2] - r[0] + 1, r[3] - r[1] + 1};
+        }
+        const int nc = n_colors[local ? t : 0], tr = transparent[local ? t : 0];
+        for (int y = 0; y < boxes[t].h; ++y) {
+            const uint8_t* px = indices + t * n + (int64_t)(boxes[t].y + y) * W + boxes[t].x;
+            for (int x = 0; x < boxes[t].w; ++x)
+                if (px[x] >= nc && px[x] != tr) return E_ARG;
+        }
+    }
+    const auto entries = [&](int p) { return n_colors[p] > transparent[p] + 1 ? n_colors[p] : transparent[p] + 1; };
+    Writer w = {out, cap, 0};
+    w.bytes("GIF89a", 6);
+    w.put16(W);
+    w.put16(H);
+    const int gbits = table_bits(entries(0));
+    w.put(local ? (uint8_t)0x70 : (uint8_t)(0x80 | 0x70 | (gbits - 1)));
+    w.put(0);
+    w.put(0);
+    if (!local) w.table(palettes, n_colors[0], gbits);
+    w.put(0x21);
+    w.put(0xFF);
+    w.put(11);
+    w.bytes("NETSCAPE2.0", 11);
+    w.put(3);
+    w.put(1);
+    w.put16(loop);
+    w.put(0);
+    int64_t clears = 0;
+    std::vector<uint8_t> rows;
+    for (int t = 0; t < T; ++t) {
+        const int p = local ? t : 0;
+        const int bits = table_bits(entries(p));
+        const int tr = transparent[p];
+        const Rect& bx = boxes[t];
+        w.put(0x21);
+        w.put(0xF9);
+        w.put(4);
+        w.put((uint8_t)((1 << 2) | (tr >= 0 ? 1 : 0)));       // disposal 1 (leave in place), the transparency flag
+        w.put16(delay_cs);
+        w.put((uint8_t)(tr >= 0 ? tr : 0));
+        w.put(0);
+        w.put(0x2C);
+        w.put16(bx.x);
+        w.put16(bx.y);
+        w.put16(bx.w);
+        w.put16(bx.h);
+        w.put(local ? (uint8_t)(0x80 | (bits - 1)) : (uint8_t)0);
+        if (local) w.table(palettes + (int64_t)p * 768, n_colors[p], bits);
+        const int min_code = bits < 2 ? 2 : bits;
+        w.put((uint8_t)min_code);
+        rows.resize((size_t)bx.w * bx.h);
+        for (int y = 0; y < bx.h; ++y) memcpy(rows.data() + (size_t)y * bx.w, indices + t * n + (int64_t)(bx.y + y) * W + bx.x, (size_t)bx.w);
+        clears += lzw_frame(w, rows.data(), (int64_t)bx.w * bx.h, min_code);
     }
     w.put(0x3B);
     if (clear_codes) *clear_codes = clears;

@@ -8,10 +8,11 @@
       -> gsdd_gif_palette_sums       (refine = N > 0) N + 1 Lloyd assignment passes; the palette of smallest squared error is kept
       -> gsdd_gif_map                nearest palette entry per pixel (optional ordered dither), or
          gsdd_gif_diffuse            (dither = "fs") Floyd-Steinberg error diffusion within each frame
-      -> gsdd_gif_encode             (host) GIF89a file
+      -> gsdd_gif_delta              (optimize) per pixel the transparent index where the displayed colour stays; a box per frame
+      -> gsdd_gif_encode             (host) GIF89a file; gsdd_gif_encode_delta writes the delta frames
 
 Every stage is integer arithmetic behind one fp32 step (the evaluator's uint8 rule), so the indices, the palette and the file's bytes
-are exactly reproducible; tests/gif_ref.py and tests/gif_refine_ref.py restate all of it in numpy.
+are exactly reproducible; tests/gif_ref.py, tests/gif_refine_ref.py and tests/gif_delta_ref.py restate all of it in numpy.
 
 The way back is probe_gif / read_gif at the end of this file: a GIF file -> uint8 frames (T, H, W, 3) on the device.
 
@@ -129,33 +130,71 @@ def delay_centiseconds(fps):
     return delay
 
 
-def encode_gif(indices, palette, n_colors, fps=5, loop=0):
+def delta_frames(clips, indices, palette, n_colors, palette_mode="clip", tolerance=0):
+    """The delta stage behind quantize_clips (gsdd_gif_delta; the rule: include/gsdd.h): -> (out (B, T, H, W) uint8: `indices` with the
+    group's free index n_colors[g] wherever a pixel keeps the colour it shows -- or, with tolerance > 0 (a squared RGB distance, at most
+    195075), shows a colour within the tolerance of its level --, rects (B, T, 4) int32: the bounding box x0, y0, x1, y1 of each frame's
+    changed pixels, (W, H, -1, -1) for none, changed (B, T) int32: their number, transparent (G,) int32: n_colors[g], or -1 for a group
+    of 256 colours, whose frames are cropped only).  All on the device, no synchronisation.  palette (G, 256, 3) as quantize_clips
+    returns it, or (G, 256, 4)."""
+    if palette_mode not in ("clip", "frame"):
+        raise GsddError(f'delta_frames: palette_mode is "clip" or "frame", got {palette_mode!r}')
+    if not torch.is_tensor(palette) or palette.dim() != 3 or palette.shape[-1] not in (3, 4):
+        raise GsddError("delta_frames: palette must be uint8 (G, 256, 3) or (G, 256, 4)")
+    if palette.shape[-1] == 3:
+        palette = torch.cat([palette, torch.zeros_like(palette[..., :1])], dim=-1)
+    clips = clips.contiguous() if torch.is_tensor(clips) else clips
+    out, rects, changed = ops.gif_delta(clips, indices, palette.contiguous(), n_colors, palette_mode == "frame", tolerance)
+    return out, rects, changed, torch.where(n_colors < 256, n_colors, torch.full_like(n_colors, -1))
+
+
+def encode_gif(indices, palette, n_colors, fps=5, loop=0, rects=None, transparent=None):
     """One clip -> the bytes of a GIF89a file.  indices (T, H, W) uint8; palette (256, 3) with n_colors an int or a 1-element tensor (a
-    global colour table) or palette (T, 256, 3) with n_colors (T,) (one local table per frame); tensors on any device, or numpy."""
+    global colour table) or palette (T, 256, 3) with n_colors (T,) (one local table per frame); tensors on any device, or numpy.
+    rects (T, 4) and transparent (an int, or one per table), both or neither: one clip's delta frames (delta_frames) are written as
+    sub-images with a transparent index (gsdd_gif_encode_delta)."""
     def host(a):
         return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if (rects is None) != (transparent is None):
+        raise GsddError("encode_gif: rects and transparent come together (delta_frames returns both)")
     idx, pal = host(indices), host(palette)
     if pal.ndim == 2:
         pal = pal[None]
     n = np.asarray(host(n_colors), dtype=np.int32).reshape(-1)
-    data, _ = ops.gif_encode(idx, pal, n, delay_centiseconds(fps), loop)
+    if rects is None:
+        data, _ = ops.gif_encode(idx, pal, n, delay_centiseconds(fps), loop)
+    else:
+        data, _ = ops.gif_encode_delta(idx, pal, n, host(rects), np.asarray(host(transparent), dtype=np.int32).reshape(-1),
+                                       delay_centiseconds(fps), loop)
     return data
 
 
-def write_gifs(clips, paths, fps=5, loop=0, **quantize_kwargs):
+def write_gifs(clips, paths, fps=5, loop=0, optimize=False, tolerance=0, **quantize_kwargs):
     """Quantise clips (B, 3, T, H, W) and write clip b to paths[b] (directories are created).  -> (indices, palette, n_colors) of
-    quantize_clips."""
+    quantize_clips.  optimize: write delta frames (delta_frames) -- the same pictures in a smaller file; tolerance > 0 (with optimize
+    only) also keeps a pixel whose level is within that squared RGB distance of what it shows.  A group needs a free palette index for
+    transparency: `colors` stays as given, and a group that took all 256 gets cropping only (colors=255 leaves one free)."""
     paths = list(paths)
     if not torch.is_tensor(clips) or clips.dim() != 5 or len(paths) != clips.shape[0]:
         raise GsddError("write_gifs: one path per clip of (B, 3, T, H, W)")
+    if tolerance != 0 and not optimize:
+        raise GsddError("write_gifs: tolerance needs optimize=True")
     delay_centiseconds(fps)
     indices, palette, n_colors = quantize_clips(clips, **quantize_kwargs)
     B, T = indices.shape[:2]
-    idx, pal, n = indices.cpu().numpy(), palette.cpu().numpy(), n_colors.cpu().numpy()
+    pal, n = palette.cpu().numpy(), n_colors.cpu().numpy()
     per_frame = quantize_kwargs.get("palette", "clip") == "frame"
+    if optimize:
+        out, rects, _, transparent = delta_frames(clips, indices, palette, n_colors, "frame" if per_frame else "clip", tolerance)
+        idx, rects, transparent = out.cpu().numpy(), rects.cpu().numpy(), transparent.cpu().numpy()
+    else:
+        idx = indices.cpu().numpy()
     for b, path in enumerate(paths):
-        p, c = (pal[b * T:(b + 1) * T], n[b * T:(b + 1) * T]) if per_frame else (pal[b:b + 1], n[b:b + 1])
-        data, _ = ops.gif_encode(idx[b], p, c, delay_centiseconds(fps), loop)
+        rows = slice(b * T, (b + 1) * T) if per_frame else slice(b, b + 1)
+        if optimize:
+            data, _ = ops.gif_encode_delta(idx[b], pal[rows], n[rows], rects[b], transparent[rows], delay_centiseconds(fps), loop)
+        else:
+            data, _ = ops.gif_encode(idx[b], pal[rows], n[rows], delay_centiseconds(fps), loop)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "wb") as f:
             f.write(data)

@@ -744,6 +744,42 @@ def gif_diffuse(clips, palette, n_colors, per_frame=False, out=None, stream=None
     return out
 
 
+GIF_MAX_TOLERANCE = 3 * 255 * 255
+
+
+def gif_delta(clips, indices, palette, n_colors, per_frame=False, tolerance=0, out=None, rects=None, changed=None, stream=None):
+    """The delta stage: indices (B, T, H, W) uint8 of gif_map / gif_diffuse, palette (G, 256, 4) uint8, n_colors (G,) int32 on the
+    device -> (out (B, T, H, W) uint8: the group's transparent index n_colors[g] wherever the pixel keeps the colour it shows (or, with
+    tolerance > 0, shows one within that squared RGB distance of its level), rects (B, T, 4) int32: x0, y0, x1, y1 of the changed
+    pixels, (W, H, -1, -1) for none, changed (B, T) int32 holding uint32 counts) (gsdd_gif_delta; the rule in full: include/gsdd.h).
+    rects and changed are initialised by the call."""
+    if not isinstance(tolerance, int) or isinstance(tolerance, bool) or not 0 <= tolerance <= GIF_MAX_TOLERANCE:
+        raise GsddError(f"gif_delta: tolerance is an integer squared RGB distance in 0 .. {GIF_MAX_TOLERANCE}, got {tolerance!r}")
+    B, T, H, W, G = _gif_clips("gif_delta", clips, per_frame)
+    _gif_palette("gif_delta", palette, n_colors, G)
+    dev = clips.device
+
+    def buffer(name, t, dtype, shape):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise GsddError(f"gif_delta: {name} must be contiguous {dtype} {shape} on {dev}")
+        return t
+    if not torch.is_tensor(indices) or indices.dtype != torch.uint8 or tuple(indices.shape) != (B, T, H, W) or indices.device != dev \
+            or not indices.is_contiguous():
+        raise GsddError(f"gif_delta: indices must be contiguous uint8 {(B, T, H, W)} on {dev}")
+    if not clips.is_contiguous():
+        raise GsddError("gif_delta: clips must be contiguous")
+    out = buffer("out", out, torch.uint8, (B, T, H, W))
+    if out.data_ptr() == indices.data_ptr():
+        raise GsddError("gif_delta: out must not be indices")
+    rects = buffer("rects", rects, torch.int32, (B, T, 4))
+    changed = buffer("changed", changed, torch.int32, (B, T))
+    check(lib().gsdd_gif_delta(ptr(clips), ptr(indices), B, T, H, W, int(bool(per_frame)), ptr(palette), ptr(n_colors), tolerance, ptr(out),
+                               ptr(rects), ptr(changed), stream_ptr(stream)))
+    return out, rects, changed
+
+
 def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
 
@@ -788,6 +824,42 @@ def gif_encode(indices, palettes, n_colors, delay_cs, loop=0, cap=None):
                           _np_ptr(buf), cap, C.byref(clears))
     if buf[cap] != 0xA5:
         raise GsddError("gif_encode: the encoder wrote behind its buffer")
+    if n < 0:
+        check(int(n))
+    return buf[:n].tobytes(), clears.value
+
+
+def gif_encode_delta(indices, palettes, n_colors, rects, transparent, delay_cs, loop=0, cap=None):
+    """Host: gif_encode for delta frames -- indices (T, H, W) uint8 (gif_delta's out), rects (T, 4) int32 = x0, y0, x1, y1 of each
+    frame's sub-image ((W, H, -1, -1): none, written as 1 x 1), transparent (1 or T,) int32: each table's transparent index, -1 = none;
+    all numpy -> (the GIF89a file as bytes, the clear codes its LZW streams hold) (gsdd_gif_encode_delta)."""
+    import numpy as np
+    if not isinstance(indices, np.ndarray) or indices.dtype != np.uint8 or indices.ndim != 3:
+        raise GsddError("gif_encode_delta: indices must be a uint8 numpy array (T, H, W)")
+    T, H, W = indices.shape
+    if not isinstance(palettes, np.ndarray) or palettes.dtype != np.uint8 or palettes.ndim != 3 or palettes.shape[1:] != (256, 3) \
+            or palettes.shape[0] not in (1, T):
+        raise GsddError(f"gif_encode_delta: palettes must be uint8 (1 or {T}, 256, 3)")
+    n_colors = np.ascontiguousarray(n_colors, dtype=np.int32).reshape(-1)
+    transparent = np.ascontiguousarray(transparent, dtype=np.int32).reshape(-1)
+    if n_colors.shape[0] != palettes.shape[0] or transparent.shape[0] != palettes.shape[0]:
+        raise GsddError("gif_encode_delta: one colour count and one transparent index per palette")
+    rects = np.ascontiguousarray(rects, dtype=np.int32)
+    if rects.shape != (T, 4):
+        raise GsddError(f"gif_encode_delta: rects must be int32 {(T, 4)}")
+    indices, palettes = np.ascontiguousarray(indices), np.ascontiguousarray(palettes)
+    L = lib()
+    if cap is None:
+        cap = L.gsdd_gif_encode_bound(T, H, W)
+        if cap < 0:
+            check(int(cap))
+    buf = np.empty(cap + 1, dtype=np.uint8)
+    buf[cap] = 0xA5                                            # a guard byte behind the buffer
+    clears = C.c_int64(0)
+    n = L.gsdd_gif_encode_delta(_np_ptr(indices), T, H, W, _np_ptr(palettes), _np_ptr(n_colors), palettes.shape[0], _np_ptr(rects),
+                                _np_ptr(transparent), int(delay_cs), int(loop), _np_ptr(buf), cap, C.byref(clears))
+    if buf[cap] != 0xA5:
+        raise GsddError("gif_encode_delta: the encoder wrote behind its buffer")
     if n < 0:
         check(int(n))
     return buf[:n].tobytes(), clears.value

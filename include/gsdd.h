@@ -705,7 +705,7 @@ int gsdd_clip_vision_embed(const float* patches, const float* class_emb, const f
  * masked before the row maximum and the sum. */
 int gsdd_clip_attention(const float* qkv, int B, int S, int C, int n_head, float scale, float* out, void* stream);
 
-/* ------------------------------------------------------------------ GIF export of decoded clips (gif.py; csrc/gif.hip, csrc/gif_refine.hip, csrc/gif_host.hpp)
+/* ------------------------------------------------------------------ GIF export of decoded clips (gif.py; csrc/gif.hip, csrc/gif_refine.hip, csrc/gif_delta.hip, csrc/gif_host.hpp)
  * Colour quantisation on the device, median cut and the GIF89a / LZW writer on the host.  clips[B][3][T][H][W] f32 are the decoder's
  * ImageNet-normalised clips.  Each pixel's uint8 channels are formed by the evaluator's rule: v = (x*std[c] + mean[c]) * 255 in fp32
  * in that order, clamped to [0, 255] (NaN -> 0), truncated.  Everything after that step is integer arithmetic with integer atomics:
@@ -743,7 +743,29 @@ int gsdd_gif_palette_sums(const float* clips, int B, int T, int H, int W, int pe
  * pixels (one workgroup per frame, one thread per row, each row two pixels behind the row above). */
 int gsdd_gif_diffuse(const float* clips, int B, int T, int H, int W, int per_frame, const uint8_t* palette, const int32_t* n_colors,
                      uint8_t* out, void* stream);
-/* The three entries below are HOST code on HOST pointers: nothing is launched, no stream. */
+/* The delta stage between the quantiser and gsdd_gif_encode_delta (csrc/gif_delta.hip).  indices[B][T][H][W] uint8 from gsdd_gif_map or
+ * gsdd_gif_diffuse (any dither), palette and n_colors as gsdd_gif_map takes them, tolerance an integer squared RGB distance in
+ * 0 .. 195075 (3 * 255^2) -> out[B][T][H][W] uint8 (not `indices` itself), rects[B][T][4] int32 = x0, y0, x1, y1 inclusive,
+ * changed[B][T] uint32; rects and changed are initialised by the call.  The rule, for every pixel of the canvas on its own, with
+ * `shown` the RGB the pixel displays, for t = 0 .. T-1 and g the frame's group:
+ *   transparent(g) = n_colors[g] < 256 ? n_colors[g] : -1
+ *   c         = palette[g][indices_t]  (R, G, B)
+ *   level_t   = the uint8 rule of the pixel in frame t (no dither offset)
+ *   unchanged = t > 0 && (c == shown || (tolerance > 0 && transparent(g) >= 0 && d2(level_t, shown) <= tolerance))
+ *               (d2: the integer squared RGB distance of gsdd_gif_map)
+ *   out_t     = unchanged && transparent(g) >= 0 ? transparent(g) : indices_t
+ *   shown     = unchanged ? shown : c
+ * rects[b][t] is the bounding box of the pixels of frame t that are not unchanged -- all of frame 0; (W, H, -1, -1) for a frame without
+ * any -- and changed[b][t] their number.  What follows from the rule:
+ *   - colours are compared, not indices: duplicated palette entries and per-frame palettes behave;
+ *   - the tolerance compares a pixel with what is DISPLAYED, not with its level in the frame before: a slow drift is repainted once it
+ *     has left the tolerance, it does not creep away;
+ *   - with tolerance = 0 a file written from out, rects and transparent() by gsdd_gif_encode_delta decodes to exactly the frames of the
+ *     file gsdd_gif_encode writes from indices.  A group with 256 colours has no free index: its frames are cropped only.
+ * With tolerance = 0 `clips` is not read.  Exact, and independent of the order the workgroups run in. */
+int gsdd_gif_delta(const float* clips, const uint8_t* indices, int B, int T, int H, int W, int per_frame, const uint8_t* palette,
+                   const int32_t* n_colors, int tolerance, uint8_t* out, int32_t* rects, uint32_t* changed, void* stream);
+/* The entries below are HOST code on HOST pointers: nothing is launched, no stream. */
 /* Deterministic integer median cut of one histogram into at most `colors` (2 .. 256) boxes: start with one box of every occupied bin;
  * split the box with the largest pixel count among those with more than one occupied bin (ties: lowest index) along its axis of largest
  * extent in bin coordinates (ties R, G, B), after the first plane where twice the cumulative count reaches the box total (one plane
@@ -756,11 +778,23 @@ int64_t gsdd_gif_encode_bound(int T, int H, int W);
  * n_palettes = 1 is a global colour table, n_palettes = T one local table per frame; tables are padded with zeros to a power of two
  * of at least 2 entries.  delay_cs: centiseconds per frame, loop: NETSCAPE2.0 loop count (0 = for ever), both 0 .. 65535.  One graphic
  * control extension per frame (disposal 1), LZW with minimum code size max(2, bits), a clear code first and again whenever the table
- * holds 4096 entries; no frame differencing, no transparency.  *clear_codes (may be NULL): the clear codes written, all frames.
+ * holds 4096 entries; whole frames, no transparency (delta frames: gsdd_gif_encode_delta).  *clear_codes (may be NULL): the clear codes written, all frames.
  * Returns the byte count; GSDD_E_ARG for bad arguments (an index outside its table included); GSDD_E_CAP when cap is too small --
  * nothing is written at or behind out[cap] in any case. */
 int64_t gsdd_gif_encode(const uint8_t* indices, int T, int H, int W, const uint8_t* palettes, const int32_t* n_colors, int n_palettes,
                         int delay_cs, int loop, uint8_t* out, int64_t cap, int64_t* clear_codes);
+/* gsdd_gif_encode for delta frames: frame t is written as the sub-image rects[t] = x0, y0, x1, y1 (inclusive) of the full-frame
+ * indices[T][H][W] (gsdd_gif_delta's out), its rows read at stride W; the empty marker (W, H, -1, -1) is written as the 1 x 1 image at
+ * (0, 0).  transparent[n_palettes]: the transparent index of each table's frames, -1 = none: the graphic control extension carries the
+ * flag and the index (disposal 1), and the table covers the index -- max(n_colors, transparent + 1) entries, then padded to the power
+ * of two, from which the minimum code size follows.  The LZW writer is gsdd_gif_encode's and gsdd_gif_encode_bound bounds the result.
+ * With whole-frame rectangles and no transparent index the bytes are gsdd_gif_encode's.  GSDD_E_ARG as gsdd_gif_encode, and for a
+ * rectangle that leaves the canvas or is inverted (other than the empty marker), a transparent index outside -1 .. 255, and an index
+ * inside a rectangle that is neither below n_colors nor the transparent one; GSDD_E_CAP when cap is too small -- nothing is written at
+ * or behind out[cap] in any case. */
+int64_t gsdd_gif_encode_delta(const uint8_t* indices, int T, int H, int W, const uint8_t* palettes, const int32_t* n_colors,
+                              int n_palettes, const int32_t* rects, const int32_t* transparent, int delay_cs, int loop, uint8_t* out,
+                              int64_t cap, int64_t* clear_codes);
 
 /* ------------------------------------------------------------------ GIF import (gif.py; csrc/gif_read.hip, csrc/gif_read_host.hpp)
  * The host walks the file and decodes the LZW streams; the device composites the frame rectangles (transparency, disposal) onto the

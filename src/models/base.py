@@ -83,21 +83,26 @@ class BaseModel(_Base):
         return self.allsplit_epoch_end("test", outputs)
 
     # ---- GIF export of sampled clips (gsdd_amd.gif); off unless `render_dir` is set
-    render_dir, render_fps, render_max, render_refine, render_dither = None, 5, 16, 0, 0
+    render_dir, render_fps, render_max, render_refine, render_dither, render_optimize, render_tolerance = None, 5, 16, 0, 0, False, 0
 
-    def _render_setup(self, render_dir, render_fps, render_max, render_refine=0, render_dither=0):
+    def _render_setup(self, render_dir, render_fps, render_max, render_refine=0, render_dither=0, render_optimize=False, render_tolerance=0):
         self.render_dir = str(render_dir) if render_dir not in (None, "", "__None__") else None
         self.render_fps, self.render_max = render_fps, int(render_max)
         # the quantiser's k-means passes (0 .. 32) and dither (an ordered-dither amplitude 0 .. 64, or "fs"): gsdd_amd.gif.quantize_clips
         self.render_refine, self.render_dither = render_refine, render_dither
+        # delta frames (transparent pixels where the picture stays, cropped frames) and their tolerance, a squared RGB distance:
+        # gsdd_amd.gif.write_gifs(optimize=, tolerance=)
+        self.render_optimize, self.render_tolerance = bool(render_optimize), int(render_tolerance)
         self._rendered = 0                                       # clips written by the test split so far
 
     def _write_gifs(self, clips, directory, names, captions):
         """clips (N, 3, T, H, W) on the device -> <directory>/<name> each, and one `<name>\\t<caption>` line each in captions.txt"""
         import os
         from gsdd_amd.gif import write_gifs
+        # with delta frames every group keeps one palette index free for the transparent pixels: 255 colours
+        optimize = dict(optimize=True, tolerance=self.render_tolerance, colors=255) if self.render_optimize else {}
         write_gifs(clips.detach().float(), [os.path.join(directory, n) for n in names], fps=self.render_fps,
-                   refine=self.render_refine, dither=self.render_dither)
+                   refine=self.render_refine, dither=self.render_dither, **optimize)
         with open(os.path.join(directory, "captions.txt"), "a") as f:
             for n, c in zip(names, captions):
                 f.write(f"{n}\t{' '.join(str(c).split())}\n")

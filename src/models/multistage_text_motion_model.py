@@ -52,9 +52,9 @@ class MultistageTextMotionModel(BaseModel):
                  checkpoint_paths=None, evaluator=None, freeze_models_dict=None, lr_args={}, render_animations=True,
                  do_evaluation=False, devices="cpu", autoencoder_train_mode=False, step_in_eval_splits=False, native_step=False,
                  native_optim=None, sample_with_ema=True, use_ema=False, render_dir=None, render_fps=5, render_max=16, render_refine=0,
-                 render_dither=0, **kwargs):
+                 render_dither=0, render_optimize=False, render_tolerance=0, **kwargs):
         super().__init__()
-        self._render_setup(render_dir, render_fps, render_max, render_refine, render_dither)
+        self._render_setup(render_dir, render_fps, render_max, render_refine, render_dither, render_optimize, render_tolerance)
         self.gpu_device = devices if devices == "cpu" else "cuda:" + str(devices[0])
         self.generator = instantiate(generator, device=self.gpu_device, _recursive_=False) if isinstance(generator, dict) else generator
         self.autoencoder = instantiate(autoencoder, device=self.gpu_device, _recursive_=False) \

@@ -746,6 +746,96 @@ int main() {
         EXPECT((int)gsdd_gif_encode(px.data(), Te, He, We, table.data(), full, 1, 20, 0, nullptr, cap, nullptr), GSDD_E_ARG, false);
         EXPECT((int)gsdd_gif_encode_bound(0, He, We), GSDD_E_ARG, false);
         EXPECT((int)gsdd_gif_encode_bound(1, 65536, We), GSDD_E_ARG, false);
+
+        // the delta stage (csrc/gif_delta.hip): the device entry's checks ...
+        {
+            int32_t* rects = devp<int32_t>((size_t)Bv * Tv * 16);
+            uint32_t* changed = devp<uint32_t>((size_t)Bv * Tv * 4);
+            uint8_t* dout = devp<uint8_t>((size_t)Bv * Tv * Hh * Hh);
+            for (int pf = 0; pf <= 1; ++pf)
+                for (int tol : {0, 1, 195075}) EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, pf, pal, ncol, tol, dout, rects, changed, st), GSDD_OK, true);
+            EXPECT(gsdd_gif_delta(clips, idx, 1, 300, 5, 3, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_OK, true);
+            EXPECT(gsdd_gif_delta(clips, idx, 1, 1, 4096, 4096, 1, pal, ncol, 48, dout, rects, changed, st), GSDD_OK, true);    // 2^24 pixels
+            EXPECT(gsdd_gif_delta(clips, idx, 1, 2, 4096, 4096, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, 1, 1, 1, 65536, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, 0, Tv, Hh, Hh, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 2, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            for (int bad : {-1, 195076}) EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, bad, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(nullptr, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, nullptr, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, nullptr, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, nullptr, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, nullptr, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, dout, nullptr, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, dout, rects, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal + 2, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, idx, rects, changed, st), GSDD_E_ARG, false);       // out is indices
+        }
+        // ... and its encoder, which RUNS here: two frames of 7 x 5 in a buffer of exactly T H W bytes (a row read past a rectangle or past
+        // the last frame is a report), frame 1 with the empty marker and then with a one-pixel rectangle in the last corner
+        {
+            const int Td = 2, Hd = 5, Wd = 7;
+            std::vector<uint8_t> dpx((size_t)Td * Hd * Wd);
+            for (size_t i = 0; i < dpx.size(); ++i) dpx[i] = (uint8_t)(i % 3);
+            for (size_t i = (size_t)Hd * Wd; i < dpx.size(); ++i) dpx[i] = 3;                                    // frame 1: all transparent
+            const int32_t nc3[1] = {3}, tr3[1] = {3}, none[1] = {-1}, nc2[2] = {3, 3}, tr2[2] = {-1, 3};
+            int32_t boxes[8] = {0, 0, Wd - 1, Hd - 1, Wd, Hd, -1, -1};
+            std::vector<uint8_t> dbig((size_t)gsdd_gif_encode_bound(Td, Hd, Wd));
+            auto delta_exact = [&](const int32_t* nc, const int32_t* tr, int npal) {
+                int64_t clears = -1;
+                const int64_t n = gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc, npal, boxes, tr, 20, 0, dbig.data(), (int64_t)dbig.size(), &clears);
+                ++g_checked;
+                if (n <= 0 || clears != Td) { std::fprintf(stderr, "FAIL gsdd_gif_encode_delta -> %lld [%s]\n", (long long)n, gsdd_last_error()); ++g_failed; return; }
+                std::vector<uint8_t> exact((size_t)n), shorter((size_t)n - 1);
+                ++g_checked;
+                if (gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc, npal, boxes, tr, 20, 0, exact.data(), n, nullptr) != n ||
+                    std::memcmp(exact.data(), dbig.data(), (size_t)n) != 0) { std::fprintf(stderr, "FAIL gsdd_gif_encode_delta at the exact size\n"); ++g_failed; }
+                ++g_checked;
+                if (gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc, npal, boxes, tr, 20, 0, shorter.data(), n - 1, nullptr) != GSDD_E_CAP) {
+                    std::fprintf(stderr, "FAIL gsdd_gif_encode_delta one byte short\n"); ++g_failed; }
+                // what it wrote is a GIF the library's own decoder takes: two frames, frame 1 with the rectangle asked for
+                int64_t info[8] = {0};
+                ++g_checked;
+                if (gsdd_gif_probe(exact.data(), n, info) != GSDD_OK || info[0] != Wd || info[1] != Hd || info[2] != Td) {
+                    std::fprintf(stderr, "FAIL gsdd_gif_probe of the delta file [%s]\n", gsdd_last_error()); ++g_failed; }
+            };
+            dpx[(size_t)Hd * Wd] = 0;                                                                           // the pixel the 1 x 1 image of an empty frame shows
+            delta_exact(nc3, tr3, 1);                                                                            // the empty marker, a global table
+            delta_exact(nc2, tr2, 2);                                                                            // local tables, one without a transparent index
+            boxes[4] = Wd - 1, boxes[5] = Hd - 1, boxes[6] = Wd - 1, boxes[7] = Hd - 1;                          // one pixel, the canvas's last
+            dpx.back() = 1;
+            delta_exact(nc3, tr3, 1);
+            delta_exact(nc3, none, 1);                                                                           // (every index 3 is outside the rectangle: not read)
+            const int64_t dcap = (int64_t)dbig.size();
+            auto bad_box = [&](int x0, int y0, int x1, int y1) {
+                const int32_t b[8] = {0, 0, Wd - 1, Hd - 1, x0, y0, x1, y1};
+                EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, b, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            };
+            bad_box(0, 0, Wd, 0);                                                                                // leaves the canvas
+            bad_box(0, 0, 0, Hd);
+            bad_box(-1, 0, 2, 2);
+            bad_box(3, 0, 2, 2);                                                                                 // inverted
+            bad_box(0, 3, 2, 2);
+            bad_box(Wd, Hd, -1, 0);                                                                              // half an empty marker
+            const int32_t tr_hi[1] = {256}, tr_lo[1] = {-2}, nc1[1] = {1}, tr255[1] = {255}, zero[1] = {0}, many[1] = {257};
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr_hi, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr_lo, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc1, 1, boxes, tr255, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);  // index beyond its table
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), zero, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), many, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), 3, Hd, Wd, table.data(), nc2, 2, boxes, tr2, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);    // 2 palettes, 3 frames
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr3, -1, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr3, 20, 65536, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), 0, Hd, Wd, table.data(), nc3, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, 65536, table.data(), nc3, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr3, 20, 0, dbig.data(), -1, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(nullptr, Td, Hd, Wd, table.data(), nc3, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, nullptr, nc3, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nullptr, 1, boxes, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, nullptr, tr3, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, nullptr, 20, 0, dbig.data(), dcap, nullptr), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_gif_encode_delta(dpx.data(), Td, Hd, Wd, table.data(), nc3, 1, boxes, tr3, 20, 0, nullptr, dcap, nullptr), GSDD_E_ARG, false);
+        }
     }
 
     // ---------------------------------------------------------------- GIF import: the decoder of FOREIGN bytes RUNS here, on exact-size heap copies
