@@ -5,7 +5,7 @@ The directory name carries a hyphen, so import it through the root-level ``gsdd_
     import gsdd_amd
     vq = gsdd_amd.VQVAE(...).cuda().eval()
 """
-from . import gif, ops  # noqa: F401
+from . import gif, metrics, ops  # noqa: F401
 from ._lib import GsddError, LIB_PATH, EXPORTS, lib  # noqa: F401
 from .d3pm import (DalleMaskImageEmbedding, DiffusionTransformer, DiscreteDiffusion,  # noqa: F401
                    Text2ImageTransformer, cond_drop_rows)

@@ -30,6 +30,7 @@ EXPORTS = [
     "gsdd_gif_histogram", "gsdd_gif_box_sums", "gsdd_gif_map", "gsdd_gif_median_cut", "gsdd_gif_encode_bound", "gsdd_gif_encode",
     "gsdd_gif_probe", "gsdd_gif_decode", "gsdd_gif_compose", "gsdd_gif_palette_sums", "gsdd_gif_diffuse",
     "gsdd_gif_delta", "gsdd_gif_encode_delta",
+    "gsdd_paired_metrics", "gsdd_paired_metrics_tiles",
 ]
 
 _p = C.c_void_p
@@ -239,6 +240,9 @@ def lib():
         L.gsdd_gif_delta.argtypes = [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p]
         L.gsdd_gif_encode_delta.argtypes = [_p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i64, C.POINTER(_i64)]   # (host pointers)
         L.gsdd_gif_encode_delta.restype = _i64
+        L.gsdd_paired_metrics_tiles.argtypes = [_i, _i]
+        L.gsdd_paired_metrics_tiles.restype = _i64
+        L.gsdd_paired_metrics.argtypes = [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p]
         L.gsdd_gif_probe.argtypes = [_p, _i64, _p]                                # (host pointers)
         L.gsdd_gif_decode.argtypes = [_p, _i64, _p, _p, _p, _p, _i64]             # (host pointers)
         L.gsdd_gif_compose.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _p]      # (select_host: a host pointer)

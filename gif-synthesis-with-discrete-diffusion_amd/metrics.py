@@ -18,6 +18,35 @@ def clip_similarity(text_embeds, frame_embeds, eps=1e-12):
     return (f * t[:, None, :]).sum(dim=-1).mean(dim=1)
 
 
+def _frame_psnr(sse, values):
+    """sse (B, T, 3) int64 -> (B, T) fp64 on the host: 10 log10(255^2 values / sum_c sse), inf where the frame has no error"""
+    from .gif import psnr_from_sse
+    total = sse.sum(dim=-1).cpu()
+    return torch.tensor([psnr_from_sse(v, values) for v in total.flatten().tolist()], dtype=torch.float64).view(total.shape)
+
+
+def paired_frame_metrics(pred, target):
+    """PSNR and SSIM of every frame of `pred` against the same frame of `target`, on their uint8 levels.  Either operand is float32
+    (B, 3, T, H, W), ImageNet-normalised as the decoder returns it (levels by the evaluator's rule: (x std + mean) 255 in fp32,
+    truncated, clamped, NaN -> 0), or uint8 (B, T, H, W, 3) as read_gif and palette[indices] give it; both on a ROCm device, H, W >= 11.
+    -> {"psnr": (B, T) fp64 dB over the frame's three channels, inf for a frame equal to its target, "ssim": (B, T) fp64, the mean over
+    the channels of the Gaussian-window SSIM (Wang et al. 2004: 11 x 11, sigma 1.5, valid windows, data range 255), "sse": (B, T, 3)
+    int64}, all on the host.  The per-pixel work is one HIP kernel (ops.paired_metrics; the rule in full: include/gsdd.h), the rest is
+    torch on (B, T, 3) numbers in fp64.  SSIM is UNSCALED, in [-1, 1]."""
+    from . import ops
+    sse, ssim = ops.paired_metrics(pred, target, want_ssim=True)
+    H, W = (pred.shape[3], pred.shape[4]) if pred.dtype == torch.float32 else (pred.shape[2], pred.shape[3])
+    return {"psnr": _frame_psnr(sse, 3 * H * W), "ssim": ssim.cpu().sum(dim=-1) / 3.0, "sse": sse.cpu()}
+
+
+def psnr(pred, target):
+    """The PSNR of paired_frame_metrics alone, (B, T) fp64 on the host: no SSIM is formed, so any H, W >= 1 is taken."""
+    from . import ops
+    sse, _ = ops.paired_metrics(pred, target, want_ssim=False)
+    H, W = (pred.shape[3], pred.shape[4]) if pred.dtype == torch.float32 else (pred.shape[2], pred.shape[3])
+    return _frame_psnr(sse, 3 * H * W)
+
+
 def _sym_sqrt(mat, eps=1e-10):
     """U diag(sqrt(s)) V^T with singular values below eps left as they are (evaluator.py:119-122)."""
     u, s, vh = torch.linalg.svd(mat)

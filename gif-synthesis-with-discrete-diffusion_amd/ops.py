@@ -865,6 +865,63 @@ def gif_encode_delta(indices, palettes, n_colors, rects, transparent, delay_cs, 
     return buf[:n].tobytes(), clears.value
 
 
+# ----------------------------------------------------------------------------- paired video metrics (metrics.py)
+def _paired_operand(name, x):
+    """-> (form, (B, T, H, W)) of one operand: 0 = float32 (B, 3, T, H, W), 1 = uint8 (B, T, H, W, 3)"""
+    if torch.is_tensor(x) and x.dim() == 5 and x.dtype == torch.float32 and x.shape[1] == 3:
+        form, shape = 0, (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
+    elif torch.is_tensor(x) and x.dim() == 5 and x.dtype == torch.uint8 and x.shape[4] == 3:
+        form, shape = 1, tuple(x.shape[:4])
+    else:
+        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+        raise GsddError(f"paired_metrics: {name} must be float32 (B, 3, T, H, W) or uint8 (B, T, H, W, 3), got {got}")
+    if not x.is_cuda:
+        raise GsddError(f"paired_metrics: {name} must live on a ROCm device (no CPU fallback)")
+    if not x.is_contiguous():
+        raise GsddError(f"paired_metrics: {name} must be contiguous")
+    return form, tuple(int(v) for v in shape)
+
+
+def paired_metrics_tiles(H, W):
+    """the tiles a plane of H x W is cut into: the length of the partials' tile axis (gsdd_paired_metrics_tiles)"""
+    n = lib().gsdd_paired_metrics_tiles(int(H), int(W))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def paired_metrics(a, b, want_ssim=True, partials=None, stream=None):
+    """Two clips, each float32 (B, 3, T, H, W) ImageNet-normalised (its levels by the uint8 rule) or uint8 (B, T, H, W, 3), of the same
+    B, T, H, W -> (sse (B, T, 3) int64: the squared error of the levels per frame and channel, exact; ssim (B, T, 3) float64: the mean
+    SSIM of the plane's 11 x 11 Gaussian windows, or None without want_ssim, which then takes any H, W instead of >= 11)
+    (gsdd_paired_metrics; the rule in full: include/gsdd.h).  partials: the kernel's per-tile results, int32
+    (B*T*3, paired_metrics_tiles(H, W), 2); every word is written by the call.  The finish is a sum over the tile axis."""
+    form_a, shape = _paired_operand("a", a)
+    form_b, shape_b = _paired_operand("b", b)
+    if shape != shape_b or a.device != b.device:
+        raise GsddError(f"paired_metrics: a is (B, T, H, W) = {shape} on {a.device}, b {shape_b} on {b.device}")
+    B, T, H, W = shape
+    if min(shape) < 1:
+        raise GsddError(f"paired_metrics: empty operands {shape}")
+    want_ssim = bool(want_ssim)
+    if want_ssim and (H < 11 or W < 11):
+        raise GsddError(f"paired_metrics: SSIM needs H and W of at least 11, got {H} x {W} (want_ssim=False gives the squared error alone)")
+    planes, tiles = B * T * 3, paired_metrics_tiles(H, W)
+    if partials is None:
+        partials = torch.zeros((planes, tiles, 2), dtype=torch.int32, device=a.device)
+    elif not torch.is_tensor(partials) or partials.dtype != torch.int32 or tuple(partials.shape) != (planes, tiles, 2) \
+            or partials.device != a.device or not partials.is_contiguous():
+        raise GsddError(f"paired_metrics: partials must be contiguous int32 {(planes, tiles, 2)} on {a.device}")
+    check(lib().gsdd_paired_metrics(ptr(a), form_a, ptr(b), form_b, B, T, H, W, int(want_ssim), ptr(partials), stream_ptr(stream)))
+    sse = partials[:, :, 0].sum(dim=1, dtype=torch.int64).view(B, T, 3)
+    if not want_ssim:
+        return sse, None
+    # (a DEVICE divisor: torch divides by a host scalar as a multiplication by its reciprocal, and n * (1 / n) is not always 1)
+    windows = torch.full((), float((H - 10) * (W - 10)), dtype=torch.float64, device=a.device)
+    ssim = partials.view(torch.float32)[:, :, 1].sum(dim=1, dtype=torch.float64) / windows
+    return sse, ssim.view(B, T, 3)
+
+
 # ----------------------------------------------------------------------------- GIF import (gif.py)
 GIF_INFO = ("width", "height", "frames", "palettes", "raster_bytes", "loop", "global_table", "version")
 

@@ -830,6 +830,39 @@ int gsdd_gif_decode(const uint8_t* data, int64_t n, int32_t* frames, int32_t* de
 int gsdd_gif_compose(const uint8_t* raster, const int32_t* frames, const uint8_t* palettes, int F, int W, int H, const int32_t* select,
                      const int32_t* select_host, int T_out, int matte_rgb, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ paired video metrics (metrics.py; csrc/paired_metrics.hip)
+ * Squared error and SSIM of two clips, per (clip, frame, channel) plane, on their uint8 levels.  The operands a and b share B, T, H, W;
+ * each is, on its own, in one of two forms:
+ *   form 0   float32 planar [B][3][T][H][W], ImageNet-normalised as the decoder returns it; a level is the uint8 rule of the GIF export
+ *            above: v = (x*std[c] + mean[c]) * 255 in fp32 in that order, truncated, clamped to [0, 255], NaN -> 0;
+ *   form 1   uint8 interleaved [B][T][H][W][3] (gsdd_gif_compose's out, palette[indices]); a level is the byte.
+ * SSE    sse[b][t][c] = sum over y, x of (a - b)^2 on the levels: an exact integer.
+ * SSIM   (Wang et al. 2004, per channel, "valid" windows, data range 255)
+ *   window   w[i][j] = g[i] g[j], g[i] ~ exp(-(i - 5)^2 / (2 * 1.5^2)) for i = 0 .. 10, normalised in fp64 and THEN rounded to fp32;
+ *            these eleven fp32 values, widened again, are the rule (g[10 - i] = g[i]):
+ *              g[0..5] = 0x1.0d956cp-10, 0x1.f1fe02p-8, 0x1.26eb18p-5, 0x1.bff0fep-4, 0x1.b43c4p-3, 0x1.10656p-2
+ *   positions every window with its corner at 0 <= y <= H - 11, 0 <= x <= W - 11: (H - 10)(W - 10) of them, no padding
+ *   moments  mu_a, mu_b the weighted means sum w a, sum w b; var_a, var_b, cov the weighted second moments about them
+ *            sum w (a - mu_a)^2, sum w (b - mu_b)^2, sum w (a - mu_a)(b - mu_b).  Nothing is divided by sum w = 1 - 2.8e-9, so
+ *            sum w (a - mu_a)^2 = sum w a a - (2 - sum w) mu_a^2: at mu = 255 the factor moves s by 3e-6, it is part of the rule
+ *   C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2
+ *   s        = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2))
+ *   ssim[b][t][c] = the mean of s over the plane's windows.
+ * Frame PSNR = 10 log10(255^2 * 3 H W / sum_c sse) (inf for no error) and frame SSIM = the mean over c are the caller's, in fp64.
+ * The entry leaves the last sum to the caller too: a workgroup handles one 16 x 16 tile of window positions of one plane, and
+ * partials[B*T*3][tiles][2] int32 (plane = (b*T + t)*3 + c; tiles = gsdd_paired_metrics_tiles(H, W) = n(H) n(W) with n(v) = 1 for
+ * v <= 26 and ceil((v - 10) / 16) above, GSDD_E_ARG for a size below 1; rows of tiles top to bottom) gets
+ * per tile {the squared error of the pixels the tile owns -- every pixel has one owner, the sum over the tiles is sse --, the bits of
+ * the fp32 sum of s over the tile's windows}.  Every word is written by exactly one workgroup: nothing has to be zeroed, there are no
+ * atomics and no memset (safe to capture), and the bits are the same in every run and whatever else the batch holds.  The moments are
+ * accumulated in fp64 (every product level x level x weight is exact there), so a window's s is good to about 1e-11 and a tile's sum
+ * to its one rounding to fp32; identical operands give s = 1.0 and ssim = 1.0 exactly.  With want_ssim = 0 only the integers are
+ * formed (the second word is written as 0.0f) and any H, W >= 1 is taken; with want_ssim = 1, H < 11 or W < 11 is GSDD_E_ARG, as are
+ * a form other than 0 / 1, sizes below 1, a plane of 2^31 pixels or more, and 2^31 workgroups or more -- before any launch. */
+int64_t gsdd_paired_metrics_tiles(int H, int W);
+int gsdd_paired_metrics(const void* a, int form_a, const void* b, int form_b, int B, int T, int H, int W, int want_ssim,
+                        int32_t* partials, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */
 int gsdd_graph_begin(void* stream);

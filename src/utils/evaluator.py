@@ -11,11 +11,19 @@ CLIPSIM (not in the reference; text-to-video work on MSR-VTT reports it next to 
 sampled clips against `batch["text"]` -- the mean over frames of the cosine between the caption's CLIP text feature and each frame's
 CLIP image feature (gsdd_amd.metrics.clip_similarity, unscaled) -- and evaluate_metrics returns {'fvd': ..., 'clipsim': ...}, the mean
 over every sample pushed.  The image tower is gsdd_amd.vision.ClipVisionTower on the HIP kernels; its preprocessing is torch's bicubic
-on the quantised frames, not the `clip` package's PIL resize.  Without a scorer nothing of this runs and the dict is {'fvd': ...}."""
+on the quantised frames, not the `clip` package's PIL resize.  Without a scorer nothing of this runs and the dict is {'fvd': ...}.
+
+PSNR and SSIM (not in the reference; what reconstruction, prediction, interpolation and inpainting work reports per frame): with
+`paired_metrics` on, push_vals also scores every frame of `outputs` against the same frame of `batch["video"]` on their uint8 levels
+(gsdd_amd.metrics.paired_frame_metrics: one HIP kernel per push) and evaluate_metrics adds {'psnr': ..., 'ssim': ...}: the mean over
+every sample pushed and over the frames `paired_from_frame` .. T - 1, so that the conditioning frames of a prediction run
+(`sample_condition_frames=N paired_from_frame=N`) stay out of the scalar.  A frame identical to its target has a PSNR of inf, and so
+has a mean that contains one.  frame_curves() gives the per-frame means over the samples, all T frames.  Off by default: nothing new
+runs and the dict is what it was."""
 import torch
 
 from gsdd_amd.hydra_lite import instantiate
-from gsdd_amd.metrics import clip_similarity, frechet_distance
+from gsdd_amd.metrics import clip_similarity, frechet_distance, paired_frame_metrics
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
@@ -71,8 +79,12 @@ def clip_scorer_from_pretrained(weights, device="cuda"):
 
 
 class Evaluator:
-    def __init__(self, device, videoencoder, checkpoint_paths=None, target_resolution=224, clip_scorer=None):
+    def __init__(self, device, videoencoder, checkpoint_paths=None, target_resolution=224, clip_scorer=None, paired_metrics=False,
+                 paired_from_frame=0):
         self.device, self.target_resolution = device, target_resolution
+        if not isinstance(paired_from_frame, int) or isinstance(paired_from_frame, bool) or paired_from_frame < 0:
+            raise ValueError(f"Evaluator: paired_from_frame is a frame number >= 0, got {paired_from_frame!r}")
+        self.paired_metrics, self.paired_from_frame = bool(paired_metrics), paired_from_frame
         if isinstance(clip_scorer, dict):
             clip_scorer = instantiate(clip_scorer, _recursive_=False)
         self.clip_scorer = clip_scorer
@@ -89,6 +101,7 @@ class Evaluator:
     def reset(self):
         self.all_video_embeds_generated, self.all_video_embeds_gt = [], []
         self.all_clip_scores = []
+        self.all_frame_psnr, self.all_frame_ssim = [], []
 
     def _prepare(self, clips):
         """evaluator.py:42-70: undo the ImageNet normalisation, quantise to uint8, preprocess at 224 (x2: [-1, 1]-ish range),
@@ -108,6 +121,29 @@ class Evaluator:
         self.all_video_embeds_gt.append(self.videoencoder(self._prepare(batch["video"])).float().cpu())
         if self.clip_scorer is not None:
             self.all_clip_scores.append(self.clip_scorer(batch["text"], outputs))
+        if self.paired_metrics:
+            got = paired_frame_metrics(self._levels_operand(outputs), self._levels_operand(batch["video"]))
+            self.all_frame_psnr.append(got["psnr"])
+            self.all_frame_ssim.append(got["ssim"])
+
+    def _levels_operand(self, clips):
+        """clips as the kernel takes them: float32 (B, 3, T, H, W) (or uint8 frames as they are), contiguous, on the evaluator's device"""
+        x = clips.detach().to(self.device)
+        return (x if x.dtype == torch.uint8 else x.float()).contiguous()
+
+    def _paired(self):
+        psnr, ssim = torch.cat(self.all_frame_psnr), torch.cat(self.all_frame_ssim)             # (samples, T) fp64 on the host
+        if self.paired_from_frame >= psnr.shape[1]:
+            raise ValueError(f"Evaluator: paired_from_frame = {self.paired_from_frame} leaves none of the clips' {psnr.shape[1]} frames")
+        return psnr, ssim
+
+    def frame_curves(self):
+        """{'psnr': (T,), 'ssim': (T,)} fp64: per frame number the mean over every sample pushed (all frames, whatever
+        paired_from_frame says) -- the curve prediction papers plot.  A frame number at which any sample equals its target has inf."""
+        if not self.paired_metrics:
+            raise ValueError("Evaluator.frame_curves: the evaluator was built without paired_metrics")
+        psnr, ssim = self._paired()
+        return {"psnr": psnr.mean(dim=0), "ssim": ssim.mean(dim=0)}
 
     def evaluate_metrics(self, val_dataset=None, generator=None):
         gen = torch.cat(self.all_video_embeds_generated).flatten(1)
@@ -115,4 +151,8 @@ class Evaluator:
         metrics = {"fvd": float(frechet_distance(gen, gt))}
         if self.clip_scorer is not None:
             metrics["clipsim"] = float(torch.cat(self.all_clip_scores).mean())
+        if self.paired_metrics:
+            psnr, ssim = self._paired()
+            metrics["psnr"] = float(psnr[:, self.paired_from_frame:].mean())
+            metrics["ssim"] = float(ssim[:, self.paired_from_frame:].mean())
         return metrics

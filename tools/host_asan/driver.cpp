@@ -771,6 +771,44 @@ int main() {
             EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal + 2, ncol, 0, dout, rects, changed, st), GSDD_E_ARG, false);
             EXPECT(gsdd_gif_delta(clips, idx, Bv, Tv, Hh, Hh, 0, pal, ncol, 0, idx, rects, changed, st), GSDD_E_ARG, false);       // out is indices
         }
+        // paired video metrics (csrc/paired_metrics.hip): every form pairing launches once; the checks return before a launch
+        {
+            int32_t* parts = devp<int32_t>();
+            const uint8_t* bytes = idx;                                                                          // a uint8 operand: any alignment
+            for (int fa = 0; fa <= 1; ++fa)
+                for (int fb = 0; fb <= 1; ++fb)
+                    for (int ssim = 0; ssim <= 1; ++ssim)
+                        EXPECT(gsdd_paired_metrics(fa ? (const void*)(bytes + 1) : (const void*)clips, fa, fb ? (const void*)bytes : (const void*)clips, fb,
+                                                   Bv, Tv, Hh, Hh, ssim, parts, st), GSDD_OK, true);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 11, 11, 1, parts, st), GSDD_OK, true);         // one window
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 1, 1, 0, parts, st), GSDD_OK, true);           // the squared error alone: any plane
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 2, 3, 5, 3, 0, parts, st), GSDD_OK, true);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 46340, 46340, 0, parts, st), GSDD_OK, true);   // just below 2^31 pixels
+            EXPECT((int)gsdd_paired_metrics_tiles(128, 128), 64, false);
+            EXPECT((int)gsdd_paired_metrics_tiles(10, 3), 1, false);
+            EXPECT((int)gsdd_paired_metrics_tiles(0, 3), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_paired_metrics_tiles(3, -1), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 10, 16, 1, parts, st), GSDD_E_ARG, false);     // SSIM needs 11 x 11
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 16, 10, 1, parts, st), GSDD_E_ARG, false);
+            for (int bad : {-1, 2}) {
+                EXPECT(gsdd_paired_metrics(clips, bad, bytes, 1, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_paired_metrics(clips, 0, bytes, bad, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+                EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, Hh, Hh, bad, parts, st), GSDD_E_ARG, false);
+            }
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 0, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, -1, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, 0, Hh, 0, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, Hh, 0, 0, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1, 1, 65536, 32768, 0, parts, st), GSDD_E_ARG, false);      // 2^31 pixels in a plane
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1 << 30, 3, Hh, Hh, 0, parts, st), GSDD_E_ARG, false);      // 9 * 2^30 planes
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, 1 << 16, 1 << 8, 128, 128, 1, parts, st), GSDD_E_ARG, false);   // 2^31 workgroups and more
+            EXPECT(gsdd_paired_metrics(nullptr, 0, bytes, 1, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, nullptr, 1, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, Hh, Hh, 1, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(bytes + 2, 0, bytes, 1, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);     // a float operand off its alignment
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes + 1, 0, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, Hh, Hh, 1, (int32_t*)(bytes + 2), st), GSDD_E_ARG, false);
+        }
         // ... and its encoder, which RUNS here: two frames of 7 x 5 in a buffer of exactly T H W bytes (a row read past a rectangle or past
         // the last frame is a report), frame 1 with the empty marker and then with a one-pixel rectangle in the last corner
         {
