@@ -31,6 +31,7 @@ EXPORTS = [
     "gsdd_gif_probe", "gsdd_gif_decode", "gsdd_gif_compose", "gsdd_gif_palette_sums", "gsdd_gif_diffuse",
     "gsdd_gif_delta", "gsdd_gif_encode_delta",
     "gsdd_paired_metrics", "gsdd_paired_metrics_tiles",
+    "gsdd_lpips_stem_rows", "gsdd_lpips_distance_slots", "gsdd_lpips_layer_distance",
 ]
 
 _p = C.c_void_p
@@ -243,6 +244,10 @@ def lib():
         L.gsdd_paired_metrics_tiles.argtypes = [_i, _i]
         L.gsdd_paired_metrics_tiles.restype = _i64
         L.gsdd_paired_metrics.argtypes = [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p]
+        L.gsdd_lpips_stem_rows.argtypes = [_p, _i, _i, _i, _i, _i, _i64, _i64, _i, _p, _p, _p]
+        L.gsdd_lpips_distance_slots.argtypes = [_i64, _i]
+        L.gsdd_lpips_distance_slots.restype = _i64
+        L.gsdd_lpips_layer_distance.argtypes = [_p, _p, _i64, _i64, _i, _p, _p]
         L.gsdd_gif_probe.argtypes = [_p, _i64, _p]                                # (host pointers)
         L.gsdd_gif_decode.argtypes = [_p, _i64, _p, _p, _p, _p, _i64]             # (host pointers)
         L.gsdd_gif_compose.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _p]      # (select_host: a host pointer)

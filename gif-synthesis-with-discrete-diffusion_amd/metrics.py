@@ -25,18 +25,24 @@ def _frame_psnr(sse, values):
     return torch.tensor([psnr_from_sse(v, values) for v in total.flatten().tolist()], dtype=torch.float64).view(total.shape)
 
 
-def paired_frame_metrics(pred, target):
+def paired_frame_metrics(pred, target, lpips=None):
     """PSNR and SSIM of every frame of `pred` against the same frame of `target`, on their uint8 levels.  Either operand is float32
     (B, 3, T, H, W), ImageNet-normalised as the decoder returns it (levels by the evaluator's rule: (x std + mean) 255 in fp32,
     truncated, clamped, NaN -> 0), or uint8 (B, T, H, W, 3) as read_gif and palette[indices] give it; both on a ROCm device, H, W >= 11.
     -> {"psnr": (B, T) fp64 dB over the frame's three channels, inf for a frame equal to its target, "ssim": (B, T) fp64, the mean over
     the channels of the Gaussian-window SSIM (Wang et al. 2004: 11 x 11, sigma 1.5, valid windows, data range 255), "sse": (B, T, 3)
     int64}, all on the host.  The per-pixel work is one HIP kernel (ops.paired_metrics; the rule in full: include/gsdd.h), the rest is
-    torch on (B, T, 3) numbers in fp64.  SSIM is UNSCALED, in [-1, 1]."""
+    torch on (B, T, 3) numbers in fp64.  SSIM is UNSCALED, in [-1, 1].
+    lpips: a gsdd_amd.lpips.Lpips scorer on the operands' device, or None.  With one the dict also holds "lpips": (B, T) fp64, the
+    frame pairs' LPIPS (unscaled, >= 0, 0 for equal frames), and the frames must reach the net's smallest side (31 for alex, 16 for
+    vgg); without one nothing of it runs and the dict is the three entries above."""
     from . import ops
     sse, ssim = ops.paired_metrics(pred, target, want_ssim=True)
     H, W = (pred.shape[3], pred.shape[4]) if pred.dtype == torch.float32 else (pred.shape[2], pred.shape[3])
-    return {"psnr": _frame_psnr(sse, 3 * H * W), "ssim": ssim.cpu().sum(dim=-1) / 3.0, "sse": sse.cpu()}
+    out = {"psnr": _frame_psnr(sse, 3 * H * W), "ssim": ssim.cpu().sum(dim=-1) / 3.0, "sse": sse.cpu()}
+    if lpips is not None:
+        out["lpips"] = lpips(pred, target)["lpips"]
+    return out
 
 
 def psnr(pred, target):

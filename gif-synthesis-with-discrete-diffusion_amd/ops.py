@@ -922,6 +922,64 @@ def paired_metrics(a, b, want_ssim=True, partials=None, stream=None):
     return sse, ssim.view(B, T, 3)
 
 
+# ----------------------------------------------------------------------------- LPIPS (lpips.py)
+def lpips_stem_rows(x, table, padw, frame0=0, n=None, out=None, stream=None):
+    """Frames frame0 .. frame0 + n - 1 (frame = b T + t; all of them by default) of a clip in either of paired_metrics' operand forms ->
+    float32 (n, H, W + 2 padw, 4): per pixel the three values table[c][level] and 0, the padw columns in front of and behind every row 0
+    -- the first convolution's operand with kw merged into the contraction (gsdd_lpips_stem_rows; the rule: include/gsdd.h).  table:
+    float32 (3, 256) on the device (lpips.stem_table()).  Every float of `out` is written."""
+    form, (B, T, H, W) = _paired_operand("x", x)
+    n = B * T - frame0 if n is None else n
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (3, 256) or table.device != x.device \
+            or not table.is_contiguous():
+        raise GsddError(f"lpips_stem_rows: table must be contiguous float32 (3, 256) on {x.device}")
+    shape = (int(n), H, W + 2 * int(padw), 4)
+    if min(shape) < 1 or padw < 0:
+        raise GsddError(f"lpips_stem_rows: nothing to write for n = {n}, padw = {padw} on frames of {H} x {W}")
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=x.device)
+    elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != x.device \
+            or not out.is_contiguous():
+        raise GsddError(f"lpips_stem_rows: out must be contiguous float32 {shape} on {x.device}")
+    check(lib().gsdd_lpips_stem_rows(ptr(x), form, B, T, H, W, int(frame0), int(n), int(padw), ptr(table), ptr(out), stream_ptr(stream)))
+    return out
+
+
+def lpips_distance_slots(P, C_):
+    """the workgroups one frame pair's P positions of C_ channels are cut into: the partials' slot axis (gsdd_lpips_distance_slots)"""
+    s = lib().gsdd_lpips_distance_slots(int(P), int(C_))
+    if s < 0:
+        check(int(s))
+    return int(s)
+
+
+def lpips_layer_distance(feat, w, n, partials=None, stream=None):
+    """feat: float32 rows (2 n P, C) of one tap, channels last, the n pred frames first and then the n target frames; w: float32 (C,)
+    -> (n,) float64 on the device: the mean over the P positions of sum_c w_c (a^_c - b^_c)^2 with a^ = a / (sqrt(sum a^2) + 1e-10)
+    (gsdd_lpips_layer_distance; the rule: include/gsdd.h).  partials: the kernel's per-workgroup sums, float64
+    (n, lpips_distance_slots(P, C)); every word is written by the call.  The finish is a sum over the slot axis and a division by P."""
+    if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 2 or not feat.is_cuda or not feat.is_contiguous():
+        raise GsddError("lpips_layer_distance: feat must be contiguous float32 rows (2 n P, C) on a ROCm device (no CPU fallback)")
+    rows, C_ = int(feat.shape[0]), int(feat.shape[1])
+    n = int(n)
+    if n < 1 or rows < 1 or rows % (2 * n) != 0:
+        raise GsddError(f"lpips_layer_distance: {rows} rows do not hold 2 x {n} frames of equally many positions")
+    if C_ % 4 != 0 or not 4 <= C_ <= 512:
+        raise GsddError(f"lpips_layer_distance: C = {C_} is not a multiple of 4 in 4 .. 512")
+    if not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (C_,) or w.device != feat.device or not w.is_contiguous():
+        raise GsddError(f"lpips_layer_distance: w must be contiguous float32 ({C_},) on {feat.device}")
+    P = rows // (2 * n)
+    slots = lpips_distance_slots(P, C_)
+    if partials is None:
+        partials = torch.zeros((n, slots), dtype=torch.float64, device=feat.device)
+    elif not torch.is_tensor(partials) or partials.dtype != torch.float64 or tuple(partials.shape) != (n, slots) \
+            or partials.device != feat.device or not partials.is_contiguous():
+        raise GsddError(f"lpips_layer_distance: partials must be contiguous float64 {(n, slots)} on {feat.device}")
+    check(lib().gsdd_lpips_layer_distance(ptr(feat), ptr(w), n, P, C_, ptr(partials), stream_ptr(stream)))
+    # (a DEVICE divisor, as in paired_metrics)
+    return partials.sum(dim=1) / torch.full((), float(P), dtype=torch.float64, device=feat.device)
+
+
 # ----------------------------------------------------------------------------- GIF import (gif.py)
 GIF_INFO = ("width", "height", "frames", "palettes", "raster_bytes", "loop", "global_table", "version")
 

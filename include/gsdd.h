@@ -863,6 +863,43 @@ int64_t gsdd_paired_metrics_tiles(int H, int W);
 int gsdd_paired_metrics(const void* a, int form_a, const void* b, int form_b, int B, int T, int H, int W, int want_ssim,
                         int32_t* partials, void* stream);
 
+/* ------------------------------------------------------------------ LPIPS (gsdd_amd/lpips.py; csrc/lpips.hip)
+ * LPIPS v0.1 (Zhang et al. 2018, "The Unreasonable Effectiveness of Deep Features as a Perceptual Metric"), net = alex or vgg, per frame
+ * pair of two clips in gsdd_paired_metrics' operand forms (form 0: float32 planar, a level by the uint8 rule; form 1: uint8 interleaved).
+ *   1. input    x = level / 127.5 - 1, then (x - shift[c]) / scale[c] with shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450).
+ *               Only 3 x 256 values exist, so the rule IS the table
+ *                 table[c * 256 + level] = (float)((level / 127.5 - 1.0 - shift[c]) / scale[c])     evaluated in fp64, rounded once,
+ *               which the caller forms on the host and hands over.  The first convolution pads with ZERO IN THE SCALED SPACE (not with
+ *               level 0, which maps to about -2.1).
+ *   2. towers   torchvision's `features`: ReLU after every convolution, max pools in floor mode without padding.
+ *                 alex  conv 3->64 k11 s4 p2 | pool 3 s2 | conv 64->192 k5 p2 | pool 3 s2 | conv 192->384 k3 p1 | conv 384->256 k3 p1 |
+ *                       conv 256->256 k3 p1; taps: the five ReLU outputs, C = (64, 192, 384, 256, 256); frames of 31 x 31 and above
+ *                 vgg   VGG-16's thirteen k3 p1 convolutions, pool 2 s2 behind the 2nd, 4th, 7th and 10th; taps: relu1_2, 2_2, 3_3, 4_3,
+ *                       5_3, C = (64, 128, 256, 512, 512); frames of 16 x 16 and above
+ *               (gsdd_gemm with bias + ReLU epilogue and gsdd_pool3d; the layer table is data in gsdd_amd/lpips.py).
+ *   3. per tap k, over the P positions of the tap's map: a^ = a / (sqrt(sum_c a_c^2) + 1e-10), the same for b (eps OUTSIDE the root: an
+ *               all-zero feature vector gives 0, not NaN), d_k = (1 / P) sum_p sum_c w_kc (a^_c - b^_c)^2 with the learned w_k >= 0
+ *               (lin{k}.model.1.weight).  LPIPS = sum_k d_k: unscaled, >= 0, 0 for equal frames.
+ *
+ * gsdd_lpips_stem_rows: frames frame0 .. frame0 + n - 1 (frame = b T + t) of x -> out[n][H][W + 2 padw][4] floats, the first
+ * convolution's operand with kw merged into the contraction (rows of 4 floats per pixel = the three table values and 0; the padw
+ * columns in front of and behind a row are 0; the convolution's taps then run over kh alone, each a run of kw * 4 floats).  Every
+ * float of out is written.  GSDD_E_ARG before the launch for a null pointer, a form other than 0 / 1, sizes below 1, padw outside
+ * 0 .. 64, frames outside the clips, a float operand or table off 4-byte alignment, out off 16-byte alignment.
+ *
+ * gsdd_lpips_layer_distance: feat[2 n P][C] channels-last rows of one tap -- the n pred frames first, then the n target frames -- and
+ * w[C] -> partials[n][slots] doubles, slots = gsdd_lpips_distance_slots(P, C) = ceil(P / (32 * 64 / G)) with G = min(64, the power
+ * of two at or above C / 4) the lanes that share a position.  partials[i][s] is sum_c w_c (a^_c - b^_c)^2 summed over the positions
+ * of slot s of frame pair i; d = (sum over s) / P is the caller's, in fp64.  Elements are read once as float4s and normalised by a
+ * multiplication with 1 / (sqrt(sum) + 1e-10) in fp32; sums over positions are fp64.  Every word of partials is written by exactly one
+ * workgroup: no atomics, nothing to zero (safe to capture), the same bits in every run and whatever else the batch holds; equal halves
+ * give exactly 0.  GSDD_E_ARG before the launch for a null pointer, C not a multiple of 4 in 4 .. 512, n or P below 1, 2 n P of 2^31
+ * or more, feat or w off 16-byte alignment, partials off 8-byte alignment. */
+int gsdd_lpips_stem_rows(const void* x, int form, int B, int T, int H, int W, int64_t frame0, int64_t n, int padw, const float* table,
+                         float* out, void* stream);
+int64_t gsdd_lpips_distance_slots(int64_t P, int C);
+int gsdd_lpips_layer_distance(const float* feat, const float* w, int64_t n, int64_t P, int C, double* partials, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture of a step
  * (the 100-iteration loop at diffusion_transformer.py:621-626 becomes 100 replays). */
 int gsdd_graph_begin(void* stream);

@@ -19,7 +19,13 @@ PSNR and SSIM (not in the reference; what reconstruction, prediction, interpolat
 every sample pushed and over the frames `paired_from_frame` .. T - 1, so that the conditioning frames of a prediction run
 (`sample_condition_frames=N paired_from_frame=N`) stay out of the scalar.  A frame identical to its target has a PSNR of inf, and so
 has a mean that contains one.  frame_curves() gives the per-frame means over the samples, all T frames.  Off by default: nothing new
-runs and the dict is what it was."""
+runs and the dict is what it was.
+
+LPIPS (not in the reference; reported next to PSNR and SSIM): with `lpips_scorer` set -- a gsdd_amd.lpips.Lpips, e.g. from
+`lpips_from_pretrained` -- push_vals also scores every frame of `outputs` against the same frame of `batch["video"]` (AlexNet or VGG-16
+features and the learned distance heads on the HIP kernels; the weights are the user's to supply) and evaluate_metrics adds
+{'lpips': ...}, the mean over every sample pushed and over the frames `paired_from_frame` .. T - 1; frame_curves() gains 'lpips'.  It
+needs neither `paired_metrics` nor the other scorer.  Unscaled, >= 0, lower is closer.  Without a scorer nothing of this runs."""
 import torch
 
 from gsdd_amd.hydra_lite import instantiate
@@ -78,9 +84,17 @@ def clip_scorer_from_pretrained(weights, device="cuda"):
     return ClipSimScorer(text, tower)
 
 
+def lpips_from_pretrained(weights, net="alex", device="cuda"):
+    """A gsdd_amd.lpips.Lpips scorer from LOCAL weights: one file with a full `lpips.LPIPS(net=...)` state dict, or a directory with
+    the lpips package's `<net>.pth` and torchvision's `alexnet.pth` / `vgg16.pth` (gsdd_amd.lpips.Lpips.from_pretrained).  Nothing is ever
+    fetched.  Usable as a `_target_` of configs/model/evaluator.yaml's `lpips_scorer`."""
+    from gsdd_amd.lpips import Lpips
+    return Lpips.from_pretrained(weights, net).to(device)
+
+
 class Evaluator:
     def __init__(self, device, videoencoder, checkpoint_paths=None, target_resolution=224, clip_scorer=None, paired_metrics=False,
-                 paired_from_frame=0):
+                 paired_from_frame=0, lpips_scorer=None):
         self.device, self.target_resolution = device, target_resolution
         if not isinstance(paired_from_frame, int) or isinstance(paired_from_frame, bool) or paired_from_frame < 0:
             raise ValueError(f"Evaluator: paired_from_frame is a frame number >= 0, got {paired_from_frame!r}")
@@ -88,6 +102,9 @@ class Evaluator:
         if isinstance(clip_scorer, dict):
             clip_scorer = instantiate(clip_scorer, _recursive_=False)
         self.clip_scorer = clip_scorer
+        if isinstance(lpips_scorer, dict):
+            lpips_scorer = instantiate(lpips_scorer, _recursive_=False)
+        self.lpips_scorer = lpips_scorer
         self.videoencoder = instantiate(videoencoder, _recursive_=False) if isinstance(videoencoder, dict) else videoencoder
         if checkpoint_paths and checkpoint_paths != "__None__":
             self.videoencoder.load_state_dict(torch.load(checkpoint_paths, map_location="cpu", weights_only=True))
@@ -102,6 +119,7 @@ class Evaluator:
         self.all_video_embeds_generated, self.all_video_embeds_gt = [], []
         self.all_clip_scores = []
         self.all_frame_psnr, self.all_frame_ssim = [], []
+        self.all_frame_lpips = []
 
     def _prepare(self, clips):
         """evaluator.py:42-70: undo the ImageNet normalisation, quantise to uint8, preprocess at 224 (x2: [-1, 1]-ish range),
@@ -125,25 +143,34 @@ class Evaluator:
             got = paired_frame_metrics(self._levels_operand(outputs), self._levels_operand(batch["video"]))
             self.all_frame_psnr.append(got["psnr"])
             self.all_frame_ssim.append(got["ssim"])
+        if self.lpips_scorer is not None:
+            got = self.lpips_scorer(self._levels_operand(outputs), self._levels_operand(batch["video"]))
+            self.all_frame_lpips.append(torch.as_tensor(got["lpips"]).to(torch.float64).cpu())
 
     def _levels_operand(self, clips):
         """clips as the kernel takes them: float32 (B, 3, T, H, W) (or uint8 frames as they are), contiguous, on the evaluator's device"""
         x = clips.detach().to(self.device)
         return (x if x.dtype == torch.uint8 else x.float()).contiguous()
 
-    def _paired(self):
-        psnr, ssim = torch.cat(self.all_frame_psnr), torch.cat(self.all_frame_ssim)             # (samples, T) fp64 on the host
-        if self.paired_from_frame >= psnr.shape[1]:
-            raise ValueError(f"Evaluator: paired_from_frame = {self.paired_from_frame} leaves none of the clips' {psnr.shape[1]} frames")
-        return psnr, ssim
+    def _paired(self, *lists):
+        out = tuple(torch.cat(v) for v in lists)                                                # (samples, T) fp64 on the host
+        if self.paired_from_frame >= out[0].shape[1]:
+            raise ValueError(f"Evaluator: paired_from_frame = {self.paired_from_frame} leaves none of the clips' {out[0].shape[1]} frames")
+        return out
 
     def frame_curves(self):
-        """{'psnr': (T,), 'ssim': (T,)} fp64: per frame number the mean over every sample pushed (all frames, whatever
-        paired_from_frame says) -- the curve prediction papers plot.  A frame number at which any sample equals its target has inf."""
-        if not self.paired_metrics:
-            raise ValueError("Evaluator.frame_curves: the evaluator was built without paired_metrics")
-        psnr, ssim = self._paired()
-        return {"psnr": psnr.mean(dim=0), "ssim": ssim.mean(dim=0)}
+        """{'psnr': (T,), 'ssim': (T,)} fp64 (with paired_metrics) and {'lpips': (T,)} (with an lpips_scorer): per frame number the mean
+        over every sample pushed (all frames, whatever paired_from_frame says) -- the curve prediction papers plot.  A frame number at
+        which any sample equals its target has a PSNR of inf."""
+        if not self.paired_metrics and self.lpips_scorer is None:
+            raise ValueError("Evaluator.frame_curves: the evaluator was built without paired_metrics and without an lpips_scorer")
+        curves = {}
+        if self.paired_metrics:
+            psnr, ssim = self._paired(self.all_frame_psnr, self.all_frame_ssim)
+            curves.update(psnr=psnr.mean(dim=0), ssim=ssim.mean(dim=0))
+        if self.lpips_scorer is not None:
+            curves["lpips"] = self._paired(self.all_frame_lpips)[0].mean(dim=0)
+        return curves
 
     def evaluate_metrics(self, val_dataset=None, generator=None):
         gen = torch.cat(self.all_video_embeds_generated).flatten(1)
@@ -152,7 +179,9 @@ class Evaluator:
         if self.clip_scorer is not None:
             metrics["clipsim"] = float(torch.cat(self.all_clip_scores).mean())
         if self.paired_metrics:
-            psnr, ssim = self._paired()
+            psnr, ssim = self._paired(self.all_frame_psnr, self.all_frame_ssim)
             metrics["psnr"] = float(psnr[:, self.paired_from_frame:].mean())
             metrics["ssim"] = float(ssim[:, self.paired_from_frame:].mean())
+        if self.lpips_scorer is not None:
+            metrics["lpips"] = float(self._paired(self.all_frame_lpips)[0][:, self.paired_from_frame:].mean())
         return metrics

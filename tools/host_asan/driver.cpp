@@ -809,6 +809,61 @@ int main() {
             EXPECT(gsdd_paired_metrics(clips, 0, bytes + 1, 0, Bv, Tv, Hh, Hh, 1, parts, st), GSDD_E_ARG, false);
             EXPECT(gsdd_paired_metrics(clips, 0, bytes, 1, Bv, Tv, Hh, Hh, 1, (int32_t*)(bytes + 2), st), GSDD_E_ARG, false);
         }
+        // LPIPS (csrc/lpips.hip): the stem operand in both forms and the distance head at every tap width; the checks return before a launch
+        {
+            const uint8_t* bytes = idx;
+            const float* table = devp();
+            float *rows = devp(), *feat = devp(), *w = devp();
+            double* parts = devp<double>();
+            const int64_t frames = (int64_t)Bv * Tv;
+            for (int form = 0; form <= 1; ++form)
+                for (int padw : {0, 1, 2, 64})
+                    EXPECT(gsdd_lpips_stem_rows(form ? (const void*)(bytes + 1) : (const void*)clips, form, Bv, Tv, Hh, Hh, 0, frames, padw, table, rows, st),
+                           GSDD_OK, true);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, 1, 1, frames - 1, 1, 0, table, rows, st), GSDD_OK, true);          // the last frame alone
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, 1, 1, 46340, 46340, 0, 1, 2, table, rows, st), GSDD_OK, true);             // just below 2^31 pixels
+            for (int bad : {-1, 2}) EXPECT(gsdd_lpips_stem_rows(clips, bad, Bv, Tv, Hh, Hh, 0, frames, 2, table, rows, st), GSDD_E_ARG, false);
+            for (int bad : {-1, 65}) EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, frames, bad, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, 0, Tv, Hh, Hh, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, -1, Hh, Hh, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, 0, Hh, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, 0, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, -1, 1, 2, table, rows, st), GSDD_E_ARG, false);            // frames outside the clips
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, 0, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 1, frames, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, frames, 1, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, INT64_MAX, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, 1, 1, 65536, 32768, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);         // 2^31 pixels in a frame
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, 1 << 16, 1 << 15, Hh, Hh, 0, 1, 2, table, rows, st), GSDD_E_ARG, false);   // 2^31 frames
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, 1 << 15, 1 << 15, 2048, 2048, 0, 1 << 29, 2, table, rows, st), GSDD_E_ARG, false);   // too many workgroups
+            EXPECT(gsdd_lpips_stem_rows(nullptr, 0, Bv, Tv, Hh, Hh, 0, frames, 2, table, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, frames, 2, nullptr, rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, frames, 2, table, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(bytes + 2, 0, Bv, Tv, Hh, Hh, 0, frames, 2, table, rows, st), GSDD_E_ARG, false);    // a float operand off its alignment
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, frames, 2, (const float*)(bytes + 1), rows, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_stem_rows(clips, 0, Bv, Tv, Hh, Hh, 0, frames, 2, table, rows + 1, st), GSDD_E_ARG, false);    // out needs 16 bytes
+            for (int C : {4, 64, 128, 192, 256, 384, 512})
+                for (int64_t P : {(int64_t)1, (int64_t)961, (int64_t)16384})
+                    EXPECT(gsdd_lpips_layer_distance(feat, w, frames, P, C, parts, st), GSDD_OK, true);
+            EXPECT((int)gsdd_lpips_distance_slots(961, 64), 8, false);
+            EXPECT((int)gsdd_lpips_distance_slots(33, 512), 2, false);
+            EXPECT((int)gsdd_lpips_distance_slots(2048, 4), 1, false);
+            EXPECT((int)gsdd_lpips_distance_slots(0, 64), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_lpips_distance_slots(5, 6), GSDD_E_ARG, false);
+            EXPECT((int)gsdd_lpips_distance_slots(5, 516), GSDD_E_ARG, false);
+            for (int bad : {0, -4, 2, 6, 516, 1024}) EXPECT(gsdd_lpips_layer_distance(feat, w, frames, 961, bad, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, 0, 961, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, frames, 0, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, 1 << 15, 1 << 15, 64, parts, st), GSDD_E_ARG, false);                 // 2^31 rows
+            EXPECT(gsdd_lpips_layer_distance(feat, w, (int64_t)1 << 40, 1, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, 1, (int64_t)1 << 40, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(nullptr, w, frames, 961, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, nullptr, frames, 961, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, frames, 961, 64, nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat + 1, w, frames, 961, 64, parts, st), GSDD_E_ARG, false);                  // rows are read as float4s
+            EXPECT(gsdd_lpips_layer_distance(feat, w + 2, frames, 961, 64, parts, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_lpips_layer_distance(feat, w, frames, 961, 64, (double*)(rows + 1), st), GSDD_E_ARG, false);
+        }
         // ... and its encoder, which RUNS here: two frames of 7 x 5 in a buffer of exactly T H W bytes (a row read past a rectangle or past
         // the last frame is a report), frame 1 with the empty marker and then with a one-pixel rectangle in the last corner
         {
