@@ -2,6 +2,7 @@
 the moment any operator is used (importing the package on a box without the .so still works so that
 CPU-only host logic — configs, weight repacking — can be tested)."""
 import ctypes as C
+import numbers
 import os
 
 import torch
@@ -32,6 +33,7 @@ EXPORTS = [
     "gsdd_gif_delta", "gsdd_gif_encode_delta",
     "gsdd_paired_metrics", "gsdd_paired_metrics_tiles",
     "gsdd_lpips_stem_rows", "gsdd_lpips_distance_slots", "gsdd_lpips_layer_distance",
+    "gsdd_d3pm_window_slide", "gsdd_clip_window_blend",
 ]
 
 _p = C.c_void_p
@@ -120,11 +122,17 @@ AXIAL_AUTO, AXIAL_VALU = 0, 1
 ATTN_AUTO, ATTN_P22, ATTN_P11, ATTN_A8, ATTN_A12, ATTN_F32PV, ATTN_KC256 = range(7)
 ATTN_NOLEAN = 256        # flag, OR-ed into an ATTN_* mode
 LAYER_AUTO, LAYER_X3P, LAYER_H2 = 0, 2, 3
+BLEND_LINEAR, BLEND_KEEP, BLEND_REPLACE = range(3)
 ATTN_BWD_AUTO, ATTN_BWD_VALU, ATTN_BWD_SPLIT, ATTN_BWD_FQC64, ATTN_BWD_FQC128, ATTN_BWD_NW8, ATTN_BWD_DBG1, ATTN_BWD_DBG2 = range(8)
 
 
 class GsddError(RuntimeError):
     pass
+
+
+def _is_int(v):
+    """An integer that is no bool: what every argument check of the package means by "an int"."""
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
 
 def lib():
@@ -248,6 +256,8 @@ def lib():
         L.gsdd_lpips_distance_slots.argtypes = [_i64, _i]
         L.gsdd_lpips_distance_slots.restype = _i64
         L.gsdd_lpips_layer_distance.argtypes = [_p, _p, _i64, _i64, _i, _p, _p]
+        L.gsdd_d3pm_window_slide.argtypes = [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _p]
+        L.gsdd_clip_window_blend.argtypes = [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]
         L.gsdd_gif_probe.argtypes = [_p, _i64, _p]                                # (host pointers)
         L.gsdd_gif_decode.argtypes = [_p, _i64, _p, _p, _p, _p, _i64]             # (host pointers)
         L.gsdd_gif_compose.argtypes = [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _p]      # (select_host: a host pointer)

@@ -11,7 +11,7 @@ int deterministic() { return g_deterministic.load(std::memory_order_relaxed); }
 using namespace gsdd;
 
 extern "C" const char* gsdd_last_error(void) { return g_err.c_str(); }
-extern "C" int gsdd_version(void) { return 116; }
+extern "C" int gsdd_version(void) { return 117; }
 extern "C" int gsdd_set_deterministic(int on) { return g_deterministic.exchange(on != 0 ? 1 : 0); }
 extern "C" int64_t gsdd_abi_sizeof(int which) {
     switch (which) {

@@ -4,7 +4,7 @@ state_dict keys, computing on gfx950 through the C ABI.
 Reference: src/models/motionencoder/{dalle_mask_image_embedding,transformer_utils,diffusion_transformer}.py and
 src/models/networks/discrete_diffusion.py.  The nn.Module tree only owns parameters under the
 reference's names.  A sampling chain is a program: the tuple of op kinds a plan lists in order of
-execution ("step", "jump", "reveal", "final").  Every op of a kind is the same launch sequence driven by device counters (the
+execution ("step", "jump", "reveal", "final", and "slide" between two windows of a long rollout).  Every op of a kind is the same launch sequence driven by device counters (the
 timestep, the Philox stream id), so `issue_schedule` has each lane run a kind eagerly once, capture it into a hipGraph if it
 recurs, and replay it from then on; `DiffusionTransformer._sample_once` walks that schedule.
 """
@@ -20,11 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import GsddError
-
-
-def _is_int(v):
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+from ._lib import GsddError, _is_int
 
 
 @contextlib.contextmanager
@@ -567,6 +563,85 @@ class PurityPlan(collections.namedtuple("PurityPlan", "calls final rule weight")
         return ("reveal",) * len(self.calls) + (("final",) if self.final else ())
 
 
+def window_count(window_frames, n_frames, overlap):
+    """Validates the geometry of a sliding-window rollout and -> W, the number of windows: F = window_frames latent frames per window,
+    consecutive windows share k = overlap of them (stride s = F - k), n = n_frames long frames: W = 1 + ceil(max(n - F, 0) / s)."""
+    for name, v in (("window_frames", window_frames), ("n_frames", n_frames), ("overlap", overlap)):
+        if not _is_int(v):
+            raise GsddError(f"{name} must be an int, got {v!r}")
+    if window_frames < 2:
+        raise GsddError(f"window_frames = {window_frames}: a window needs at least 2 latent frames (one known, one to sample)")
+    if not 1 <= overlap <= window_frames - 1:
+        raise GsddError(f"overlap must lie in [1, {window_frames - 1}] (window_frames - 1: at least one frame is left to sample), got {overlap}")
+    if n_frames < window_frames:
+        raise GsddError(f"n_frames = {n_frames} is below window_frames = {window_frames}: a long clip holds at least one window")
+    s = window_frames - overlap
+    return 1 + (max(n_frames - window_frames, 0) + s - 1) // s
+
+
+class LongPlan(collections.namedtuple("LongPlan", "window_frames n_frames overlap window windows")):
+    """A sliding-window rollout (made by `long_plan`, which validates the geometry and counts the windows once): `windows` runs of the
+    plan `window` (a SamplePlan or a ResamplePlan from all-[MASK]) with a "slide"
+    between two of them.  Window w covers long frames [w s, w s + F), s = F - k; from window 1 on the first k frames are known -- the
+    last k of the window before.  Long frame f takes its tokens from the first window that sampled it (`owned`).  t0, dt, post_skip,
+    q_sample and jump read like the window plan's: every window is the same chain, so the lanes' step / jump graphs serve all of them."""
+    __slots__ = ()
+    q_sample = False
+
+    @property
+    def stride(self):
+        return self.window_frames - self.overlap
+
+    @property
+    def program(self):
+        return self.window.program + (("slide",) + self.window.program) * (self.windows - 1)
+
+    @property
+    def draws(self):
+        """The sum of the windows' draws: a slide spends no noise stream."""
+        return self.windows * self.window.draws
+
+    @property
+    def n_steps(self):
+        return self.windows * self.window.n_steps
+
+    t0 = property(lambda self: self.window.t0)
+    dt = property(lambda self: self.window.dt)
+    post_skip = property(lambda self: self.window.post_skip)
+    jump = property(lambda self: self.window.jump)
+
+    def owned(self, w):
+        """-> range of the long frames window w contributes: [0, F) for window 0, [w s + k, min(w s + F, n)) for w >= 1."""
+        if not 0 <= w < self.windows:
+            raise GsddError(f"window {w} of a rollout with {self.windows}")
+        lo = 0 if w == 0 else w * self.stride + self.overlap
+        return range(lo, min(w * self.stride + self.window_frames, self.n_frames))
+
+    def frame_map(self):
+        """-> [(window, frame within the window)] for every long frame."""
+        out = [None] * self.n_frames
+        for w in range(self.windows):
+            for f in self.owned(w):
+                out[f] = (w, f - w * self.stride)
+        return out
+
+
+def long_plan(window_frames, n_frames, overlap, window_plan):
+    """The rollout sample_long() runs, host-side and pure: `window_plan` is what sample() / sample_fast() would run for one window
+    (sample_plan(T), sample_plan(T, skip_step) or resample_plan(T, jump, times)).  A purity-prior plan is refused -- its reveal schedule
+    counts [MASK] positions, as check_known says -- and so is a partially noised start (filter_ratio > 0), which re-noises the known
+    frames."""
+    windows = window_count(window_frames, n_frames, overlap)
+    if isinstance(window_plan, PurityPlan):
+        raise GsddError("long_plan: no rollout for the purity prior (prior_rule 1 / 2): the overlap frames are known tokens and the "
+                        "purity prior's reveal schedule counts [MASK] positions")
+    if not isinstance(window_plan, (SamplePlan, ResamplePlan)):
+        raise GsddError(f"long_plan: window_plan must be a SamplePlan or a ResamplePlan, got {type(window_plan).__name__}")
+    if window_plan.q_sample:
+        raise GsddError("long_plan: filter_ratio > 0 (a partially noised start) is refused: a window samples from all-[MASK] only")
+    return LongPlan(int(window_frames), int(n_frames), int(overlap), window_plan, windows)
+
+
 def issue_schedule(program, lanes, graphed):
     """-> [(lane, kind, action)] in host issue order for a plan's `program` (its op kinds in order of execution), pure.  Op-major,
     lane-minor, so that the lanes' queues are fed alternately.  Not graphed: every op is "eager".  Graphed: a lane runs the first op
@@ -802,7 +877,7 @@ class _Lane:
     keywords, the graph of every op kind captured so far and what only some programs need: the jump's table and held positions, the
     reveal's plan arrays, counters and candidate buffers.  Built on `st`, after st waits for the caller's stream."""
 
-    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw, cond_len=None):
+    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw, cond_len=None, long_tok=None):
         dev, L, K, Bs, tr = dm.device, dm.shape, dm.num_classes - 1, sl.stop - sl.start, dm.transformer
         self.tr, self.plan, self.st, self.rep, self.guided, self.graphs = tr, plan, st, rep, dm._guided, {}
         self.trunc_kw = trunc_kw                    # a launch constant of both step kernels: a captured graph records it
@@ -824,7 +899,21 @@ class _Lane:
                               T=self.T, seed=self.seed, row0=self.row0, stream=st)
         # known positions (check_known): this lane's slices of mask and tokens, made once, here, outside graph capture -- they are
         # constants of the chain; nothing at all without a mask
-        self.known_kw = _known_kwargs(known, dev, sl)
+        if long_tok is None:
+            self.known_kw = _known_kwargs(known, dev, sl)
+        else:
+            # a rollout (LongPlan): every window runs the step with known positions on buffers of the lane's own, which the slide
+            # rewrites between two windows -- so the graphs of the first windows serve all later ones.  `known` is (mask or None,
+            # tokens or None, mode): window 0 carries the caller's mask, or none at all (all zero: the plain step, bit for bit)
+            mask, xk, mode = known
+            self.known_kw = {"known": torch.zeros((Bs, L), dtype=torch.uint8, device=dev),
+                             "x_known": torch.zeros((Bs, L), dtype=torch.int64, device=dev), "known_mode": mode}
+            if mask is not None:
+                self.known_kw["known"].copy_(mask[sl])
+                self.known_kw["x_known"].copy_(xk[sl])
+            self.long_rows = long_tok[sl]           # this lane's rows of the (B, n h w) long buffer
+            self.win_state = i64([0, 0])            # the finished window's index, the slide kernel's arrival counter
+            self.bad = torch.zeros((1,), dtype=torch.int32, device=dev)      # tokens outside [0, K) that a slide made known
         if "jump" in plan.program:              # the jump's table and, in hold mode, the positions it copies through
             self.jump_table = dm._jump_table(plan.jump, dev)
             self.jump_hold = self.known_kw["known"] if self.known_kw["known_mode"] == KNOWN_MODES["hold"] else None
@@ -868,7 +957,12 @@ class _Lane:
     def final(self):                            # the purity chain's ordinary reverse step at t = 0
         self.plain_step(0)
 
-    OPS = {"step": step, "jump": jump, "reveal": reveal, "final": final}
+    def slide(self, final=False):               # between two windows: frames out, the overlap in as known tokens, [MASK], t2 = t0
+        p, kw = self.plan, self.known_kw
+        ops.d3pm_window_slide(self.tok, self.long_rows, kw["x_known"], kw["known"], self.t2, self.win_state, self.bad,
+                              F=p.window_frames, k=p.overlap, n=p.n_frames, K=self.K, t0=p.t0, final=final, stream=self.st)
+
+    OPS = {"step": step, "jump": jump, "reveal": reveal, "final": final, "slide": slide}
 
     def issue(self, kind, action, trace=None):
         """One entry of `issue_schedule`; an eager op of a traced call appends the lane's tokens to `trace`."""
@@ -1121,6 +1215,78 @@ class DiffusionTransformer(nn.Module):
         return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
                                     use_graph=use_graph, trace=trace, truncation_rate=trunc, **known_kw, **kwargs)
 
+    @torch.no_grad()
+    def sample_long(self, condition_token, condition_mask, condition_embed, cf_condition_embed, *, latent_shape, n_frames, overlap,
+                    content_token=None, known_mask=None, known_mode="renoise", skip_step=None, resample_jump=None, resample_times=1,
+                    condition_len=None, cf_condition_len=None, use_graph=True, trace=None, filter_ratio=0, **kwargs):
+        """A clip of n_frames latent frames, longer than the model's window of F = latent_shape[0]: the sliding-window rollout of
+        `long_plan` as one program of the executor.  Window 0 is the call sample() -- or, with skip_step, sample_fast() -- would make
+        (content_token / known_mask apply to it alone: continuing a real clip); every later window keeps the last `overlap` frames
+        of the window before as known tokens (frame_mask(latent_shape, overlap), known_mode, the resampling jumps) and samples the
+        rest.  Between two windows one launch per lane (gsdd_d3pm_window_slide) moves the finished frames to the long buffer, makes
+        the overlap the next window's known tokens and resets tokens and timesteps, all on the lane's fixed buffers: no host round
+        trip, and the step / jump graphs captured in the first windows replay in every later one.  One condition per clip serves all
+        windows.  The tokens are those of the manual chain of those calls under the same set_noise, and noise_stream ends where the
+        chain leaves it.  A [MASK] in an overlap raises after the call (one read of device counters, with the range flags; after a
+        repeat on the bf16x3 kernel they are the repeat's counters).  On that error path alone the call differs from the chain: the
+        whole rollout has run and noise_stream has advanced by all its draws, where the chain's check_known would have stopped before
+        the next window.
+        n_frames == F is sample() / sample_fast() itself.  Not with prior_rule > 0, filter_ratio > 0, or skip_step together with
+        resampling jumps.  -> {"content_token": (B, n_frames h w) int64, "windows": W}"""
+        T, K = self.num_timesteps, self.num_classes - 1
+        shape = tuple(latent_shape)
+        if len(shape) != 3 or not all(_is_int(v) and v >= 1 for v in shape) or shape[0] * shape[1] * shape[2] != self.shape:
+            raise GsddError(f"latent_shape must be three positive ints (t, h, w) with t h w = content_seq_len = {self.shape}, got {latent_shape!r}")
+        if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
+            raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
+        if self.prior_rule != 0:
+            raise GsddError("sample_long cannot be combined with prior_rule > 0: the overlap frames are known tokens and the purity "
+                            "prior's reveal schedule counts [MASK] positions")
+        if int(T * filter_ratio) != 0:
+            raise GsddError(f"sample_long samples every window from all-[MASK]: int(num_timesteps * filter_ratio) = {int(T * filter_ratio)}, "
+                            "must be 0")
+        if skip_step is not None:
+            if not _is_int(skip_step) or skip_step < 0:
+                raise GsddError(f"skip_step must be None or a non-negative int, got {skip_step!r}")
+            if resample_jump is not None or resample_times != 1:
+                raise GsddError("skip_step cannot be combined with resample_jump / resample_times: the skip-step chain has no resampling jumps")
+        if not isinstance(known_mode, str) or known_mode not in KNOWN_MODES:
+            raise GsddError(f"known_mode must be one of {sorted(KNOWN_MODES)}, got {known_mode!r}")
+        resample = check_resample(resample_jump, resample_times, T, True)       # (every window from the second on has known frames)
+        window = sample_plan(T, skip_step=int(skip_step)) if skip_step is not None else (
+            sample_plan(T) if resample is None else resample_plan(T, *resample))
+        plan = long_plan(shape[0], n_frames, overlap, window)
+        B, L, hw = self._batch_of(condition_token, kwargs), self.shape, shape[1] * shape[2]
+        lens = _len_kwargs(condition_len, cf_condition_len)
+        if plan.windows == 1:                       # one window: the existing call, launch for launch
+            if resample is not None and known_mask is None:      # (window 0 of a resampled rollout: the jumps with nothing known)
+                content_token, known_mask = torch.zeros((B, L), dtype=torch.int64), torch.zeros((L,), dtype=torch.bool)
+            known_kw = {} if known_mask is None else {"known_mask": known_mask, "known_mode": known_mode}
+            if skip_step is not None:
+                out = self.sample_fast(condition_token, condition_mask, condition_embed, content_token=content_token, filter_ratio=0,
+                                       skip_step=int(skip_step), cf_condition_embed=cf_condition_embed, use_graph=use_graph, trace=trace,
+                                       **known_kw, **lens, **kwargs)
+            else:
+                if resample is not None:
+                    known_kw.update(resample_jump=resample_jump, resample_times=resample_times)
+                out = self.sample(condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=content_token,
+                                  filter_ratio=0, use_graph=use_graph, trace=trace, **known_kw, **lens, **kwargs)
+            return {"content_token": out["content_token"], "windows": 1}
+        trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)
+        known = (None, None, KNOWN_MODES[known_mode])
+        if known_mask is not None:
+            known = check_known(known_mask, content_token, known_mode, B=B, L=L, K=K)
+        # the long buffer: made once, on the caller's stream, before the lanes fork; every lane writes its own rows
+        long_tok = torch.full((B, plan.n_frames * hw), K, dtype=torch.int64, device=self.device)
+        out = self._sample_checked(plan, condition_token, condition_embed, cf_condition_embed, use_graph=use_graph, trace=trace,
+                                   truncation_rate=trunc, known=known, long_tok=long_tok, **lens, **kwargs)
+        bad = sum(int(c.item()) for c in self._bad_counters)      # (the lanes of the run that counted: _sample_checked's last)
+        if bad:
+            raise GsddError(f"sample_long: {bad} token(s) outside [0, {K}) in the overlap frames of a finished window ([MASK] = {K} is "
+                            "no clean token: the window's chain did not resolve every position)")
+        return {"content_token": out["content_token"], "windows": plan.windows}
+
     def _sample_checked(self, plan, *args, trace=None, **kw):
         """`_sample_once`, then one read of the layer kernel's range flags after the loop (outside graph capture): if an activation left
         the f16 operand range the call is repeated on the bf16x3 layer kernel (Text2ImageTransformer.demote_to_x3p) -- same noise
@@ -1138,7 +1304,7 @@ class DiffusionTransformer(nn.Module):
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
                      use_graph=True, trace=None, truncation_rate=None, known=None, condition_len=None, cf_condition_len=None,
-                     **kwargs):
+                     long_tok=None, **kwargs):
         """Runs plan.program once: resolves the guidance copies and the lane count, builds the lanes, issues `issue_schedule`'s
         entries and joins the lanes' streams."""
         dev = self.device
@@ -1190,16 +1356,20 @@ class DiffusionTransformer(nn.Module):
                     sl = slice(len(lane_list) * (B // lanes), (len(lane_list) + 1) * (B // lanes))
                     conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
                     lane_len = None if lens is None else (torch.cat([lens[0][sl], lens[1][sl]]) if rep == 2 else lens[0][sl])
-                    lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate), lane_len))
+                    lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate), lane_len, long_tok))
             return lane_list[ln]
         for ln, kind, action in issue_schedule(plan.program, lanes, graphed):
             lane(ln).issue(kind, action, trace)
         lane(lanes - 1)                             # (an empty program: the all-[MASK] start is the result)
+        if long_tok is not None:                    # a rollout: the last window's frames join the long buffer (no slide follows it)
+            for lane in lane_list:
+                lane.slide(final=True)
         for lane in lane_list:
             cur.wait_stream(lane.st)
             lane.tok.record_stream(cur)
         self._redo_counters = [lane.ws["redo"] for lane in lane_list]      # attention chunk-redo events of this call, per lane
         self._range_flags = [lane.ws["range"] for lane in lane_list]
+        self._bad_counters = [lane.bad for lane in lane_list] if long_tok is not None else []
         # the graphs live until the next call: their replays may still be in flight when this one returns
         self._last_graphs = [lane.graphs for lane in lane_list]
         self._last_jump_graphs = [lane.graphs.get("jump") for lane in lane_list] if graphed and "jump" in plan.program else []
@@ -1207,6 +1377,8 @@ class DiffusionTransformer(nn.Module):
         self.noise_stream += plan.draws
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
+        if long_tok is not None:
+            return {"content_token": long_tok}
         return {"content_token": lane_list[0].tok if lanes == 1 else torch.cat([lane.tok for lane in lane_list], 0)}
 
     def attention_redo_events(self):
@@ -1406,13 +1578,29 @@ class DiscreteDiffusion(nn.Module):
     mask_text_padding: true asks a per-token provider for each caption's length (end-of-text position + 1) and hands it to the training
     objective and the sampler as condition lengths: the cross-attention then runs over a caption's own tokens and never reads the
     padding behind them, so a sample does not depend on how wide the batch was padded.  The unconditional copy and a dropped training
-    sample stay full length.  Dropped with zero_text_emb (condition and null condition are the same zeros there)."""
+    sample stay full length.  Dropped with zero_text_emb (condition and null condition are the same zeros there).
+    sample_long_frames: null, or the number of latent frames of a long clip (at least the model's window): the render path
+    (src/models/base.py) and sample_videos(long_frames=) then sample it with DiffusionTransformer.sample_long -- windows that share
+    sample_long_overlap latent frames -- and decode it with VQVAE.decode_long, sample_long_blend "linear" / "keep" / "replace" across
+    the overlaps.  forward(do_inference=True) keeps sampling one window.  Not with sample_prior_rule > 0."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
                  sample_condition_frames=None, sample_known_mode="renoise", sample_resample_jump=None, sample_resample_times=None,
+                 sample_long_frames=None, sample_long_overlap=4, sample_long_blend="linear",
                  train_cond_drop_prob=None, mask_text_padding=False, **kwargs):
         super().__init__()
+        if sample_long_frames is not None and not (_is_int(sample_long_frames) and sample_long_frames >= 2):
+            raise GsddError(f"sample_long_frames must be null or an int >= 2 (latent frames of the long clip), got {sample_long_frames!r}")
+        if not (_is_int(sample_long_overlap) and sample_long_overlap >= 1):
+            raise GsddError(f"sample_long_overlap must be an int >= 1 (latent frames two windows share), got {sample_long_overlap!r}")
+        if not isinstance(sample_long_blend, str) or sample_long_blend not in ops.BLEND_MODES:
+            raise GsddError(f"sample_long_blend must be one of {sorted(ops.BLEND_MODES)}, got {sample_long_blend!r}")
+        if sample_long_frames is not None and sample_prior_rule:
+            raise GsddError("sample_long_frames and sample_prior_rule > 0 cannot be combined: the overlap frames are known tokens and the "
+                            "purity prior's reveal schedule counts [MASK] positions")
+        self.sample_long_frames = None if sample_long_frames is None else int(sample_long_frames)
+        self.sample_long_overlap, self.sample_long_blend = int(sample_long_overlap), sample_long_blend
         if not isinstance(mask_text_padding, bool):
             raise GsddError(f"mask_text_padding must be true or false, got {mask_text_padding!r}")
         self.mask_text_padding = mask_text_padding
@@ -1569,12 +1757,15 @@ class DiscreteDiffusion(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None, text_len=None):
+    def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None, text_len=None,
+                      long_frames=None):
         """The inference branch of forward (discrete_diffusion.py:44-62): text -> tokens -> decoded clips.
         known_tokens (B, L) / known_mask ((B, L) or (L,) bool): clean tokens to keep at the mask's positions (the sampler's
         content_token / known_mask, with sample_known_mode); without a mask the call is the plain one.
         text_len goes with text_emb: the captions' (B,) condition lengths (the sampler's condition_len), None for none; without
-        text_emb both come from the provider."""
+        text_emb both come from the provider.
+        long_frames: None, or the latent frames n of a long clip: sample_long with sample_long_overlap (the mask, if any, applies to
+        its first window), then decode_long with sample_long_blend -> (B, 3, n d_t, H, W); last_content_token is the long grid."""
         dev = autoencoder.device
         B = len(texts)
         if text_emb is None:
@@ -1609,13 +1800,23 @@ class DiscreteDiffusion(nn.Module):
                                 resample_times=1 if self.sample_resample_times is None else self.sample_resample_times)
         if text_len is not None:
             known_kw = dict(known_kw, condition_len=text_len)          # (the unconditional copy stays full length)
+        shape = tuple(latent_shape if latent_shape is not None else autoencoder.latent_shape)
+        if long_frames is not None:
+            long_kw = dict({"known_mode": self.sample_known_mode}, **known_kw)
+            if self.sample_resample_jump is not None:          # (every window from the second on has known frames to harmonise with)
+                long_kw.update(resample_jump=self.sample_resample_jump,
+                               resample_times=1 if self.sample_resample_times is None else self.sample_resample_times)
+            out = dm.sample_long(texts, None, text_emb, cf_emb, latent_shape=shape, n_frames=long_frames, overlap=self.sample_long_overlap,
+                                 content_token=content, skip_step=self.sample_skip_step, **long_kw)
+            self.last_content_token = out["content_token"]
+            return autoencoder.decode_long(out["content_token"].view(B, long_frames, *shape[1:]), self.sample_long_overlap,
+                                           blend=self.sample_long_blend)
         if self.sample_skip_step is None:
             out = self.diffusion_model.sample(texts, None, text_emb, cf_emb, content_token=content, filter_ratio=0, **known_kw)
         else:
             out = self.diffusion_model.sample_fast(texts, None, text_emb, content_token=content, filter_ratio=0,
                                                    skip_step=self.sample_skip_step, cf_condition_embed=cf_emb, **known_kw)
         self.last_content_token = out["content_token"]
-        shape = latent_shape if latent_shape is not None else autoencoder.latent_shape
         return autoencoder.decode(out["content_token"].view(B, *shape))
 
     def get_text_embeddings(self, features):                                           # discrete_diffusion.py:91-94

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib as abi
-from ._lib import GemmDesc, GsddError, JumpDesc, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, check, lib, ptr, stream_ptr
+from ._lib import GemmDesc, GsddError, JumpDesc, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, _is_int, check, lib, ptr, stream_ptr
 
 ACT_NONE, ACT_RELU, ACT_GELU2 = 0, 1, 2
 
@@ -557,6 +557,58 @@ def advance_plan(step_dev, plan_t, plan_n, t_dev, n_dev, stream_dev, ds, stream=
     """step += 1; t[:] = plan_t[min(step, len - 1)], n = plan_n[...]; stream += ds -- on the device (the purity chain's counter)."""
     check(lib().gsdd_advance_plan(ptr(step_dev), ptr(plan_t), ptr(plan_n), plan_t.numel(), ptr(t_dev), t_dev.numel(), ptr(n_dev),
                                   ptr(stream_dev), ds, stream_ptr(stream)))
+
+
+# ----------------------------------------------------------------------------- long clips (d3pm.long_plan, VQVAE.decode_long)
+def d3pm_window_slide(tok, long_tok, x_known, known, t2, state, bad, *, F, k, n, K, t0, final=False, stream=None):
+    """The op between two windows of a sliding-window rollout (gsdd_d3pm_window_slide): the finished window tok (Bs, F hw) int64,
+    whose index is state[0], contributes its frames to long_tok (Bs, n hw) -- the lane's rows of the long buffer --, its last k
+    frames become x_known[:, :k hw] (a token outside [0, K) there adds one to bad, int32 (1,)), known (Bs, F hw) uint8 becomes 1 on
+    the first k hw positions and 0 elsewhere, tok all [MASK] = K, t2 (int64, its rows) t0 and state (int64 (2,)) moves to the next
+    window.  final: only the copy to long_tok (the launch behind the last window); x_known, known, t2 and bad may be None."""
+    if tok.dim() != 2 or tok.dtype != torch.int64 or not all(_is_int(v) for v in (F, k, n, K, t0)) or F < 1 or tok.shape[1] % F:
+        raise GsddError(f"d3pm_window_slide: tok must be int64 (Bs, F hw) and F, k, n, K, t0 ints, got {tuple(tok.shape)} {tok.dtype}, F = {F!r}")
+    Bs, Lw = tok.shape
+    hw = Lw // F
+    if long_tok.dtype != torch.int64 or tuple(long_tok.shape) != (Bs, n * hw):
+        raise GsddError(f"d3pm_window_slide: long_tok must be int64 {(Bs, n * hw)}, got {tuple(long_tok.shape)} {long_tok.dtype}")
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise GsddError("d3pm_window_slide: state must hold two int64 words (the finished window's index, 0)")
+    n_t2 = 0
+    if not final:
+        if x_known is None or known is None or t2 is None or bad is None:
+            raise GsddError("d3pm_window_slide: x_known, known, t2 and bad are needed unless final")
+        if x_known.dtype != torch.int64 or tuple(x_known.shape) != (Bs, Lw) or known.dtype != torch.uint8 or tuple(known.shape) != (Bs, Lw):
+            raise GsddError(f"d3pm_window_slide: x_known must be int64 and known uint8, both {(Bs, Lw)}, got {tuple(x_known.shape)} "
+                            f"{x_known.dtype} / {tuple(known.shape)} {known.dtype}")
+        if t2.dtype != torch.int64 or bad.dtype != torch.int32 or bad.numel() != 1:
+            raise GsddError("d3pm_window_slide: t2 must be int64 and bad one int32 word")
+        n_t2 = t2.numel()
+    check(lib().gsdd_d3pm_window_slide(ptr(tok), ptr(long_tok), ptr(x_known), ptr(known), ptr(t2), ptr(state), ptr(bad), Bs, F, hw, k, n,
+                                       K, t0, n_t2, 1 if final else 0, stream_ptr(stream)))
+
+
+BLEND_MODES = {"linear": abi.BLEND_LINEAR, "keep": abi.BLEND_KEEP, "replace": abi.BLEND_REPLACE}
+
+
+def clip_window_blend(win, out, f0, n_ov, blend="linear", stream=None):
+    """One decoded window win (B, C, Fw, H, W) float32 merged into the long clip out (B, C, Fo, H, W) at output frame f0
+    (gsdd_clip_window_blend): its first n_ov frames overlap frames already in `out` -- crossfaded ("linear", weight (j + 1) /
+    (n_ov + 1) for the window), left alone ("keep") or overwritten ("replace") --, the others are copied; frames behind Fo are
+    dropped."""
+    if not isinstance(blend, str) or blend not in BLEND_MODES:
+        raise GsddError(f"clip_window_blend: blend must be one of {sorted(BLEND_MODES)}, got {blend!r}")
+    if win.dim() != 5 or out.dim() != 5 or win.dtype != torch.float32 or out.dtype != torch.float32:
+        raise GsddError(f"clip_window_blend: win and out must be float32 (B, C, frames, H, W), got {tuple(win.shape)} {win.dtype} / "
+                        f"{tuple(out.shape)} {out.dtype}")
+    B, C_, Fw, H, W = win.shape
+    if tuple(out.shape[:2]) != (B, C_) or tuple(out.shape[3:]) != (H, W):
+        raise GsddError(f"clip_window_blend: out {tuple(out.shape)} does not match win {tuple(win.shape)} outside the frame axis")
+    if not _is_int(f0) or not _is_int(n_ov):
+        raise GsddError(f"clip_window_blend: f0 and n_ov must be ints, got {f0!r}, {n_ov!r}")
+    check(lib().gsdd_clip_window_blend(ptr(win), ptr(out), B * C_, Fw, H * W, out.shape[2], f0, n_ov, BLEND_MODES[blend],
+                                       stream_ptr(stream)))
+    return out
 
 
 # ----------------------------------------------------------------------------- CLIP text tower (text.py)

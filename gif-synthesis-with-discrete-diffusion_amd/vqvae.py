@@ -397,6 +397,37 @@ class VQVAE(nn.Module):
             self._packed = None                                     # BN running stats changed in place
         return out
 
+    @torch.no_grad()
+    def decode_long(self, tokens, overlap, blend="linear"):
+        """A long token grid (B, n, h, w), n >= F = latent_shape[0], through the F-frame decoder -> (B, 3, n d_t, H, W), d_t =
+        downsample[0].  The grid is decoded window by window with `decode`, at the windows of d3pm.long_plan (window w: latent frames
+        [w s, w s + F), s = F - overlap), and every decoded window is merged into the output by one launch (gsdd_clip_window_blend):
+        the frames a window contributes are copied; the overlap d_t frames it shares with the window before are crossfaded
+        ("linear": out + a_j (win - out), a_j = (j + 1) / (overlap d_t + 1)), kept from the earlier window ("keep") or taken from
+        the later one ("replace").  A last window that reaches past frame n is filled up with copies of the grid's last frame; what it
+        decodes behind n d_t is dropped.  n == F is decode(tokens), bit for bit.  Eval mode only: a train-mode decode would update the
+        BatchNorm statistics once per window."""
+        from .d3pm import window_count
+        if blend not in ops.BLEND_MODES:
+            raise GsddError(f"decode_long: blend must be one of {sorted(ops.BLEND_MODES)}, got {blend!r}")
+        if tokens.dim() != 4:
+            raise GsddError(f"decode_long: tokens must be (B, n, h, w), got {tuple(tokens.shape)}")
+        if self.training:
+            raise GsddError("decode_long needs the VQ-VAE in eval mode: a train-mode decode updates BatchNorm statistics, once per window")
+        B, n, h, w = tokens.shape
+        F, dt = self.latent_shape[0], self.downsample[0]
+        W = window_count(F, n, overlap)
+        if W == 1:
+            return self.decode(tokens)
+        s, out = F - overlap, None
+        for wi in range(W):
+            idx = torch.arange(wi * s, wi * s + F, device=tokens.device).clamp_(max=n - 1)
+            win = self.decode(tokens.index_select(1, idx))
+            if out is None:
+                out = torch.zeros((B, win.shape[1], n * dt) + tuple(win.shape[3:]), dtype=torch.float32, device=win.device)
+            ops.clip_window_blend(win, out, wi * s * dt, overlap * dt if wi else 0, blend)
+        return out
+
     def _tile(self, x):
         """Codebook._tile (videogpt_vq_vae.py:151-158): repeat + jitter when there are fewer latents than codes."""
         d, ew = x.shape

@@ -653,6 +653,39 @@ int gsdd_advance_floor(int64_t* t_dev, int B, int64_t dt, int64_t t_min, int64_t
 int gsdd_advance_plan(int64_t* step_dev, const int64_t* plan_t, const int64_t* plan_n, int64_t n_calls, int64_t* t_dev, int B,
                       int64_t* n_dev, int64_t* stream_dev, int64_t ds, void* stream);
 
+/* ------------------------------------------------------------------ long clips: sliding-window rollout and stitched decode
+ * A long grid of n latent frames is sampled as windows of F frames that overlap by k (stride s = F - k): window w covers long frames
+ * [w s, w s + F) and is conditioned on the last k frames of window w - 1; long frame f takes its tokens from the first window that
+ * sampled it (window 0: f < F; window w >= 1: f in [w s + k, w s + F)); frames >= n are dropped.
+ *
+ * gsdd_d3pm_window_slide: the op between two windows, one launch, on the caller's fixed buffers (safe to capture: every fill is a
+ * store of the kernel).  tok[Bs][F hw] holds finished window w = state[0]:
+ *   long_tok[b][(w s + f) hw + q] = tok[b][f hw + q] for the frames f the window contributes whose long frame is < n (long_tok: the
+ *       caller's first row of the (B, n hw) long buffer, row pitch n hw; nothing is written behind a row's end);
+ *   x_known[b][: k hw] = tok[b][s hw :]; bad[0] += the number of those tokens outside [0, K) ([MASK] = K is no clean token);
+ *   known[b][p] = p < k hw; tok[b][p] = K; t2[i] = t0 for i < n_t2; state[0] = w + 1.
+ * state: device int64[2], {the finished window's index, 0}; the second word is the kernel's own arrival counter and is 0 again when
+ * the launch has finished.  The entry point is not idempotent: every launch moves state[0] on, so the caller zeroes the state at the
+ * start of every rollout and does not reuse it after a failed launch.  A state[0] outside [0, n] writes nothing to long_tok (x_known,
+ * known, tok and t2 are rewritten all the same).  final_copy = 1 (behind the last window): only the
+ * copy to long_tok; x_known, known, t2 and bad may be null and the state does not move.
+ * GSDD_E_ARG before the launch for a null pointer, sizes below 1, k outside [1, F - 1], n < F, K < 1, t0 < 0, n_t2 outside
+ * [0, Bs F hw], Bs F hw of 2^31 or more.
+ *
+ * gsdd_clip_window_blend: one decoded window win[BC][Fw][HW] (BC = batch x channels planes) merged into the long clip
+ * out[BC][Fo][HW] at output frame f0.  Frames f0 + j >= Fo are not written.  The first n_ov frames of the window overlap frames
+ * the window before has written: GSDD_BLEND_LINEAR crossfades them in fp32, out <- out + a_j (win - out) with
+ * a_j = (j + 1) / (n_ov + 1); GSDD_BLEND_KEEP leaves them as they are (no write); GSDD_BLEND_REPLACE overwrites them.  The frames
+ * behind the overlap are copied bit for bit.
+ * GSDD_E_ARG before the launch for a null pointer, sizes below 1, BC above 65535, Fo < Fw, n_ov outside [0, Fw - 1], f0 outside
+ * [0, Fo - 1], n_ov > 0 with f0 = 0, an unknown mode, a pointer off 4-byte alignment. */
+#define GSDD_BLEND_LINEAR 0
+#define GSDD_BLEND_KEEP 1
+#define GSDD_BLEND_REPLACE 2
+int gsdd_d3pm_window_slide(int64_t* tok, int64_t* long_tok, int64_t* x_known, uint8_t* known, int64_t* t2, int64_t* state, int* bad,
+                           int Bs, int F, int hw, int k, int n, int K, int64_t t0, int n_t2, int final_copy, void* stream);
+int gsdd_clip_window_blend(const float* win, float* out, int BC, int Fw, int HW, int Fo, int f0, int n_ov, int mode, void* stream);
+
 /* uniform Philox floats, layout of oracle/philox.py uniform_rows (test hook) */
 int gsdd_philox_uniform(uint64_t seed, int64_t stream_id, int64_t row0, int64_t n_rows, int n_cols,
                         float* out, void* stream);

@@ -107,14 +107,44 @@ class BaseModel(_Base):
             for n, c in zip(names, captions):
                 f.write(f"{n}\t{' '.join(str(c).split())}\n")
 
+    def _long_frames(self):
+        """The generator's sample_long_frames when it renders long clips (a DiscreteDiffusion over an autoencoder), else None."""
+        n = getattr(getattr(self, "generator", None), "sample_long_frames", None)
+        return n if isinstance(n, int) and getattr(self, "autoencoder", None) is not None else None
+
+    def _sample_long_clips(self, batch, limit):
+        """The first `limit` items of `batch` as long clips (B, 3, n d_t, H, W): sampled here with the generator's sliding-window
+        rollout and decoded with the stitched decode -- the evaluation's one-window sample is neither reused nor touched.  With
+        sample_condition_frames the rollout's first window keeps those latent frames of the item's own clip."""
+        import contextlib
+        gen, auto, n = self.generator, self.autoencoder, self._long_frames()
+        texts = list(batch["text"])[:limit]
+        was_training = gen.training
+        gen.eval()
+        try:
+            with torch.no_grad(), (self.ema_scope() if hasattr(self, "ema_scope") else contextlib.nullcontext()):
+                known_kw = {}
+                if gen.sample_condition_frames is not None:
+                    quant = auto.encode(batch["video"][:limit].to(auto.device))
+                    known_kw = {"known_tokens": quant.view(quant.shape[0], -1),
+                                "known_mask": gen.condition_frame_mask(tuple(quant.shape[1:])), "latent_shape": tuple(quant.shape[1:])}
+                return gen.sample_videos(texts, auto, long_frames=n, **known_kw)
+        finally:
+            gen.train(was_training)
+
     def render_test_batch(self, batch, batch_idx, sampled=None):
         """Test split with `render_dir` set: the batch's sampled clips as <render_dir>/test/<batch_idx>_<i>.gif, at most `render_max`
         in all (`render_dir` alone switches this on: the shipped configs keep `render_animations`, the validation item's switch,
-        off).  `sampled`: what do_evaluation has already sampled for this batch (reused); None = the sample is made here."""
+        off).  `sampled`: what do_evaluation has already sampled for this batch (reused); None = the sample is made here.
+        With the generator's sample_long_frames set the clips written are long ones, sampled here (`_sample_long_clips`): `sampled` is
+        not used, and the extra rollout draws from the sampler's noise stream, so the evaluation samples of LATER batches start at
+        another stream offset than in a run without sample_long_frames -- metrics of two such runs are not sample for sample the same."""
         if not self.render_dir or self._rendered >= self.render_max:
             return
         import os
-        if sampled is None:
+        if self._long_frames() is not None:
+            sampled = {"pred_data": self._sample_long_clips(batch, self.render_max - self._rendered)}
+        elif sampled is None:
             was_training = self.generator.training
             self.generator.eval()
             with torch.no_grad():
@@ -145,7 +175,7 @@ class BaseModel(_Base):
         self.generator.train(was_training)
         if self.render_dir:
             import os
-            pred = self.last_sample["pred_data"]
+            pred = self.last_sample["pred_data"] if self._long_frames() is None else self._sample_long_clips(one, 1)      # (pred.gif long)
             caption = one["text"][0] if isinstance(one.get("text"), (list, tuple)) and one["text"] else ""
             directory = os.path.join(self.render_dir, f"epoch_{self.current_epoch}")
             self._write_gifs(pred[:1], directory, ["pred.gif"], [caption])

@@ -864,6 +864,58 @@ int main() {
             EXPECT(gsdd_lpips_layer_distance(feat, w + 2, frames, 961, 64, parts, st), GSDD_E_ARG, false);
             EXPECT(gsdd_lpips_layer_distance(feat, w, frames, 961, 64, (double*)(rows + 1), st), GSDD_E_ARG, false);
         }
+        // long clips: the slide between two windows and the window blend -- the accepted forms launch, every refusal returns before one
+        {
+            alignas(16) static unsigned char raw[64];
+            int64_t* i64p = (int64_t*)raw;
+            uint8_t* u8p = raw;
+            int* i32p = (int*)raw;
+            float* f32p = (float*)raw;
+            const int Bs = 8, F = 16, hw = 256, k = 4, n = 40, Kc = 4096;
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, nullptr, nullptr, nullptr, i64p, nullptr, Bs, F, hw, k, n, Kc, 99, 0, 1, st), GSDD_OK, true);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, 1, 2, 1, 1, 2, 1, 0, 0, 0, st), GSDD_OK, true);     // the smallest
+            EXPECT(gsdd_d3pm_window_slide(nullptr, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, nullptr, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, nullptr, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, nullptr, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, nullptr, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, nullptr, i32p, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, nullptr, Bs, F, hw, k, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, nullptr, nullptr, nullptr, nullptr, i64p, nullptr, Bs, F, hw, k, n, Kc, 99, 0, 1, st), GSDD_E_ARG, false);
+            for (int bad : {0, -1, F, F + 1}) EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, bad, n, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);      // k >= F
+            for (int bad : {F - 1, 0, -40}) EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, bad, Kc, 99, 2 * Bs, 0, st), GSDD_E_ARG, false);       // n < F
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, 0, F, hw, k, n, Kc, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, -Bs, F, hw, k, n, Kc, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, -F, hw, k, n, Kc, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, 0, k, n, Kc, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, -hw, k, n, Kc, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, 0, 99, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, -1, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, -1, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, Bs * F * hw + 1, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, Bs, F, hw, k, n, Kc, 99, 0, 2, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_window_slide(i64p, i64p, i64p, u8p, i64p, i64p, i32p, 1 << 15, 1 << 8, 1 << 8, k, 1 << 9, Kc, 99, 0, 0, st), GSDD_E_ARG, false);   // 2^31 tokens
+            const int BC = 48, Fw = 16, HW = 128 * 128, Fo = 40;
+            for (int mode : {GSDD_BLEND_LINEAR, GSDD_BLEND_KEEP, GSDD_BLEND_REPLACE}) {
+                EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, 12, 4, mode, st), GSDD_OK, true);
+                EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, 0, 0, mode, st), GSDD_OK, true);
+                EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, 35, Fo, 36, 4, mode, st), GSDD_OK, mode != GSDD_BLEND_KEEP);     // only the overlap fits: keep writes nothing
+            }
+            EXPECT(gsdd_clip_window_blend(nullptr, f32p, BC, Fw, HW, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_clip_window_blend(f32p, nullptr, BC, Fw, HW, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+            for (int bad : {Fw, Fw + 1, -1}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, 12, bad, 0, st), GSDD_E_ARG, false);     // k >= F
+            for (int bad : {Fw - 1, 0, -Fo}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, bad, 0, 0, 0, st), GSDD_E_ARG, false);       // n < F
+            for (int bad : {0, -3, 65536}) EXPECT(gsdd_clip_window_blend(f32p, f32p, bad, Fw, HW, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+            for (int bad : {0, -16}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, bad, HW, Fo, 12, 0, 0, st), GSDD_E_ARG, false);
+            for (int bad : {0, -35}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, bad, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+            for (int bad : {-1, Fo, Fo + 7}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, bad, 0, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, 0, 4, 0, st), GSDD_E_ARG, false);                    // an overlapped first window
+            for (int bad : {-1, 3}) EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, Fw, HW, Fo, 12, 4, bad, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_clip_window_blend(f32p, f32p, BC, 1 << 12, 1 << 19, 1 << 12, 0, 0, 0, st), GSDD_E_ARG, false);      // 2^31 floats in a window
+            EXPECT(gsdd_clip_window_blend((const float*)(raw + 2), f32p, BC, Fw, HW, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_clip_window_blend(f32p, (float*)(raw + 1), BC, Fw, HW, Fo, 12, 4, 0, st), GSDD_E_ARG, false);
+        }
         // ... and its encoder, which RUNS here: two frames of 7 x 5 in a buffer of exactly T H W bytes (a row read past a rectangle or past
         // the last frame is a report), frame 1 with the empty marker and then with a one-pixel rectangle in the last corner
         {

@@ -22,9 +22,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "-Wno-unused-function"]
 # the sampler's per-block kernels: attention (+ its K / V pre-split), the fused layer (+ logits); the purity-prior step's kernels; the
 # reverse step (and the training objective's kernels that share its file); the forward jump of RePaint's resampling; the training
-# step's cross-attention over several condition tokens; its condition dropout and null-embedding gradient; its optimiser stage
+# step's cross-attention over several condition tokens; its condition dropout and null-embedding gradient; its optimiser stage; the
+# slide between two windows of a long rollout and the stitched decode's window blend
 SOURCES = ["d3pm_attention.hip", "d3pm_layer.hip", "d3pm_purity.hip", "d3pm_step.hip", "d3pm_jump.hip", "d3pm_cross.hip", "d3pm_cond.hip",
-           "optim.hip"]
+           "optim.hip", "d3pm_window.hip"]
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
           "Occupancy [waves/SIMD]": "occupancy_waves_per_simd", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "static_lds_bytes"}
 
