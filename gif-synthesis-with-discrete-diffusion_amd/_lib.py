@@ -34,6 +34,7 @@ EXPORTS = [
     "gsdd_paired_metrics", "gsdd_paired_metrics_tiles",
     "gsdd_lpips_stem_rows", "gsdd_lpips_distance_slots", "gsdd_lpips_layer_distance",
     "gsdd_d3pm_window_slide", "gsdd_clip_window_blend",
+    "gsdd_d3pm_compose",
 ]
 
 _p = C.c_void_p
@@ -88,6 +89,13 @@ class JumpDesc(C.Structure):
         ("tok_in", _p), ("tok_out", _p), ("B", _i), ("L", _i), ("K", _i), ("T", _i), ("table", _p), ("jump", _i),
         ("t_dev", _p), ("hold", _p), ("seed", C.c_uint64), ("stream_dev", _p), ("row0", _i64),
     ]
+
+
+class ComposeDesc(C.Structure):
+    _fields_ = [("logits", _p), ("n_cond", _i), ("B", _i), ("L", _i), ("K", _i), ("weights", _p), ("out", _p)]
+
+
+COMPOSE_MAX_COND = 4       # GSDD_COMPOSE_MAX_COND
 
 
 class TrainDesc(C.Structure):
@@ -150,7 +158,7 @@ def lib():
         for which, name, cls in ((0, "gsdd_gemm_desc", GemmDesc), (1, "gsdd_layer_desc", LayerDesc), (2, "gsdd_step_desc", StepDesc),
                                  (3, "gsdd_train_desc", TrainDesc), (4, "gsdd_purity_desc", PurityDesc),
                                  (5, "gsdd_purity_select_desc", PuritySelectDesc), (7, "gsdd_jump_desc", JumpDesc),
-                                 (8, "gsdd_optim_state", OptimState)):      # (6 is not assigned)
+                                 (8, "gsdd_optim_state", OptimState), (10, "gsdd_compose_desc", ComposeDesc)):      # (6 and 9 are not assigned)
             if L.gsdd_abi_sizeof(which) != C.sizeof(cls):
                 raise GsddError(f"{LIB_PATH} was built from another revision of include/gsdd.h: sizeof({name}) is {L.gsdd_abi_sizeof(which)} "
                                 f"there and {C.sizeof(cls)} in this binding -- rebuild it with ./build.sh")
@@ -229,6 +237,7 @@ def lib():
         L.gsdd_d3pm_purity_step.argtypes = [C.POINTER(PurityDesc), _p]
         L.gsdd_d3pm_purity_select.argtypes = [C.POINTER(PuritySelectDesc), _p]
         L.gsdd_d3pm_forward_jump.argtypes = [C.POINTER(JumpDesc), _p]
+        L.gsdd_d3pm_compose.argtypes = [C.POINTER(ComposeDesc), _p]
         L.gsdd_advance_plan.argtypes = [_p, _p, _p, _i64, _p, _i, _p, _p, _i64, _p]
         L.gsdd_text_embed.argtypes = [_p, _p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]
         L.gsdd_text_attention.argtypes = [_p, _i, _i, _i, _i, C.c_float, _p, _p]

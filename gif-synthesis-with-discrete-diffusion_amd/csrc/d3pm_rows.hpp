@@ -77,6 +77,7 @@ __device__ __forceinline__ StepSched load_sched(const float* const* s, int64_t t
 struct SchedPtrs { const float* p[8]; };
 
 // log_softmax over the wave's row (fp64 sum/log), clamp to [-70,0]   (predict_start, :231-236)
+// (d3pm_compose.hip's two-pass J = 32 path restates the two halves as row_lse / lsm_clamp, operation for operation: a change here goes there too)
 template <int J>
 __device__ __forceinline__ void log_softmax_clamp(float (&x)[J][4]) {
     float mx = -INFINITY;

@@ -11,7 +11,7 @@ int deterministic() { return g_deterministic.load(std::memory_order_relaxed); }
 using namespace gsdd;
 
 extern "C" const char* gsdd_last_error(void) { return g_err.c_str(); }
-extern "C" int gsdd_version(void) { return 117; }
+extern "C" int gsdd_version(void) { return 118; }
 extern "C" int gsdd_set_deterministic(int on) { return g_deterministic.exchange(on != 0 ? 1 : 0); }
 extern "C" int64_t gsdd_abi_sizeof(int which) {
     switch (which) {
@@ -23,6 +23,7 @@ extern "C" int64_t gsdd_abi_sizeof(int which) {
         case 5: return (int64_t)sizeof(gsdd_purity_select_desc);
         case 7: return (int64_t)sizeof(gsdd_jump_desc);          // (6 stays unassigned: -1)
         case 8: return (int64_t)sizeof(gsdd_optim_state);
+        case 10: return (int64_t)sizeof(gsdd_compose_desc);      // (9 stays unassigned as well)
         default: return -1;
     }
 }

@@ -12,6 +12,7 @@ import collections
 import collections.abc
 import contextlib
 import ctypes
+import math
 import numbers
 import os
 
@@ -855,6 +856,77 @@ def _len_kwargs(condition_len, cf_condition_len):
     return {"condition_len": condition_len, "cf_condition_len": cf_condition_len}
 
 
+COMPOSE_MAX_COND = ops.abi.COMPOSE_MAX_COND     # conditions of a composed call, the call's own condition_embed included
+
+Compose = collections.namedtuple("Compose", "embeds weights lens")
+Compose.__doc__ = """A composed call's extra conditions (`check_compose`): embeds, the 1 ... 3 tensors shaped like condition_embed;
+weights, f32 CPU (B, N) over all N = 1 + len(embeds) conditions, the call's own first; lens, None or one (B,) int32 CPU length vector
+per extra condition."""
+
+
+def check_compose(compose_embeds, compose_weights, compose_lens, condition_embed, B):
+    """Validates sample()'s compose_embeds / compose_weights / compose_lens.  -> None (the plain call) or a `Compose`.
+    The step of a composed call reads e = x_u + sum_i w_i (x_i - x_u) over the N conditions (gsdd_d3pm_compose, include/gsdd.h):
+    the weights are the scales and guidance_scale plays no part."""
+    if compose_embeds is None:
+        if compose_weights is not None or compose_lens is not None:
+            raise GsddError("compose_weights / compose_lens need compose_embeds (the extra conditions they belong to)")
+        return None
+    embeds = list(compose_embeds) if isinstance(compose_embeds, (list, tuple)) else None
+    if not embeds or not all(torch.is_tensor(e) for e in embeds):
+        raise GsddError(f"compose_embeds must be a list of 1 ... {COMPOSE_MAX_COND - 1} tensors shaped like condition_embed")
+    N = 1 + len(embeds)
+    if N > COMPOSE_MAX_COND:
+        raise GsddError(f"a composed call takes at most {COMPOSE_MAX_COND} conditions, condition_embed included: got {N}")
+    if condition_embed.dim() != 3:
+        raise GsddError(f"a composed call needs condition_embed (B, Te, cond_dim), got {tuple(condition_embed.shape)}")
+    for i, e in enumerate(embeds):
+        if e.shape != condition_embed.shape or e.device != condition_embed.device:
+            raise GsddError(f"compose_embeds[{i}] is {tuple(e.shape)} on {e.device}: must be {tuple(condition_embed.shape)} on "
+                            f"{condition_embed.device}, like condition_embed")
+    if compose_weights is None:
+        raise GsddError(f"compose_embeds needs compose_weights: ({N},) or ({B}, {N}) weights, condition_embed's first")
+    w = torch.as_tensor(compose_weights)
+    if w.is_complex() or w.dtype == torch.bool or tuple(w.shape) not in ((N,), (B, N)):
+        raise GsddError(f"compose_weights must be ({N},) or ({B}, {N}) numbers, got {w.dtype} {tuple(w.shape)}")
+    w = w.detach().cpu().to(torch.float32)
+    if not bool(torch.isfinite(w).all()):
+        raise GsddError("compose_weights must be finite")
+    w = (w.unsqueeze(0).expand(B, N) if w.dim() == 1 else w).contiguous()
+    lens = None
+    if compose_lens is not None:
+        lens = list(compose_lens) if isinstance(compose_lens, (list, tuple)) else None
+        if lens is None or len(lens) != len(embeds):
+            raise GsddError(f"compose_lens must list one ({B},) length vector per extra condition ({len(embeds)})")
+        lens = [check_condition_len(n, B, condition_embed.shape[1], f"compose_lens[{i}]") for i, n in enumerate(lens)]
+    return Compose(tuple(embeds), w, lens)
+
+
+def check_compose_entries(entries, what="compose"):
+    """Validates the glue's list of extra captions: None, or at most COMPOSE_MAX_COND - 1 mappings {text: str, weight: finite number}
+    (nothing else in them).  -> None or a tuple of (text, weight)."""
+    if entries is None:
+        return None
+    if isinstance(entries, (str, bytes)) or not isinstance(entries, collections.abc.Sequence) or not 1 <= len(entries) <= COMPOSE_MAX_COND - 1:
+        raise GsddError(f"{what} must be null or a list of 1 ... {COMPOSE_MAX_COND - 1} {{text, weight}} entries, got {entries!r}")
+    out = []
+    for i, e in enumerate(entries):
+        if not isinstance(e, collections.abc.Mapping) or set(e.keys()) != {"text", "weight"}:
+            raise GsddError(f"{what}[{i}] must be a mapping with exactly the keys text and weight, got {e!r}")
+        text, w = e["text"], e["weight"]
+        if not isinstance(text, str):
+            raise GsddError(f"{what}[{i}].text must be a string, got {text!r}")
+        if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w):
+            raise GsddError(f"{what}[{i}].weight must be a finite number, got {w!r}")
+        out.append((text, float(w)))
+    return tuple(out)
+
+
+def _compose_kwargs(compose):
+    """check_compose's result as `_sample_once` takes it; nothing at all for a plain call."""
+    return {} if compose is None else {"compose": compose}
+
+
 def _known_kwargs(known, dev, sl=slice(None)):
     """check_known's result -> the known / x_known / known_mode keywords of ops.d3pm_step for the clips `sl` of the batch, on `dev`;
     nothing at all without a mask."""
@@ -877,9 +949,12 @@ class _Lane:
     keywords, the graph of every op kind captured so far and what only some programs need: the jump's table and held positions, the
     reveal's plan arrays, counters and candidate buffers.  Built on `st`, after st waits for the caller's stream."""
 
-    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw, cond_len=None, long_tok=None):
+    def __init__(self, dm, plan, st, sl, conds, rep, x0, known, trunc_kw, cond_len=None, long_tok=None, compose_w=None):
         dev, L, K, Bs, tr = dm.device, dm.shape, dm.num_classes - 1, sl.stop - sl.start, dm.transformer
         self.tr, self.plan, self.st, self.rep, self.guided, self.graphs = tr, plan, st, rep, dm._guided, {}
+        # a composed lane (rep = N + 1 copies: the N conditions, then the null condition): its clips' (Bs, N) weights, a device buffer
+        # every captured op reads
+        self.compose_w, self.Bs, self.L = None if compose_w is None else compose_w.to(dev).contiguous(), Bs, L
         self.trunc_kw = trunc_kw                    # a launch constant of both step kernels: a captured graph records it
         self.sched, self.K, self.T = dm._sched(), K, dm.num_timesteps
         self.guidance, self.seed = float(dm.guidance_scale), dm.noise_seed
@@ -927,6 +1002,8 @@ class _Lane:
 
     def denoise(self):                          # -> the conditional and the unconditional logits of the lane's tokens at t2
         logits = self.tr.run(self.tok, self.condv, self.Te, self.t2, self.ws, rep=self.rep, stream=self.st, cond_len=self.cond_len)
+        if self.compose_w is not None:          # the composed row, into block 0 of the logits: the step reads it alone
+            return ops.d3pm_compose(logits, self.compose_w, n_cond=self.rep - 1, B=self.Bs, L=self.L, K=self.K, stream=self.st), None
         return logits[:self.M], (logits[self.M:] if self.rep == 2 else logits[:self.M]) if self.guided else None
 
     def plain_step(self, post_skip):
@@ -1071,13 +1148,14 @@ class DiffusionTransformer(nn.Module):
             raise GsddError(f"the null condition must be (Te, cond_dim) = {(Te, cond_dim)} or (1, Te, cond_dim), got {tuple(null_cond.shape)}")
         return n.detach().float().contiguous()
 
-    def _cf_embed(self, condition_embed, cf_condition_embed):
-        """The unconditional condition of a guided sampling call: the caller's, else (learnable_cf) the learned null rows repeated over
-        the batch."""
-        if cf_condition_embed is not None or not self._guided:
+    def _cf_embed(self, condition_embed, cf_condition_embed, composed=False):
+        """The unconditional condition of a guided or composed sampling call: the caller's, else (learnable_cf) the learned null rows
+        repeated over the batch."""
+        if cf_condition_embed is not None or not (self._guided or composed):
             return cf_condition_embed
         if not self.learnable_cf:
-            raise GsddError("guided sampling (guidance_scale != 1) needs cf_condition_embed")
+            raise GsddError("a composed call (compose_embeds) needs the unconditional condition: cf_condition_embed, or a model with "
+                            "learnable_cf" if composed else "guided sampling (guidance_scale != 1) needs cf_condition_embed")
         cond = condition_embed if condition_embed.dim() == 3 else condition_embed.unsqueeze(1)
         B, Te, cd = cond.shape
         return self.null_condition(Te, cd).to(cond.device).unsqueeze(0).expand(B, Te, cd).contiguous()
@@ -1134,7 +1212,8 @@ class DiffusionTransformer(nn.Module):
     def sample(self, condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=None,
                filter_ratio=0.5, temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                print_log=True, use_graph=True, trace=None, *, known_mask=None, known_mode="renoise", resample_jump=None,
-               resample_times=1, condition_len=None, cf_condition_len=None, **kwargs):
+               resample_times=1, condition_len=None, cf_condition_len=None, compose_embeds=None, compose_weights=None,
+               compose_lens=None, **kwargs):
         """diffusion_transformer.py:568-644.  The arguments pick a plan (`sample_plan`, `resample_plan`, `_purity_plan`); `_sample_once`
         executes the plan's program -- its op kinds in order -- as `issue_schedule` lays it out over the lanes (a lane runs a kind
         eagerly once, captures it into a hipGraph if it recurs and replays it from then on; use_graph=False or a `trace` list: every
@@ -1160,11 +1239,20 @@ class DiffusionTransformer(nn.Module):
         conditioned on the first condition_len[b] rows of condition_embed[b] only -- the rows behind them are caption padding, which
         the cross-attention never reads -- and its unconditional copy on the first cf_condition_len[b] rows of cf_condition_embed[b]
         (default Te: the null embedding is full length).  They work with every plan.  The positional condition_mask stays ignored.
-        None: the call without them, launch for launch."""
+        None: the call without them, launch for launch.
+        compose_embeds / compose_weights / compose_lens: composed guidance (`check_compose`) -- compose_embeds lists 1 ... 3 further
+        conditions shaped like condition_embed, compose_weights the (N,) or (B, N) weights of all N = 1 + len(compose_embeds)
+        conditions, condition_embed's first (any finite number: a negative weight is a negative prompt), compose_lens one (B,) length
+        vector per extra condition (default: full length).  Every denoiser pass then runs N + 1 stacked copies and one launch
+        (gsdd_d3pm_compose) folds their rows into e = x_u + sum_i w_i (x_i - x_u), which the step reads without a second row.  The
+        weights are the scales: guidance_scale plays no part, the unconditional condition is always needed, and the copies are never
+        deduplicated.  They work with every plan.  None: the call without them, launch for launch."""
         kwargs = dict(kwargs, **_len_kwargs(condition_len, cf_condition_len))
+        compose = check_compose(compose_embeds, compose_weights, compose_lens, condition_embed, self._batch_of(condition_token, kwargs))
+        kwargs.update(_compose_kwargs(compose))
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
         start_step = int(self.num_timesteps * filter_ratio)
-        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed, compose is not None)      # (None + learnable_cf: the learned null rows)
         if isinstance(self.prior_rule, bool) or self.prior_rule not in (0, 1, 2):
             raise GsddError(f"prior_rule must be 0, 1 or 2, got {self.prior_rule!r}")
         known = None if known_mask is None else check_known(known_mask, content_token, known_mode, B=self._batch_of(condition_token, kwargs),
@@ -1189,15 +1277,17 @@ class DiffusionTransformer(nn.Module):
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None, print_log=True,
                     skip_step=1, *, cf_condition_embed=None, use_graph=True, trace=None, known_mask=None, known_mode="renoise",
-                    condition_len=None, cf_condition_len=None, **kwargs):
+                    condition_len=None, cf_condition_len=None, compose_embeds=None, compose_weights=None, compose_lens=None, **kwargs):
         """VQ-Diffusion's skip-step sampler (diffusion_transformer.py:648-713): the denoiser runs at t = T-1, T-1-(1+s), ..., then 0
         (`sample_plan`), and each step's posterior jumps to t - s (for t > s) across the skipped levels.  From all-[MASK] only, as the
         reference asserts.  The reference passes cf_predict_start three of its four arguments; the
         unconditional embedding is the keyword cf_condition_embed here.  skip_step = 0 is sample(filter_ratio=0), bit for bit.
         known_mask / known_mode: as in sample(); a known position is re-noised to the level the step's posterior jumps to.
-        condition_len / cf_condition_len: as in sample()."""
+        condition_len / cf_condition_len, compose_embeds / compose_weights / compose_lens: as in sample()."""
         T = self.num_timesteps
         kwargs = dict(kwargs, **_len_kwargs(condition_len, cf_condition_len))
+        compose = check_compose(compose_embeds, compose_weights, compose_lens, condition_embed, self._batch_of(condition_token, kwargs))
+        kwargs.update(_compose_kwargs(compose))
         if "resample_jump" in kwargs or "resample_times" in kwargs:
             raise GsddError("sample_fast takes no resample_jump / resample_times: the skip-step chain has no resampling jumps (use sample)")
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
@@ -1209,7 +1299,7 @@ class DiffusionTransformer(nn.Module):
                             "must be 0 (diffusion_transformer.py:686)")
         if not _is_int(skip_step) or skip_step < 0:
             raise GsddError(f"skip_step must be a non-negative int, got {skip_step!r}")
-        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)      # (None + learnable_cf: the learned null rows)
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed, compose is not None)      # (None + learnable_cf: the learned null rows)
         if return_logits:
             raise NotImplementedError("return_logits is unused by the reference call sites")
         return self._sample_checked(sample_plan(T, skip_step=int(skip_step)), condition_token, condition_embed, cf_condition_embed,
@@ -1218,7 +1308,8 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample_long(self, condition_token, condition_mask, condition_embed, cf_condition_embed, *, latent_shape, n_frames, overlap,
                     content_token=None, known_mask=None, known_mode="renoise", skip_step=None, resample_jump=None, resample_times=1,
-                    condition_len=None, cf_condition_len=None, use_graph=True, trace=None, filter_ratio=0, **kwargs):
+                    condition_len=None, cf_condition_len=None, compose_embeds=None, compose_weights=None, compose_lens=None,
+                    use_graph=True, trace=None, filter_ratio=0, **kwargs):
         """A clip of n_frames latent frames, longer than the model's window of F = latent_shape[0]: the sliding-window rollout of
         `long_plan` as one program of the executor.  Window 0 is the call sample() -- or, with skip_step, sample_fast() -- would make
         (content_token / known_mask apply to it alone: continuing a real clip); every later window keeps the last `overlap` frames
@@ -1231,6 +1322,7 @@ class DiffusionTransformer(nn.Module):
         repeat on the bf16x3 kernel they are the repeat's counters).  On that error path alone the call differs from the chain: the
         whole rollout has run and noise_stream has advanced by all its draws, where the chain's check_known would have stopped before
         the next window.
+        compose_embeds / compose_weights / compose_lens: as in sample(); the composed conditions serve all windows.
         n_frames == F is sample() / sample_fast() itself.  Not with prior_rule > 0, filter_ratio > 0, or skip_step together with
         resampling jumps.  -> {"content_token": (B, n_frames h w) int64, "windows": W}"""
         T, K = self.num_timesteps, self.num_classes - 1
@@ -1262,25 +1354,29 @@ class DiffusionTransformer(nn.Module):
             if resample is not None and known_mask is None:      # (window 0 of a resampled rollout: the jumps with nothing known)
                 content_token, known_mask = torch.zeros((B, L), dtype=torch.int64), torch.zeros((L,), dtype=torch.bool)
             known_kw = {} if known_mask is None else {"known_mask": known_mask, "known_mode": known_mode}
+            # the composed keywords as they came, nothing at all without them: the call below validates them
+            compose_kw = {k: v for k, v in (("compose_embeds", compose_embeds), ("compose_weights", compose_weights),
+                                            ("compose_lens", compose_lens)) if v is not None}
             if skip_step is not None:
                 out = self.sample_fast(condition_token, condition_mask, condition_embed, content_token=content_token, filter_ratio=0,
                                        skip_step=int(skip_step), cf_condition_embed=cf_condition_embed, use_graph=use_graph, trace=trace,
-                                       **known_kw, **lens, **kwargs)
+                                       **known_kw, **lens, **compose_kw, **kwargs)
             else:
                 if resample is not None:
                     known_kw.update(resample_jump=resample_jump, resample_times=resample_times)
                 out = self.sample(condition_token, condition_mask, condition_embed, cf_condition_embed, content_token=content_token,
-                                  filter_ratio=0, use_graph=use_graph, trace=trace, **known_kw, **lens, **kwargs)
+                                  filter_ratio=0, use_graph=use_graph, trace=trace, **known_kw, **lens, **compose_kw, **kwargs)
             return {"content_token": out["content_token"], "windows": 1}
+        compose = check_compose(compose_embeds, compose_weights, compose_lens, condition_embed, B)
         trunc = check_truncation_rate(getattr(self, "truncation_rate", None))
-        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed)
+        cf_condition_embed = self._cf_embed(condition_embed, cf_condition_embed, compose is not None)
         known = (None, None, KNOWN_MODES[known_mode])
         if known_mask is not None:
             known = check_known(known_mask, content_token, known_mode, B=B, L=L, K=K)
         # the long buffer: made once, on the caller's stream, before the lanes fork; every lane writes its own rows
         long_tok = torch.full((B, plan.n_frames * hw), K, dtype=torch.int64, device=self.device)
         out = self._sample_checked(plan, condition_token, condition_embed, cf_condition_embed, use_graph=use_graph, trace=trace,
-                                   truncation_rate=trunc, known=known, long_tok=long_tok, **lens, **kwargs)
+                                   truncation_rate=trunc, known=known, long_tok=long_tok, **lens, **_compose_kwargs(compose), **kwargs)
         bad = sum(int(c.item()) for c in self._bad_counters)      # (the lanes of the run that counted: _sample_checked's last)
         if bad:
             raise GsddError(f"sample_long: {bad} token(s) outside [0, {K}) in the overlap frames of a finished window ([MASK] = {K} is "
@@ -1304,7 +1400,7 @@ class DiffusionTransformer(nn.Module):
 
     def _sample_once(self, plan, condition_token, condition_embed, cf_condition_embed, content_token=None, return_logits=False,
                      use_graph=True, trace=None, truncation_rate=None, known=None, condition_len=None, cf_condition_len=None,
-                     long_tok=None, **kwargs):
+                     long_tok=None, compose=None, **kwargs):
         """Runs plan.program once: resolves the guidance copies and the lane count, builds the lanes, issues `issue_schedule`'s
         entries and joins the lanes' streams."""
         dev = self.device
@@ -1312,7 +1408,7 @@ class DiffusionTransformer(nn.Module):
             raise GsddError("sampling runs on the HIP path only: move the module to a ROCm device")
         B, L, K = self._batch_of(condition_token, kwargs), self.shape, self.num_classes - 1
         cond = condition_embed.to(dev).float()
-        cf = cf_condition_embed.to(dev).float().type_as(cond) if self._guided else None
+        cf = cf_condition_embed.to(dev).float().type_as(cond) if (self._guided or compose is not None) else None
         # Identical conditional and unconditional embeddings -- the reference's shipped inference path: DiscreteDiffusion.forward zeroes
         # both (discrete_diffusion.py:25, :49) -- make the two guidance copies the same computation on the same inputs, bit for bit.
         # Then one copy runs and the step kernel reads its logits on both sides of log p_u + s (log p_c - log p_u): the same values
@@ -1323,10 +1419,23 @@ class DiffusionTransformer(nn.Module):
         if condition_len is not None or cf_condition_len is not None:
             if cond.dim() != 3:
                 raise GsddError(f"condition_len needs condition_embed (B, Te, cond_dim), got {tuple(cond.shape)}")
-            lens = _guidance_lens(condition_len, cf_condition_len, B, cond.shape[1], self._guided)
-        same_cond = (self._guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape
+            lens = _guidance_lens(condition_len, cf_condition_len, B, cond.shape[1], self._guided or compose is not None)
+        same_cond = (compose is None and self._guided and os.environ.get("GSDD_CFG_DEDUPE", "1") != "0" and cf.shape == cond.shape
                      and bool(torch.equal(cond, cf)) and (lens is None or bool(torch.equal(lens[0], lens[1]))))
         rep = 2 if (self._guided and not same_cond) else 1
+        if compose is not None:
+            # A composed call: rep = N + 1 copies, cat([c_0, ..., c_{N-1}, u]), never deduplicated; the lengths stack the same way
+            # (an extra condition's default is full length, as the unconditional copy's)
+            if cf.shape != cond.shape:
+                raise GsddError(f"a composed call needs cf_condition_embed shaped like condition_embed {tuple(cond.shape)}, got {tuple(cf.shape)}")
+            extra = [e.to(dev).float() for e in compose.embeds]
+            same_cond, rep, Te = False, len(extra) + 2, cond.shape[1]
+            if (lens is not None or compose.lens is not None) and Te > 1:
+                full = torch.full((B,), Te, dtype=torch.int32)
+                len_c, len_u = (full, full) if lens is None else (lens[0], full if lens[1] is None else lens[1])
+                lens = [len_c, *(compose.lens if compose.lens is not None else [full] * len(extra)), len_u]
+            else:
+                lens = None
         x0 = None
         if plan.q_sample:
             x0 = content_token.to(dev).long().reshape(B, L).contiguous()
@@ -1354,6 +1463,12 @@ class DiffusionTransformer(nn.Module):
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
                     sl = slice(len(lane_list) * (B // lanes), (len(lane_list) + 1) * (B // lanes))
+                    if compose is not None:
+                        conds = torch.cat([cond[sl], *(e[sl] for e in extra), cf[sl]], 0)
+                        lane_len = None if lens is None else torch.cat([n[sl] for n in lens])
+                        lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate), lane_len, long_tok,
+                                               compose_w=compose.weights[sl]))
+                        continue
                     conds = torch.cat([cond[sl], cf[sl]], 0) if rep == 2 else cond[sl]
                     lane_len = None if lens is None else (torch.cat([lens[0][sl], lens[1][sl]]) if rep == 2 else lens[0][sl])
                     lane_list.append(_Lane(self, plan, st, sl, conds, rep, x0, known, _trunc_kwargs(truncation_rate), lane_len, long_tok))
@@ -1582,14 +1697,27 @@ class DiscreteDiffusion(nn.Module):
     sample_long_frames: null, or the number of latent frames of a long clip (at least the model's window): the render path
     (src/models/base.py) and sample_videos(long_frames=) then sample it with DiffusionTransformer.sample_long -- windows that share
     sample_long_overlap latent frames -- and decode it with VQVAE.decode_long, sample_long_blend "linear" / "keep" / "replace" across
-    the overlaps.  forward(do_inference=True) keeps sampling one window.  Not with sample_prior_rule > 0."""
+    the overlaps.  forward(do_inference=True) keeps sampling one window.  Not with sample_prior_rule > 0.
+    sample_compose: null, or a list of at most three {text, weight} entries shared by every clip of a batch: composed guidance
+    (DiffusionTransformer.sample's compose_embeds / compose_weights) -- a clip is sampled under x_u + w_0 (x_caption - x_u) +
+    sum_i weight_i (x_text_i - x_u) in log-probability space, a negative weight pushing away from its text (a negative prompt).
+    sample_compose_caption_weight is w_0; null takes the diffusion model's guidance_scale.  Not with zero_text_emb: true."""
 
     def __init__(self, textencoder, diffusion_model, zero_text_emb=True, sample_skip_step=None, sample_prior_rule=None,
                  sample_prior_weight=None, sample_prior_ps=None, sample_prior_scale_schedule=False, sample_truncation_rate=None,
                  sample_condition_frames=None, sample_known_mode="renoise", sample_resample_jump=None, sample_resample_times=None,
                  sample_long_frames=None, sample_long_overlap=4, sample_long_blend="linear",
+                 sample_compose=None, sample_compose_caption_weight=None,
                  train_cond_drop_prob=None, mask_text_padding=False, **kwargs):
         super().__init__()
+        self.sample_compose = check_compose_entries(sample_compose, "sample_compose")
+        if self.sample_compose is not None and zero_text_emb:
+            raise GsddError("sample_compose cannot be combined with zero_text_emb: true -- every caption would be the same zero vectors; "
+                            "set zero_text_emb: false")
+        w = sample_compose_caption_weight
+        if w is not None and (isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w)):
+            raise GsddError(f"sample_compose_caption_weight must be null or a finite number, got {w!r}")
+        self.sample_compose_caption_weight = None if w is None else float(w)
         if sample_long_frames is not None and not (_is_int(sample_long_frames) and sample_long_frames >= 2):
             raise GsddError(f"sample_long_frames must be null or an int >= 2 (latent frames of the long clip), got {sample_long_frames!r}")
         if not (_is_int(sample_long_overlap) and sample_long_overlap >= 1):
@@ -1758,16 +1886,22 @@ class DiscreteDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample_videos(self, texts, autoencoder, latent_shape=None, text_emb=None, known_tokens=None, known_mask=None, text_len=None,
-                      long_frames=None):
+                      long_frames=None, compose=None):
         """The inference branch of forward (discrete_diffusion.py:44-62): text -> tokens -> decoded clips.
         known_tokens (B, L) / known_mask ((B, L) or (L,) bool): clean tokens to keep at the mask's positions (the sampler's
         content_token / known_mask, with sample_known_mode); without a mask the call is the plain one.
         text_len goes with text_emb: the captions' (B,) condition lengths (the sampler's condition_len), None for none; without
         text_emb both come from the provider.
         long_frames: None, or the latent frames n of a long clip: sample_long with sample_long_overlap (the mask, if any, applies to
-        its first window), then decode_long with sample_long_blend -> (B, 3, n d_t, H, W); last_content_token is the long grid."""
+        its first window), then decode_long with sample_long_blend -> (B, 3, n d_t, H, W); last_content_token is the long grid.
+        compose: None (then sample_compose), or that list for this call: every clip is sampled under its own caption at
+        sample_compose_caption_weight (null: the diffusion model's guidance_scale) composed with the listed texts at their weights
+        (the sampler's compose_embeds / compose_weights, with the texts' lengths under mask_text_padding)."""
         dev = autoencoder.device
         B = len(texts)
+        compose = self.sample_compose if compose is None else check_compose_entries(compose)
+        if compose is not None and self.zero_text_emb:
+            raise GsddError("compose cannot be combined with zero_text_emb: every caption would be the same zero vectors")
         if text_emb is None:
             text_emb, text_len = self._text(texts, dev, return_lengths=True)
         if self.zero_text_emb:
@@ -1800,6 +1934,12 @@ class DiscreteDiffusion(nn.Module):
                                 resample_times=1 if self.sample_resample_times is None else self.sample_resample_times)
         if text_len is not None:
             known_kw = dict(known_kw, condition_len=text_len)          # (the unconditional copy stays full length)
+        if compose is not None:
+            w0 = dm.guidance_scale if self.sample_compose_caption_weight is None else self.sample_compose_caption_weight
+            extra = [self._text([text] * B, dev, return_lengths=True) for text, _ in compose]
+            known_kw = dict(known_kw, compose_embeds=[e for e, _ in extra], compose_weights=[float(w0)] + [w for _, w in compose])
+            if text_len is not None and all(n is not None for _, n in extra):
+                known_kw["compose_lens"] = [n for _, n in extra]
         shape = tuple(latent_shape if latent_shape is not None else autoencoder.latent_shape)
         if long_frames is not None:
             long_kw = dict({"known_mode": self.sample_known_mode}, **known_kw)

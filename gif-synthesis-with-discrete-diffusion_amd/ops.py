@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib as abi
-from ._lib import GemmDesc, GsddError, JumpDesc, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, _is_int, check, lib, ptr, stream_ptr
+from ._lib import ComposeDesc, GemmDesc, GsddError, JumpDesc, LayerDesc, PurityDesc, PuritySelectDesc, StepDesc, TrainDesc, _is_int, check, lib, ptr, stream_ptr
 
 ACT_NONE, ACT_RELU, ACT_GELU2 = 0, 1, 2
 
@@ -460,6 +460,36 @@ def d3pm_forward_jump(tok_in, tok_out, table, t_dev, stream_dev, *, K, T, jump, 
     d.t_dev, d.seed, d.stream_dev, d.row0 = ptr(t_dev), seed, ptr(stream_dev), row0
     check(lib().gsdd_d3pm_forward_jump(C.byref(d), stream_ptr(stream)))
     return tok_out
+
+
+def d3pm_compose(logits, weights, *, n_cond, B, L, K, out=None, stream=None):
+    """out = x_u + sum_i weights[b][i] (x_i - x_u) per position, x = clamp(log_softmax(.), -70, 0) (gsdd_d3pm_compose, include/gsdd.h):
+    what a reverse step then reads as logits_c with logits_u = None.  logits: the denoiser's stacked f32 output, n_cond + 1 blocks of
+    B L rows of K, the conditions first and the null condition last; weights: device f32 (B, n_cond); out: None (block 0 of logits,
+    in place) or a (B L, K) f32 tensor clear of logits.  -> out, (B L, K)."""
+    if not _is_int(n_cond) or not 1 <= n_cond <= abi.COMPOSE_MAX_COND:
+        raise GsddError(f"d3pm_compose: n_cond must be an int in [1, {abi.COMPOSE_MAX_COND}], got {n_cond!r}")
+    if not all(_is_int(v) and v >= 1 for v in (B, L, K)):
+        raise GsddError(f"d3pm_compose: B, L and K must be positive ints, got {B!r}, {L!r}, {K!r}")
+    rows = B * L
+    if not torch.is_tensor(logits):
+        raise GsddError(f"d3pm_compose: logits must be a tensor, got {type(logits).__name__}")
+    if logits.dtype != torch.float32 or logits.numel() != (n_cond + 1) * rows * K or not logits.is_contiguous():
+        raise GsddError(f"d3pm_compose: logits must be a contiguous float32 tensor of {n_cond + 1} blocks of {(rows, K)}, got "
+                        f"{tuple(logits.shape)} {logits.dtype}")
+    if not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (B, n_cond) or not weights.is_contiguous():
+        raise GsddError(f"d3pm_compose: weights must be a contiguous float32 {(B, n_cond)} tensor")
+    if weights.device != logits.device:
+        raise GsddError(f"d3pm_compose: weights live on {weights.device}, logits on {logits.device}")
+    if out is None:
+        out = logits.view(n_cond + 1, rows, K)[0]
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, K) or not out.is_contiguous() or out.device != logits.device:
+        raise GsddError(f"d3pm_compose: out must be a contiguous float32 {(rows, K)} tensor on {logits.device}, got {tuple(out.shape)} {out.dtype}")
+    d = ComposeDesc()
+    d.logits, d.weights, d.out = ptr(logits), ptr(weights), ptr(out)
+    d.n_cond, d.B, d.L, d.K = n_cond, B, L, K
+    check(lib().gsdd_d3pm_compose(C.byref(d), stream_ptr(stream)))
+    return out
 
 
 def _train_desc(logits, x0, xt, t_dev, pt, sched, K, T, mask_weight, aux_weight, adaptive_aux):

@@ -34,7 +34,7 @@ extern "C" {
 const char* gsdd_last_error(void);
 int gsdd_version(void);
 /* sizeof of a descriptor struct as this build of the library sees it (which: 0 gsdd_gemm_desc, 1 gsdd_layer_desc, 2 gsdd_step_desc,
- * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc, 7 gsdd_jump_desc, 8 gsdd_optim_state; anything else, 6 included: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
+ * 3 gsdd_train_desc, 4 gsdd_purity_desc, 5 gsdd_purity_select_desc, 7 gsdd_jump_desc, 8 gsdd_optim_state, 10 gsdd_compose_desc; anything else, 6 and 9 included: -1).  A binding checks its own struct sizes against these when it loads the library, so that a
  * library built from another revision of this header fails at load time instead of misreading a descriptor. */
 int64_t gsdd_abi_sizeof(int which);
 
@@ -477,6 +477,31 @@ typedef struct {
     int64_t row0;               /* global row (position) offset of this shard                                                   */
 } gsdd_jump_desc;
 int gsdd_d3pm_forward_jump(const gsdd_jump_desc* d, void* stream);
+
+/* Composed guidance: several weighted conditions per clip (conjunctions, negative prompts, per-clip weight sweeps) folded into the one
+ * logits row a reverse step reads.  A clip has conditions c_0 ... c_{N-1} (1 <= N <= GSDD_COMPOSE_MAX_COND), weights w[b][0 ... N-1]
+ * (any finite float, negative allowed) and the null condition u.  Per position and class,
+ *   x_i = clamp(log_softmax(logits_i), -70, 0)     i = 0 ... N-1, and x_u likewise (predict_start: the fp64 sum of gsdd_d3pm_step,
+ *                                                  the same bits the step computes from the same row)
+ *   e   = x_u + sum_i w_i (x_i - x_u)              f32, accumulated in the order i = 0, 1, ...; the first term is the step's own mix,
+ *                                                  x_u + w_0 * (x_0 - x_u); no fused multiply-add
+ * The reverse step that follows runs with logits_c = e and logits_u = NULL: its log_softmax turns e into clamp(e - logsumexp(e), -70, 0),
+ * i.e. cf_predict_start (diffusion_transformer.py:245-247) with the sum over i in place of the single term.
+ *   - N = 1, w = s is gsdd_d3pm_step's guided row up to the rounding of the last log-sum-exp (fp64 here, f32 in the two-way kernel):
+ *     close to a guided call, not bit-identical to it.
+ *   - Weights that sum to 1 cancel x_u: (s, 1 - s) on (caption, negative caption) give x_neg + s (x_cap - x_neg).
+ *   - gsdd_step_desc.guidance plays no part: the weights are the scales.  The unconditional row is always needed, also when they sum to 1.
+ * `weights` is read on the device, so a captured graph replays whatever the buffer holds at launch.  One launch, no workspace, no
+ * memset, no host synchronisation. */
+#define GSDD_COMPOSE_MAX_COND 4
+typedef struct {
+    const float* logits;        /* (n_cond + 1) blocks of [B*L][K] rows: conditions 0 ... n_cond-1, then the null condition (the
+                                   order the denoiser leaves for a batch stacked as cat([c_0, ..., c_{N-1}, u])); 16-byte aligned */
+    int n_cond, B, L, K;        /* 1 <= n_cond <= 4; K a multiple of 4 in [4, 8192]                                             */
+    const float* weights;       /* device float[B][n_cond]                                                                      */
+    float* out;                 /* [B*L][K]; may be block 0 of `logits` (out == logits), otherwise it must not overlap `logits` */
+} gsdd_compose_desc;
+int gsdd_d3pm_compose(const gsdd_compose_desc* d, void* stream);
 
 /* Training objective, forward value: _train_loss + the loss tail of forward (diffusion_transformer.py:391-457, :548)
  * from the denoiser logits of x_t.  Per-position scratch (kl, nll, aux: float[B*L]; x0_recon, xt1_recon: int64[B*L]),

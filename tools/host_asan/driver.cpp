@@ -286,6 +286,38 @@ int main() {
             EXPECT(gsdd_d3pm_forward_jump(nullptr, st), GSDD_E_ARG, false);
             EXPECT(gsdd_d3pm_forward_jump(&j, st), GSDD_OK, true);
         }
+        {   // composed guidance: every class width and condition count, in place and into a buffer of its own; bad arguments
+            gsdd_compose_desc c;
+            std::memset(&c, 0, sizeof c);
+            float* lg = devp(1 << 20);
+            c.logits = lg; c.weights = devp(); c.out = devp(); c.n_cond = 2; c.B = 2; c.L = 3; c.K = 8;
+            const size_t blk = (size_t)c.B * c.L * c.K;
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true);
+            c.out = lg;                                                  // block 0: in place
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true);
+            c.out = lg + 3 * blk;                                        // right behind the last block
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true);
+            for (size_t off : {blk, 2 * blk, (size_t)4, 3 * blk - 4}) { c.out = lg + off; EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false); }
+            c.out = lg + 1;                                              // not 16-byte aligned
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false);
+            c.out = lg;
+            for (int n : {1, 3, 4}) { c.n_cond = n; EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true); }
+            for (int bad : {0, -1, 5}) { c.n_cond = bad; EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false); }
+            c.n_cond = 2;
+            for (int k : {4, 256, 1020, 2048, 4092, 4096, 8192}) { c.K = k; EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true); }
+            for (int bad : {0, 2, 30, 8196, -4}) { c.K = bad; EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false); }
+            c.K = 8; c.logits = nullptr;
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false);
+            c.logits = lg; c.weights = nullptr;
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false);
+            c.weights = devp(); c.out = nullptr;
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false);
+            c.out = lg; c.B = 0;
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_E_ARG, false);
+            c.B = 2;
+            EXPECT(gsdd_d3pm_compose(nullptr, st), GSDD_E_ARG, false);
+            EXPECT(gsdd_d3pm_compose(&c, st), GSDD_OK, true);
+        }
         {   // the training step's gradient reductions, in the fast form and in the reproducible one (gsdd_set_deterministic)
             float *dh = devp(1 << 25), *xr = devp(1 << 25), *stats = devp(), *gam = devp(), *dxo = devp(1 << 25), *dg = devp(), *dbt = devp();
             float *dW = devp(), *dbias = devp(), *osum = devp(), *dtab = devp(), *emb = devp(), *wad = devp(), *demb = devp(), *dpos = devp(1 << 21);
